@@ -8,12 +8,16 @@ resident in HBM before timing. One step = one full decode of that stream by libd
 (frame split + Change decode into SoA columns, decode.js:144-262 + messages/index.js:5)
 plus, for N > 1, the RCCL all-gather of per-stream stats and the global index scan.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames F] [--dump-outputs DIR] [--full]
     torchrun --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
-Prints ONE JSON line (rank 0). `roofline` prices the decode kernel from HIP events on
-the libdrp stream; `cpu_baseline` times the C restatement of the reference (oracle/) on
-a bounded sample on this host's cores.
+Prints ONE JSON line (rank 0). A plain run sets up, warms up (checking the decoded columns
+against the generator), times the K steps and prints the line; `roofline` prices the decode
+kernel from the HIP events libdrp records around it in those same steps. --dump-outputs DIR
+also writes what the last timed step computed as DIR/<name>.npy (dump_outputs). --full adds
+every other leg: the c4 / c5 / c3 sub-lines, `cpu_baseline*` (the C restatement of the
+reference, oracle/, on a bounded sample on this host's cores), the H2D rate, the Node path,
+C5's decode-after-C2 leg and C3's HBM-resident roofline leg.
 """
 import argparse
 import ctypes as C
@@ -72,6 +76,57 @@ def alloc_outputs(cap, dev):
     for k in drp_amd.COLS64:
         o[k] = torch.empty(cap, dtype=torch.int64, device=dev)
     return o
+
+
+DUMP_ROWS = 1 << 18       # rows of the frame table --dump-outputs keeps
+DUMP_ELEMS = 1 << 20      # elements it keeps of any other output array (under 64 MB in all)
+CHANGE_COLS = drp_amd.COLS32 + drp_amd.COLS64 + ["flags"]
+
+
+def _dump_pick(n, limit, seed):
+    """Every index below n, or a fixed sorted sample of at most `limit` of them (seeded: the same
+    rows in every run with the same arguments)."""
+    if n <= limit:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(seed).integers(0, n, size=limit, dtype=np.int64))
+
+
+def _dump_take(v, idx):
+    """v[idx] on the host: float32 for byte arrays, float64 otherwise (exact: every value the
+    benchmark's workloads decode is an integer below 2^53)."""
+    if isinstance(v, torch.Tensor):
+        v = v[torch.from_numpy(idx).to(v.device)].cpu().numpy()
+    else:
+        v = np.asarray(v)[idx]
+    return v.astype(np.float32 if v.dtype.itemsize == 1 else np.float64)
+
+
+def dump_outputs(path, table, n, result, **arrays):
+    """--dump-outputs: what the last timed step left in the caller's buffers, as <path>/<name>.npy.
+    `table`: the frame table's columns (torch or numpy, n rows), one file per column. Past
+    DUMP_ROWS rows a seeded sample of rows is kept and rows.npy holds their indices. The Change
+    columns are written as 0 on rows that are not Changes (the decoder does not write them there).
+    `result`: the per-stream results (a 2-D array, result.npy). `arrays`: further 1-D outputs,
+    each whole or as a seeded sample of DUMP_ELEMS elements with its indices in <name>_index.npy."""
+    os.makedirs(path, exist_ok=True)
+    idx = _dump_pick(n, DUMP_ROWS, seed=20)
+    np.save(os.path.join(path, "rows.npy"), idx.astype(np.float64))
+    got = {k: _dump_take(v, idx) for k, v in table.items()}
+    change = (got["type"].astype(np.uint8) & 0x3F) == drp_amd.TYPE_CHANGE
+    for k, v in got.items():
+        np.save(os.path.join(path, k + ".npy"), np.where(change, v, 0).astype(v.dtype) if k in CHANGE_COLS else v)
+    np.save(os.path.join(path, "result.npy"), np.asarray(result, dtype=np.float64))
+    for k, v in arrays.items():
+        idx = _dump_pick(len(v), DUMP_ELEMS, seed=21)
+        np.save(os.path.join(path, k + "_index.npy"), idx.astype(np.float64))
+        np.save(os.path.join(path, k + ".npy"), _dump_take(v, idx))
+
+
+def stream_results(res):
+    """The StreamResult records of a device decode as a float64 array, one row per stream
+    (every field but the reserved one, in declaration order)."""
+    r = np.frombuffer(res.cpu().numpy().tobytes(), dtype=np.dtype(drp_amd.StreamResult))
+    return np.stack([r[f].astype(np.float64) for f, _ in drp_amd.StreamResult._fields_ if f != "reserved"], axis=1)
 
 
 def verify_c2(o, res, nframes, dev):
@@ -373,11 +428,12 @@ def verify_c5(cols, heap, wire, o, res, n, dev, samples=256):
             assert torch.equal(wire[po + off_w:po + off_w + ln], heap[off_h:off_h + ln]), i
 
 
-def run_c5(args, dev, rank=0, world=1, steps=None, warmup=None, cpu=True):
+def run_c5(args, dev, rank=0, world=1, steps=None, warmup=None, cpu=True, dump=None):
     """C5: batched encode -> decode round trip of 1M Changes with 4 KB values per step per GPU
     (BASELINE configs[4]: 8 x MI355X); each rank round-trips its own rows (weak scaling), then the
     32 B per-stream stats are all-gathered (drp_index_allgather over RCCL; gloo only to rehearse
-    ranks on one GPU). value = Changes round-tripped per second, whole job. Returns rank 0's line."""
+    ranks on one GPU). value = Changes round-tripped per second, whole job. Returns rank 0's line.
+    dump: rank 0 writes the last timed step's wire, frame offsets and decoded table there."""
     dist = world > 1
     steps = args.steps if steps is None else steps
     warmup = args.warmup if warmup is None else warmup
@@ -438,10 +494,12 @@ def run_c5(args, dev, rank=0, world=1, steps=None, warmup=None, cpu=True):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if dump and rank == 0:
+        dump_outputs(dump, outs, n, stream_results(res), wire=wire, frame_off=foff)
     # the same context right after a dense C2 batch: the claims form is chosen per launch on the
     # device (walk_sync's density sample), not from the context's previous decode
     after_c2 = None
-    if rank == 0 and not args.no_after_c2:
+    if rank == 0 and args.full and not args.no_after_c2:
         nf2 = 10_000_000
         w2 = c2_on_device(nf2, seed=99, dev=dev)
         so2 = torch.tensor([0, w2.numel()], dtype=torch.int64, device=dev)
@@ -579,7 +637,7 @@ def c3_device_leg(pinned, nf, dev, steps, warmup):
     return float(np.mean(ms))
 
 
-def run_c3(args, dev, steps, warmup, cpu):
+def run_c3(args, dev, steps, warmup, cpu, dump=None):
     """C3 through the host-batch path: a ~1 GiB C3 stream in pinned host memory decoded by
     drp_decode_batch (what the Node addon runs per batch) with blob skipping: only the pieces
     around the blobs' headers are staged into HBM, the blob payloads stay in host memory as
@@ -588,7 +646,9 @@ def run_c3(args, dev, steps, warmup, cpu):
     is decoded as it lands (drp_api.hip pipe_chunk: one piece per 128 MiB chunk, hidden behind the
     PCIe copy but for the last), so the roofline prices the device kernels on their own: the same
     wire resident in HBM, decoded in one launch sequence per step (args.c3_leg "device": that leg
-    only, for the PMC passes of scripts/gpu_pmc.sh)."""
+    only, for the PMC passes of scripts/gpu_pmc.sh). That leg is a run of its own, so it and the
+    roofline are part of --full (or of --c3-leg device) only. dump: the last timed step's host
+    columns and counters are written there."""
     units = args.c3_units
     host = c3_host(units)
     pinned = torch.empty(host.size, dtype=torch.uint8, pin_memory=True)
@@ -598,7 +658,7 @@ def run_c3(args, dev, steps, warmup, cpu):
     nf = units * (C3_UNIT_FRAMES + 1)
     nc = units * C3_UNIT_FRAMES
     b_dev = wire.size + 13 * nf + 49 * nc
-    kern = c3_device_leg(pinned, nf, dev, steps, warmup)
+    kern = c3_device_leg(pinned, nf, dev, steps, warmup) if args.full or args.c3_leg == "device" else None
     if args.c3_leg == "device":
         return {"value": 0.0, "roofline_kernel_ms": kern,
                 "config": {"workload": f"C3: {units} units, HBM-resident decode only", "frames": nf}}
@@ -613,7 +673,7 @@ def run_c3(args, dev, steps, warmup, cpu):
     t_step, t_dec, t_h2d, t_d2h, staged, skipped = [], [], [], [], 0, 0
     for _ in range(steps):
         t0 = time.perf_counter()
-        ctx.decode_batch(wire, outs=outs)
+        r = ctx.decode_batch(wire, outs=outs)
         t_step.append(time.perf_counter() - t0)
         t = ctx.timing()
         t_dec.append(t.total_ms)
@@ -621,8 +681,11 @@ def run_c3(args, dev, steps, warmup, cpu):
         t_d2h.append(t.d2h_ms)
         staged, skipped = int(t.h2d_bytes), int(t.h2d_skipped)
     ctx.close()
+    if dump:
+        counters = ["nframes", "err_frame", "err_code", "err_detail", "consumed", "tail", "blob_remaining"]
+        dump_outputs(dump, {k: v for k, v in r.items() if isinstance(v, np.ndarray)}, r["nframes"],
+                     [[r[k] for k in counters]])
     step_s = float(np.mean(t_step))
-    dec_s = kern / 1e3
     line = {
         "value": nf / step_s, "unit": "frames/s", "steps": steps, "warmup": warmup, "ms_per_step": step_s * 1e3,
         "data": "synthetic: C3 generator (seeded), in pinned host memory (the Node path's input side)",
@@ -634,25 +697,29 @@ def run_c3(args, dev, steps, warmup, cpu):
                 "ms": float(np.mean(t_h2d))},
         "d2h_ms": float(np.mean(t_d2h)),
         "pieces_decode_ms": float(np.mean(t_dec)),
-        "roofline": {"bound": "hbm", "achieved": b_dev / dec_s / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": b_dev / dec_s / 1e9 / HBM_PEAK_GBPS, "traffic": traffic_from_profile("c3", nf),
-                     "traffic_source": TRAFFIC_SOURCE % "c3",
-                     "kernel": "the decode of the same wire resident in HBM (claims + verify + emit, one launch "
-                               "sequence, HIP events on libdrp's stream); the host path's pieces "
-                               "(pieces_decode_ms, summed with the host waits between their passes) overlap the "
-                               "PCIe copy", "kernel_ms": kern,
-                     "bytes_model": "wire + 13*frames + 49*changes"},
     }
+    if kern is not None:
+        dec_s = kern / 1e3
+        line["roofline"] = {
+            "bound": "hbm", "achieved": b_dev / dec_s / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+            "frac": b_dev / dec_s / 1e9 / HBM_PEAK_GBPS, "traffic": traffic_from_profile("c3", nf),
+            "traffic_source": TRAFFIC_SOURCE % "c3",
+            "kernel": "the decode of the same wire resident in HBM (claims + verify + emit, one launch "
+                      "sequence, HIP events on libdrp's stream); the host path's pieces "
+                      "(pieces_decode_ms, summed with the host waits between their passes) overlap the "
+                      "PCIe copy", "kernel_ms": kern,
+            "bytes_model": "wire + 13*frames + 49*changes"}
     if cpu:
         line["cpu_baseline"] = cpu_baseline_c3()
     del pinned, wire, outs
     return line
 
 
-def run_decode(args, dev, rank, world, workload, steps, warmup):
+def run_decode(args, dev, rank, world, workload, steps, warmup, dump=None):
     """C2 (one 8.6 GB stream per GPU) or C4 (8192 independent streams sharded over the ranks):
     `steps` timed decodes after `warmup`, each followed for N > 1 by the all-gather of the 32 B
-    per-stream stats and the global index scan. Returns rank 0's line (no CPU legs)."""
+    per-stream stats and the global index scan. Returns rank 0's line (no CPU legs). dump: rank 0
+    writes the last timed step's frame table and stream results there."""
     dist = world > 1
     if workload == "c2":
         nframes = args.frames
@@ -721,6 +788,8 @@ def run_decode(args, dev, rank, world, workload, steps, warmup):
         frames_all = frames_all.to(cdev)
         torch.distributed.all_reduce(frames_all)
     frames_node = int(frames_all.item())
+    if dump and rank == 0:
+        dump_outputs(dump, outs, nframes, stream_results(res))
     ctx.close()
     del wire, outs, res
     torch.cuda.empty_cache()
@@ -779,24 +848,31 @@ def run_decode(args, dev, rank, world, workload, steps, warmup):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also the c4/c5/c3 sub-lines, the CPU baselines, the H2D rate, the Node path, C5's "
+                         "decode-after-C2 leg and C3's HBM-resident roofline leg (a plain run: the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--frames", type=int, default=100_000_000, help="C2 frames per GPU")
     ap.add_argument("--workload", choices=["c2", "c3", "c4", "c5"], default="c2")
     ap.add_argument("--c5-changes", type=int, default=1_000_000, help="C5 Changes per step")
     ap.add_argument("--streams", type=int, default=8192, help="C4 streams across all GPUs")
     ap.add_argument("--sub-steps", type=int, default=5, help="timed steps of the c4/c5 sub-lines")
-    ap.add_argument("--no-sub", action="store_true", help="C2 only: no c3/c4/c5 sub-lines")
+    ap.add_argument("--no-sub", action="store_true", help="--full, C2 only: no c3/c4/c5 sub-lines")
     ap.add_argument("--c3-units", type=int, default=947, help="C3 units (1000 C2 frames + 1 MiB blob) per step")
     ap.add_argument("--c3-leg", choices=["both", "device"], default="both",
                     help="c3: device = only the HBM-resident decode (the PMC passes)")
     ap.add_argument("--tile", type=int, default=0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: no CPU baselines, H2D rate or Node path")
     ap.add_argument("--no-after-c2", action="store_true",
-                    help="C5: no decode-after-C2 leg (PMC passes: its C2 kernels would join C5's counters)")
+                    help="--full, C5: no decode-after-C2 leg (PMC passes: its C2 kernels would join C5's counters)")
     ap.add_argument("--backend", default="nccl", help="nccl (RCCL) for runs; gloo only to rehearse "
                     "several ranks on one GPU")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if os.environ.get("DRP_BENCH_WATCHDOG"):  # (hang finding: every thread's Python stack, then exit)
         import faulthandler
         faulthandler.dump_traceback_later(float(os.environ["DRP_BENCH_WATCHDOG"]), exit=True)
@@ -826,21 +902,22 @@ def main():
             torch.distributed.init_process_group(args.backend)
     dev = torch.device("cuda", local % max(1, torch.cuda.device_count()))
     torch.cuda.set_device(dev)
-    cpu = world == 1 and rank == 0 and not args.no_cpu
+    cpu = args.full and world == 1 and rank == 0 and not args.no_cpu
+    dump = args.dump_outputs
 
     if args.workload == "c5":
-        out = run_c5(args, dev, rank, world)
+        out = run_c5(args, dev, rank, world, cpu=cpu, dump=dump)
     elif args.workload == "c3":
-        out = run_c3(args, dev, args.steps, args.warmup, cpu)
+        out = run_c3(args, dev, args.steps, args.warmup, cpu, dump=dump)
     else:
-        out = run_decode(args, dev, rank, world, args.workload, args.steps, args.warmup)
+        out = run_decode(args, dev, rank, world, args.workload, args.steps, args.warmup, dump=dump)
         if cpu:
             if args.workload == "c2":
                 out["cpu_baseline"] = cpu_baseline()
                 out["cpu_baseline_all_cores"] = cpu_baseline_streams()
             else:
                 out["cpu_baseline"] = cpu_baseline_streams()
-        if args.workload == "c2" and not args.no_sub:
+        if args.full and args.workload == "c2" and not args.no_sub:
             # BASELINE configs[3] and [4] as sub-lines of the same run (own timing, roofline and
             # CPU baseline); the top-level value stays C2's
             c4 = run_decode(args, dev, rank, world, "c4", args.sub_steps, args.warmup)

@@ -6,8 +6,8 @@
 #   tests          the GPU suite (pytest -m gpu)
 #   tests:<expr>   the GPU tests matching a -k expression
 #   smoke          __graft_entry__.smoke()
-#   bench          the default bench line (C2 + c4/c5 sub-lines + CPU legs + Node path)
-#   quick          the default bench line without CPU legs and the Node path
+#   bench          the bench.py --full line (C2 + c3/c4/c5 sub-lines + CPU legs + Node path)
+#   quick          the same without CPU legs and the Node path
 #   prof           rocprofv3 --kernel-trace --stats of a quick C2 + C4 + C5 run (no CPU legs)
 #   prof:<w>[:tag] the same for workload w's line alone (c2, c4, c5: its kernels' averages are per launch)
 #   pmc:<w>        FETCH_SIZE / WRITE_SIZE / SQ passes of workload w (c2, c4, c5) (scripts/gpu_pmc.sh)
@@ -43,16 +43,16 @@ for step in "$@"; do
       echo "smoke: $(tail -1 $OUT/smoke.log)"
       ;;
     bench)
-      timeout -k 10 600 python -u bench.py > $OUT/bench.log 2>&1
+      timeout -k 10 600 python -u bench.py --full > $OUT/bench.log 2>&1
       echo bench done
       ;;
     quick)
-      timeout -k 10 300 python -u bench.py --no-cpu > $OUT/bench_quick.log 2>&1
+      timeout -k 10 300 python -u bench.py --full --no-cpu > $OUT/bench_quick.log 2>&1
       echo quick done
       ;;
     prof)
       (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/prof -o run -- \
-        python3 -u $ROOT/bench.py --steps 5 --warmup 2 --no-cpu > $ROOT/$OUT/bench_prof.log 2>&1)
+        python3 -u $ROOT/bench.py --full --steps 5 --warmup 2 --no-cpu > $ROOT/$OUT/bench_prof.log 2>&1)
       echo prof done
       ;;
     prof:*)
@@ -60,7 +60,7 @@ for step in "$@"; do
       T=${W#*:}
       [ "$T" = "$W" ] && T="" || W=${W%%:*}
       (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $ROOT/$OUT/prof_$W$T -o run -- \
-        python3 -u $ROOT/bench.py --workload $W --steps 10 --warmup 2 --no-cpu --no-sub > $ROOT/$OUT/bench_prof_$W$T.log 2>&1)
+        python3 -u $ROOT/bench.py --full --workload $W --steps 10 --warmup 2 --no-cpu --no-sub > $ROOT/$OUT/bench_prof_$W$T.log 2>&1)
       echo "prof $W$T done: $(python3 scripts/kstats.py $OUT/prof_$W$T/run_kernel_stats.csv 3 | tr -s ' ' | tr '\n' ';')"
       ;;
     pmc:*)
@@ -71,7 +71,7 @@ for step in "$@"; do
       ;;
     ab:*)
       V=${step#ab:}
-      DRP_LIB=exp/$V/libdrp.so timeout -k 10 300 python -u bench.py --steps 10 --warmup 2 --no-cpu \
+      DRP_LIB=exp/$V/libdrp.so timeout -k 10 300 python -u bench.py --full --steps 10 --warmup 2 --no-cpu \
         > $OUT/ab_$V.log 2>&1
       echo "ab $V done"
       ;;
@@ -105,7 +105,7 @@ for step in "$@"; do
       unset "${step#unenv:}"
       ;;
     c2 | c3 | c4 | c5)
-      timeout -k 10 300 python -u bench.py --workload $step --no-cpu --no-sub --steps 10 --warmup 2 >> $OUT/$step.log 2>&1
+      timeout -k 10 300 python -u bench.py --full --workload $step --no-cpu --no-sub --steps 10 --warmup 2 >> $OUT/$step.log 2>&1
       echo "$step (${DRP_CLAIMS:-auto} ${DRP_LIB:-}): $(tail -1 $OUT/$step.log | cut -c1-400)"
       ;;
     *)

@@ -1,4 +1,4 @@
-"""Per-workload kernel times of a `bench.py --no-cpu` rocprofv3 kernel trace (C2, then C4, then C5:
+"""Per-workload kernel times of a `bench.py --full --no-cpu` rocprofv3 kernel trace (C2, then C4, then C5:
 warmup + steps decodes each): the dispatches of each drp kernel in time order, split into the three
 phases by the tile_prefix launches (one per decode). Usage: python scripts/trace_phases.py TRACE.csv [per]"""
 import collections
