@@ -237,6 +237,12 @@ struct drp_ctx {
     uint64_t rows = 0, nf0 = 0, cap = 0;
     std::vector<std::pair<uint64_t, uint64_t>> pieces;
     const uint8_t *dev = nullptr;  // the last piece's bytes on the device (a one-piece batch: all of it)
+    // drp_relay_staged: the batch's bytes from batch offset `base` on as they lie on the device
+    // (every piece at its own batch offset, the skipped blob payloads as holes), the delivered GPU
+    // rows (no malformed Change), and whether a staged batch is held at all
+    const uint8_t *wire = nullptr;
+    uint64_t wire_bytes = 0, base = 0, good = 0;
+    bool valid = false;
     uint64_t off0 = 0;
     uint32_t len0 = 0;
     uint8_t ty0 = 0;
@@ -976,6 +982,7 @@ static int decode_batch_device_out(drp_ctx *c, const uint8_t *bytes, uint64_t n,
   const bool out_dev = true;
   carry->frame_bytes = 0;
   c->staged.rows = 0;
+  c->staged.valid = false;
   hipStream_t st = c->st;
   *err_frame = ~0ull;
   *err_code = DRP_ERR_NONE;
@@ -1278,6 +1285,14 @@ static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, d
   uint64_t copied = 0;
   const uint64_t cap = stage_cap(c, n - pos);
   if (!c->dec_cols.ensure(carve_bytes(cap))) return DRP_E_NOMEM;
+  // every piece is staged at its own batch offset (from base0 on), so the Changes of the whole
+  // batch stay on the device for drp_relay_staged; the skipped blob payloads are holes never
+  // written or read
+  const uint64_t base0 = pos & ~15ull;
+  if (!c->in_stage.ensure(n - base0 + 64)) return DRP_E_NOMEM;
+  S.wire = static_cast<const uint8_t *>(c->in_stage.p);
+  S.wire_bytes = n - base0;
+  S.base = base0;
   carve(c->dec_cols, cap, S.fr, S.co);
   if (c->key_post != DRP_KEY_POST_HASH) S.co.key_hash = nullptr;
   S.cap = cap;
@@ -1308,7 +1323,6 @@ static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, d
     if (pipe && pend.empty()) {  // (the compute stream is idle here: every piece ends in a wait)
       pbase = pos & ~15ull;
       const uint64_t m = n - pbase;
-      if (!c->in_stage.ensure(m + 64)) return DRP_E_NOMEM;
       // uniform chunks, then a half and a quarter chunk: the decode and fetch left after the copy
       // are a quarter chunk's (each piece's decode hides behind the next, shorter copy)
       const uint64_t chunk =
@@ -1322,7 +1336,7 @@ static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, d
       for (size_t k = 0; k < pend.size(); k++) {
         if (!c->pev[k]) CHK(hipEventCreateWithFlags(&c->pev[k], hipEventDisableTiming));
         const uint64_t lo = k ? pend[k - 1] : pbase;
-        CHK(hipMemcpyAsync(c->in_stage.at<uint8_t>(lo - pbase), H.flat + lo, pend[k] - lo, hipMemcpyHostToDevice,
+        CHK(hipMemcpyAsync(c->in_stage.at<uint8_t>(lo - base0), H.flat + lo, pend[k] - lo, hipMemcpyHostToDevice,
                            c->cst));
         CHK(hipEventRecord(c->pev[k], c->cst));
       }
@@ -1340,7 +1354,7 @@ static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, d
       pe = pend[pk];
       ps = pos & ~15ull;
       mp = pe - ps;
-      dp = c->in_stage.at<uint8_t>(ps - pbase);
+      dp = c->in_stage.at<uint8_t>(ps - base0);
       CHK(hipStreamWaitEvent(st, c->pev[pk], 0));
       pk++;
       hipLaunchKernelGGL(piece_meta_kernel, dim3(1), dim3(1), 0, st, soff, ent, mp, pos - ps);
@@ -1349,10 +1363,9 @@ static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, d
       pe = std::min(n, pos + want);
       ps = pos & ~15ull;
       mp = pe - ps;
-      if (!c->in_stage.ensure(mp + 64)) return DRP_E_NOMEM;
-      dp = static_cast<const uint8_t *>(c->in_stage.p);
+      dp = c->in_stage.at<uint8_t>(ps - base0);
       CHK(hipEventRecord(c->hev[0], st));
-      if (const int rc = h2d_range(c, H, ps, mp, c->in_stage.p, st, &copied)) return rc;
+      if (const int rc = h2d_range(c, H, ps, mp, c->in_stage.at<uint8_t>(ps - base0), st, &copied)) return rc;
       hipLaunchKernelGGL(piece_meta_kernel, dim3(1), dim3(1), 0, st, soff, ent, mp, pos - ps);
       CHK(hipGetLastError());
       CHK(hipEventRecord(c->hev[1], st));
@@ -1402,12 +1415,12 @@ static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, d
         hipLaunchKernelGGL(piece_shift_kernel, dim3(g), dim3(256), 0, st, fr.payload_off, nr, ps - pbase);
         CHK(hipGetLastError());
       }
-      S.dev = static_cast<const uint8_t *>(c->in_stage.p);
+      S.dev = c->in_stage.at<uint8_t>(pbase - base0);
     } else {
       float ms = 0;
       if (hipEventElapsedTime(&ms, c->hev[0], c->hev[1]) == hipSuccess) h2d_ms += ms;
       S.pieces.emplace_back(rows, ps);
-      S.dev = static_cast<const uint8_t *>(c->in_stage.p);
+      S.dev = dp;
     }
     const uint64_t bad = (r.err_code == DRP_ERR_CHANGE || r.err_code == DRP_ERR_REQUIRED) ? 1 : 0;
     if (r.err_code || pe == n) {  // the batch's end or its error: this piece's tail is the batch's
@@ -1505,6 +1518,7 @@ static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, d
   c->frames_per_byte = (double)rows / (double)(n - S.pieces[0].second);
   S.rows = S.nf0 + rows;
   *n_frames = S.nf0 + rows - ((*err_code == DRP_ERR_CHANGE || *err_code == DRP_ERR_REQUIRED) ? 1 : 0);
+  S.good = *n_frames - S.nf0;
   return DRP_OK;
 }
 
@@ -1519,6 +1533,8 @@ static int stage_decode(drp_ctx *c, const HostSrc &H, drp_carry *carry, uint64_t
   auto &S = c->staged;
   S.rows = S.nf0 = 0;
   S.pieces.clear();
+  S.wire = nullptr;
+  S.wire_bytes = S.base = S.good = 0;
   *err_frame = ~0ull;
   *err_code = DRP_ERR_NONE;
   *err_detail = 0;
@@ -1632,6 +1648,10 @@ static int stage_decode(drp_ctx *c, const HostSrc &H, drp_carry *carry, uint64_t
   const uint64_t bad = (r.err_code == DRP_ERR_CHANGE || r.err_code == DRP_ERR_REQUIRED) ? 1 : 0;
   S.pieces.emplace_back(0, a);
   S.dev = dbytes;
+  S.wire = dbytes;
+  S.wire_bytes = m;
+  S.base = a;
+  S.good = r.frames;
   S.rows = S.nf0 + r.frames + bad;
   *n_frames = S.nf0 + r.frames;
   if (r.err_code) {
@@ -1830,7 +1850,7 @@ int drp_decode_fetch_keys(drp_ctx *c, uint64_t first, uint64_t rows, uint32_t *k
   if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
   auto &S = c->staged;
   if (first > S.rows || rows > S.rows - first) return DRP_E_INVAL;
-  if (S.pieces.size() != 1 || !S.dev || c->key_post == DRP_KEY_POST_OFF) return DRP_E_INVAL;
+  if (!S.valid || S.pieces.size() != 1 || !S.dev || c->key_post == DRP_KEY_POST_OFF) return DRP_E_INVAL;
   *text_len = 0;
   if (!rows) return DRP_OK;
   const uint64_t dst = first == 0 && S.nf0 ? 1 : 0;  // (a carried blob row: no key)
@@ -1880,7 +1900,10 @@ int drp_decode_stage(drp_ctx *c, const uint8_t *bytes, uint64_t n, drp_carry *ca
   HostSrc H;
   H.flat = bytes;
   H.n = n;
-  return stage_decode(c, H, carry, n_frames, err_frame, err_code, err_detail);
+  c->staged.valid = false;
+  const int rc = stage_decode(c, H, carry, n_frames, err_frame, err_code, err_detail);
+  c->staged.valid = rc == DRP_OK;
+  return rc;
 }
 
 int drp_decode_stage_v(drp_ctx *c, const drp_chunk *chunks, uint64_t nchunks, drp_carry *carry, uint64_t *n_frames,
@@ -1899,11 +1922,11 @@ int drp_decode_stage_v(drp_ctx *c, const drp_chunk *chunks, uint64_t nchunks, dr
     H.ch = nullptr;
   }
   if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
-  if (!H.n) {
-    HostSrc E;
-    return stage_decode(c, E, carry, n_frames, err_frame, err_code, err_detail);
-  }
-  return stage_decode(c, H, carry, n_frames, err_frame, err_code, err_detail);
+  c->staged.valid = false;
+  HostSrc E;
+  const int rc = stage_decode(c, H.n ? H : E, carry, n_frames, err_frame, err_code, err_detail);
+  c->staged.valid = rc == DRP_OK;
+  return rc;
 }
 
 int drp_decode_fetch(drp_ctx *c, const drp_frames *frames, const drp_changes *cols, uint64_t first, uint64_t rows) {
@@ -1931,7 +1954,9 @@ int drp_decode_batch(drp_ctx *c, const uint8_t *bytes, uint64_t n, drp_carry *ca
   c->dco = cols;
   c->dcap = cap;
   c->dfetched = 0;
+  c->staged.valid = false;
   int rc = stage_decode(c, H, carry, n_frames, err_frame, err_code, err_detail);
+  c->staged.valid = rc == DRP_OK;
   c->dfr = nullptr;
   c->dco = nullptr;
   c->key_post = key_post;
@@ -1980,6 +2005,7 @@ static int stage_src(drp_ctx *c, const drp_change_src *src, const uint8_t *heap,
     dsrc = *src;
     dheap = heap;
     if (!is_device_ptr(heap) && heap_bytes) {
+      c->staged.valid = false;  // (the staged wire lives in in_stage: drp_relay_staged must not read it now)
       if (!c->in_stage.ensure(heap_bytes)) return DRP_E_NOMEM;
       CHK(hipMemcpyAsync(c->in_stage.p, heap, heap_bytes, hipMemcpyDefault, c->st));
       dheap = (const uint8_t *)c->in_stage.p;
@@ -1987,6 +2013,7 @@ static int stage_src(drp_ctx *c, const drp_change_src *src, const uint8_t *heap,
     return DRP_OK;
   }
   const size_t need = al(heap_bytes + 16) + 10 * al(n * 8 + 8);
+  c->staged.valid = false;  // (as above: the encoder's staging overwrites or reallocates in_stage)
   if (!c->in_stage.ensure(need)) return DRP_E_NOMEM;
   size_t o = 0;
   hipError_t copy_err = hipSuccess;  // first failed staging copy, returned below
@@ -2060,6 +2087,148 @@ int drp_encode_batch(drp_ctx *c, const drp_change_src *src, const uint8_t *heap,
     CHK(hipStreamSynchronize(c->st));
   }
   return DRP_OK;
+}
+
+// drp_filter -> the select kernel's parameters and byte strings (DRP_E_INVAL: unknown bits,
+// EQ together with NONE, a string longer than DRP_SEL_MAX_BYTES or missing)
+static int select_filter(const drp_filter *f, drp::SelectParams &P, drp::SelectBytes &fb) {
+  P.fflags = 0;
+  P.subset_len = P.prefix_len = 0;
+  P.change_min = 0;
+  P.change_max = ~0ull;
+  if (!f) return DRP_OK;
+  if (f->flags & ~drp_select_known_flags()) return DRP_E_INVAL;
+  if ((f->flags & DRP_SEL_SUBSET_EQ) && (f->flags & DRP_SEL_SUBSET_NONE)) return DRP_E_INVAL;
+  P.fflags = f->flags;
+  if (f->flags & DRP_SEL_CHANGE_RANGE) {
+    P.change_min = f->change_min;
+    P.change_max = f->change_max;
+  }
+  if (f->flags & DRP_SEL_SUBSET_EQ) {
+    if (f->subset_len > DRP_SEL_MAX_BYTES || (f->subset_len && !f->subset)) return DRP_E_INVAL;
+    P.subset_len = f->subset_len;
+    if (f->subset_len) memcpy(fb.b, f->subset, f->subset_len);
+  }
+  if (f->flags & DRP_SEL_KEY_PREFIX) {
+    if (f->key_prefix_len > DRP_SEL_MAX_BYTES || (f->key_prefix_len && !f->key_prefix)) return DRP_E_INVAL;
+    P.prefix_len = f->key_prefix_len;
+    if (f->key_prefix_len) memcpy(fb.b + DRP_SEL_MAX_BYTES, f->key_prefix, f->key_prefix_len);
+  }
+  return DRP_OK;
+}
+
+static void select_out(drp::SelectParams &P, const drp_change_src *o, uint64_t *sel_idx, uint64_t *n_selected) {
+  // (the caller's arrays are writable device memory behind drp_change_src's const pointers)
+  P.o_key_off = const_cast<uint64_t *>(o->key_off);
+  P.o_key_len = const_cast<uint32_t *>(o->key_len);
+  P.o_subset_off = const_cast<uint64_t *>(o->subset_off);
+  P.o_subset_len = const_cast<uint32_t *>(o->subset_len);
+  P.o_value_off = const_cast<uint64_t *>(o->value_off);
+  P.o_value_len = const_cast<uint32_t *>(o->value_len);
+  P.o_change = const_cast<uint64_t *>(o->change);
+  P.o_from = const_cast<uint64_t *>(o->from);
+  P.o_to = const_cast<uint64_t *>(o->to);
+  P.o_flags = const_cast<uint8_t *>(o->flags);
+  P.sel_idx = sel_idx;
+  P.n_selected = n_selected;
+}
+
+int drp_select_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                      const drp_changes *cols, uint64_t n, const drp_filter *filter, const drp_change_src *out_rows,
+                      uint64_t *sel_idx, uint64_t *n_selected) {
+  if (!c || !frames || !cols || !out_rows || !n_selected || (!bytes && nbytes)) return DRP_E_INVAL;
+  if (n && (!frames->payload_off || !frames->type || !cols->key_off || !cols->key_len || !cols->subset_off ||
+            !cols->subset_len || !cols->value_off || !cols->value_len || !cols->change || !cols->from || !cols->to ||
+            !cols->flags || !out_rows->key_off || !out_rows->key_len || !out_rows->subset_off ||
+            !out_rows->subset_len || !out_rows->value_off || !out_rows->value_len || !out_rows->change ||
+            !out_rows->from || !out_rows->to || !out_rows->flags))
+    return DRP_E_INVAL;
+  drp::SelectParams P;
+  drp::SelectBytes fb;
+  memset(&P, 0, sizeof(P));
+  memset(&fb, 0, sizeof(fb));
+  if (const int rc = select_filter(filter, P, fb)) return rc;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  // (the decode scratch: free between decodes, and every user is ordered on the ctx's stream)
+  if (!c->scratch.ensure(drp_select_scratch_bytes(n))) return DRP_E_NOMEM;
+  P.bytes = bytes;
+  P.nbytes = nbytes;
+  P.payload_off = frames->payload_off;
+  P.type = frames->type;
+  P.cols = *cols;
+  P.n = n;
+  select_out(P, out_rows, sel_idx, n_selected);
+  CHK(drp_launch_select(&P, &fb, c->scratch.p, c->st));
+  return DRP_OK;
+}
+
+int drp_relay_staged(drp_ctx *c, const drp_filter *filter, uint8_t *out, uint64_t cap, uint64_t *written,
+                     uint64_t *n_selected) {
+  if (!c || !written || !n_selected || (!out && cap)) return DRP_E_INVAL;
+  auto &S = c->staged;
+  if (!S.valid) return DRP_E_INVAL;
+  drp::SelectParams P;
+  drp::SelectBytes fb;
+  memset(&P, 0, sizeof(P));
+  memset(&fb, 0, sizeof(fb));
+  if (const int rc = select_filter(filter, P, fb)) return rc;
+  *written = 0;
+  *n_selected = 0;
+  const uint64_t n = S.good;  // the delivered GPU rows (a carried blob's row 0 is built on the host)
+  if (!n) return DRP_OK;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  hipStream_t st = c->st;
+  // scratch (the decode's, free until the next decode): the kernel's words, the count, the piece
+  // table, the selected rows' columns
+  const uint64_t np = S.pieces.size();
+  const size_t o_cnt = al(drp_select_scratch_bytes(n)), o_piece = o_cnt + 256, o_rows = o_piece + al(2 * np * 8),
+               o_end = o_rows + 10 * al(n * 8);
+  if (!c->scratch.ensure(o_end)) return DRP_E_NOMEM;
+  uint64_t *dcnt = c->scratch.at<uint64_t>(o_cnt);
+  drp_change_src rows;
+  {
+    size_t o = o_rows;
+    auto take = [&](size_t w) { void *p = c->scratch.at<char>(o); o += al(n * w); return p; };
+    rows.key_off = (const uint64_t *)take(8);
+    rows.key_len = (const uint32_t *)take(4);
+    rows.subset_off = (const uint64_t *)take(8);
+    rows.subset_len = (const uint32_t *)take(4);
+    rows.value_off = (const uint64_t *)take(8);
+    rows.value_len = (const uint32_t *)take(4);
+    rows.change = (const uint64_t *)take(8);
+    rows.from = (const uint64_t *)take(8);
+    rows.to = (const uint64_t *)take(8);
+    rows.flags = (const uint8_t *)take(1);
+  }
+  // a piece's payload offsets are relative to the batch offset it was staged at; the staged bytes
+  // start at batch offset S.base (a leading blob continuation never reaches the device)
+  if (np > 1) {
+    std::vector<uint64_t> &h = c->host_tmp;
+    h.resize(2 * np);
+    for (uint64_t k = 0; k < np; k++) {
+      h[k] = S.pieces[k].first;
+      h[np + k] = S.pieces[k].second - S.base;
+    }
+    CHK(hipMemcpyAsync(c->scratch.at<uint64_t>(o_piece), h.data(), 2 * np * 8, hipMemcpyHostToDevice, st));
+    P.piece_row = c->scratch.at<uint64_t>(o_piece);
+    P.piece_shift = P.piece_row + np;
+    P.npieces = np;
+  } else {
+    P.shift0 = np ? S.pieces[0].second - S.base : 0;
+  }
+  P.bytes = S.wire;
+  P.nbytes = S.wire_bytes;
+  P.payload_off = S.fr.payload_off;
+  P.type = S.fr.type;
+  P.cols = S.co;
+  P.n = n;
+  select_out(P, &rows, nullptr, dcnt);
+  CHK(drp_launch_select(&P, &fb, c->scratch.p, st));
+  uint64_t nsel = 0;
+  CHK(hipMemcpyAsync(&nsel, dcnt, 8, hipMemcpyDeviceToHost, st));
+  CHK(hipStreamSynchronize(st));  // (the one readback that sizes the encode)
+  *n_selected = nsel;
+  return drp_encode_batch(c, &rows, S.wire, S.wire_bytes, nsel, out, cap, written);
 }
 
 int drp_index_scan(drp_ctx *c, const drp_stream_stats *stats, uint64_t count, uint64_t *base) {

@@ -109,6 +109,38 @@ struct EncodeParams {
   uint64_t nob;  // output blocks the grid covers (from cap)
 };
 
+// drp_select.hip: predicate + stable compaction of decoded Change rows into encoder rows
+struct SelectParams {
+  const uint8_t *bytes;  // the wire the columns point into
+  uint64_t nbytes;
+  const uint64_t *payload_off;
+  const uint8_t *type;
+  drp_changes cols;  // (read only)
+  uint64_t n;
+  // filter (drp_filter; its byte strings in device memory, placed by the launcher)
+  uint32_t fflags, subset_len, prefix_len;
+  uint64_t change_min, change_max;
+  const uint8_t *subset, *prefix;
+  // rows of a batch staged in pieces: piece k holds rows [piece_row[k], piece_row[k + 1]) and its
+  // payload offsets are piece_shift[k] short of offsets into `bytes` (npieces <= 1: shift0 for all)
+  const uint64_t *piece_row, *piece_shift;
+  uint64_t npieces, shift0;
+  // scratch (placed by the launcher): one ballot word per 64 rows, one count per workgroup
+  uint64_t *mask, *block_cnt;
+  // outputs
+  uint64_t *o_key_off, *o_subset_off, *o_value_off;
+  uint32_t *o_key_len, *o_subset_len, *o_value_len;
+  uint64_t *o_change, *o_from, *o_to;
+  uint8_t *o_flags;
+  uint64_t *sel_idx;  // may be null
+  uint64_t *n_selected;
+};
+
+// the filter's byte strings as launch arguments: subset, then key prefix
+struct SelectBytes {
+  uint8_t b[2 * DRP_SEL_MAX_BYTES];
+};
+
 }  // namespace drp
 
 extern "C" {
@@ -168,6 +200,9 @@ hipError_t drp_launch_key_post(const uint8_t *bytes, const uint64_t *tile_prefix
                                const uint64_t *tile_base, const uint64_t *tile_count, uint64_t cap,
                                const drp_frames *fr, const drp_changes *co, int flags_only, const uint32_t *abort_flag,
                                uint32_t abort_mask, hipStream_t st);
+uint64_t drp_select_scratch_bytes(uint64_t n);  // device scratch drp_launch_select needs for n rows
+uint32_t drp_select_known_flags(void);
+hipError_t drp_launch_select(const drp::SelectParams *P, const drp::SelectBytes *fb, void *scratch, hipStream_t st);
 hipError_t drp_launch_index_scan(const drp_stream_stats *stats, uint64_t count, uint64_t *base,
                                  hipStream_t st);
 hipError_t drp_launch_stats_from_results(const drp_stream_result *res, const uint64_t *stream_off,

@@ -1,0 +1,183 @@
+// drp_select.hip — gfx950 select of decoded Changes: a predicate over the Change columns and a
+// stable compaction of the rows it keeps into encoder rows (drp_change_src, offsets absolute into
+// the wire), so the encoder (drp_encode.hip) re-encodes them with the received wire as its heap.
+// No reference counterpart: the reference has no relay; the fields the predicate reads are those
+// of messages/schema.proto:1-8 (subset, key, change).
+//
+// The same three steps as enc_size / enc_blocksum / enc_addbase: (1) one row per lane, the
+// predicate's wave ballot kept as one word per 64 rows and its popcounts summed across the
+// workgroup's waves in LDS into one count per workgroup, (2) one workgroup scans the counts,
+// (3) every selected row finds its slot from its workgroup's base, the popcounts of the waves
+// before it and the ballot bits below its lane, and writes its columns there. No global atomics;
+// the order of the rows is kept. The columns are read one 1 / 4 / 8-byte element per lane,
+// consecutive lanes consecutive elements; step (1) reads only the columns the filter names and
+// step (3) only the rows kept (the byte compares read wire bytes only of rows whose lengths match).
+#include "drp_device.h"
+#include "drp_kernels.h"
+
+namespace drp {
+
+constexpr uint32_t SEL_BLK = 1024, SEL_WAVES = SEL_BLK / 64;
+constexpr uint32_t SEL_KNOWN = DRP_SEL_CHANGE_RANGE | DRP_SEL_SUBSET_EQ | DRP_SEL_SUBSET_NONE | DRP_SEL_KEY_PREFIX;
+
+// what row i's payload offsets lack to be offsets into P.bytes
+__device__ __forceinline__ uint64_t sel_shift(const SelectParams &P, uint64_t i) {
+  if (P.npieces <= 1) return P.shift0;
+  uint64_t lo = 0, hi = P.npieces;  // piece_row[lo] <= i < piece_row[hi]
+  while (hi - lo > 1) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if (P.piece_row[mid] <= i) lo = mid;
+    else hi = mid;
+  }
+  return P.piece_shift[lo];
+}
+
+// wire bytes [off, off + len) == ref[0, len); a range outside the wire matches nothing
+__device__ __forceinline__ bool sel_bytes_eq(const SelectParams &P, uint64_t off, uint32_t len, const uint8_t *ref) {
+  if ((uint64_t)len > P.nbytes || off > P.nbytes - len) return false;
+  const uint8_t *w = P.bytes + off;
+  for (uint32_t k = 0; k < len; k++)
+    if (w[k] != ref[k]) return false;
+  return true;
+}
+
+__device__ __forceinline__ bool sel_pred(const SelectParams &P, uint64_t i) {
+  const drp_changes &c = P.cols;
+  if ((P.type[i] & 0x3F) != DRP_TYPE_CHANGE) return false;
+  const uint32_t fl = c.flags[i];
+  if (fl & DRP_F_BAD) return false;
+  const uint32_t ff = P.fflags;
+  if (ff & DRP_SEL_CHANGE_RANGE) {
+    const uint64_t v = c.change[i];
+    if (v < P.change_min || v > P.change_max) return false;
+  }
+  if ((ff & DRP_SEL_SUBSET_NONE) && (fl & DRP_F_SUBSET)) return false;
+  if (ff & DRP_SEL_SUBSET_EQ) {
+    if (!(fl & DRP_F_SUBSET) || c.subset_len[i] != P.subset_len) return false;
+  }
+  if ((ff & DRP_SEL_KEY_PREFIX) && c.key_len[i] < P.prefix_len) return false;
+  // the byte compares last: only rows whose lengths match read the wire
+  if ((ff & DRP_SEL_SUBSET_EQ) && P.subset_len) {
+    const uint64_t off = P.payload_off[i] + sel_shift(P, i) + c.subset_off[i];
+    if (!sel_bytes_eq(P, off, P.subset_len, P.subset)) return false;
+  }
+  if ((ff & DRP_SEL_KEY_PREFIX) && P.prefix_len) {
+    const uint64_t off = P.payload_off[i] + sel_shift(P, i) + c.key_off[i];
+    if (!sel_bytes_eq(P, off, P.prefix_len, P.prefix)) return false;
+  }
+  return true;
+}
+
+// the filter's byte strings into device memory (they travel as launch arguments: no host buffer
+// to keep alive behind an asynchronous copy)
+__global__ __launch_bounds__(2 * DRP_SEL_MAX_BYTES) void sel_filter_kernel(const SelectBytes F, uint8_t *dst) {
+  dst[threadIdx.x] = F.b[threadIdx.x];
+}
+
+// (1) the ballot word of every 64 rows and the rows kept per workgroup
+__global__ __launch_bounds__(SEL_BLK) void sel_count_kernel(const SelectParams P) {
+  __shared__ uint32_t wcnt[SEL_WAVES];
+  const uint64_t i = (uint64_t)blockIdx.x * SEL_BLK + threadIdx.x;
+  const bool keep = i < P.n && sel_pred(P, i);
+  const uint64_t b = __ballot(keep);
+  const uint32_t wv = threadIdx.x >> 6;
+  if (lane_id() == 0) {
+    P.mask[i >> 6] = b;  // (i >> 6 < ceil(n / 64) rounded up to the workgroup: the scratch covers it)
+    wcnt[wv] = (uint32_t)__popcll(b);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t s = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < SEL_WAVES; k++) s += wcnt[k];
+    P.block_cnt[blockIdx.x] = s;
+  }
+}
+
+// (2) exclusive scan of the workgroup counts in place (any number of them: SEL_BLK per round with
+// a running carry); the total is the number of rows kept
+__global__ __launch_bounds__(SEL_BLK) void sel_scan_kernel(const SelectParams P, uint64_t nblk) {
+  __shared__ uint64_t part[SEL_BLK];
+  __shared__ uint64_t carry;
+  if (threadIdx.x == 0) carry = 0;
+  __syncthreads();
+  for (uint64_t c0 = 0; c0 < nblk; c0 += SEL_BLK) {
+    const uint64_t b = c0 + threadIdx.x;
+    const uint64_t v0 = b < nblk ? P.block_cnt[b] : 0;
+    part[threadIdx.x] = v0;
+    __syncthreads();
+    for (uint32_t d = 1; d < SEL_BLK; d <<= 1) {
+      const uint64_t v = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
+      __syncthreads();
+      part[threadIdx.x] += v;
+      __syncthreads();
+    }
+    if (b < nblk) P.block_cnt[b] = carry + part[threadIdx.x] - v0;
+    __syncthreads();
+    if (threadIdx.x == SEL_BLK - 1) carry += part[SEL_BLK - 1];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) *P.n_selected = carry;
+}
+
+// (3) every kept row's columns to its slot
+__global__ __launch_bounds__(SEL_BLK) void sel_scatter_kernel(const SelectParams P) {
+  __shared__ uint32_t wcnt[SEL_WAVES];
+  const uint64_t i = (uint64_t)blockIdx.x * SEL_BLK + threadIdx.x;
+  const uint32_t wv = threadIdx.x >> 6, lane = lane_id();
+  const uint64_t b = P.mask[i >> 6];  // (wave-uniform; written by sel_count_kernel for every wave of the grid)
+  if (lane == 0) wcnt[wv] = (uint32_t)__popcll(b);
+  __syncthreads();
+  if (!((b >> lane) & 1ull)) return;
+  uint64_t slot = P.block_cnt[blockIdx.x];
+  for (uint32_t k = 0; k < wv; k++) slot += wcnt[k];
+  slot += (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
+  const drp_changes &c = P.cols;
+  const uint64_t base = P.payload_off[i] + sel_shift(P, i);
+  P.o_key_off[slot] = base + c.key_off[i];
+  P.o_key_len[slot] = c.key_len[i];
+  P.o_subset_off[slot] = base + c.subset_off[i];
+  P.o_subset_len[slot] = c.subset_len[i];
+  P.o_value_off[slot] = base + c.value_off[i];
+  P.o_value_len[slot] = c.value_len[i];
+  P.o_change[slot] = c.change[i];
+  P.o_from[slot] = c.from[i];
+  P.o_to[slot] = c.to[i];
+  P.o_flags[slot] = (uint8_t)(c.flags[i] & (DRP_F_SUBSET | DRP_F_VALUE));
+  if (P.sel_idx) P.sel_idx[slot] = i;
+}
+
+}  // namespace drp
+
+using namespace drp;
+
+extern "C" uint32_t drp_select_known_flags(void) { return SEL_KNOWN; }
+
+// scratch: the filter's byte strings, the ballot words (one per 64 rows, for whole workgroups),
+// the workgroup counts
+static uint64_t sel_nblk(uint64_t n) { return (n + SEL_BLK - 1) / SEL_BLK; }
+static uint64_t sel_mask_bytes(uint64_t n) { return (sel_nblk(n) * SEL_WAVES * 8 + 255) & ~255ull; }
+extern "C" uint64_t drp_select_scratch_bytes(uint64_t n) {
+  return 2 * DRP_SEL_MAX_BYTES + sel_mask_bytes(n) + sel_nblk(n) * 8 + 256;
+}
+
+extern "C" void drp_dbg_mark(const char *name, hipStream_t st);  // (drp_api.hip: DRP_WATCHDOG)
+
+extern "C" hipError_t drp_launch_select(const SelectParams *Pp, const SelectBytes *fb, void *scratch, hipStream_t st) {
+  SelectParams P = *Pp;
+  if (P.n == 0) return hipMemsetAsync(P.n_selected, 0, 8, st);
+  const uint64_t nblk = sel_nblk(P.n);
+  if (nblk >= (1ull << 31)) return hipErrorInvalidValue;
+  uint8_t *sc = static_cast<uint8_t *>(scratch);
+  P.subset = sc;
+  P.prefix = sc + DRP_SEL_MAX_BYTES;
+  P.mask = reinterpret_cast<uint64_t *>(sc + 2 * DRP_SEL_MAX_BYTES);
+  P.block_cnt = reinterpret_cast<uint64_t *>(sc + 2 * DRP_SEL_MAX_BYTES + sel_mask_bytes(P.n));
+  if (P.fflags & (DRP_SEL_SUBSET_EQ | DRP_SEL_KEY_PREFIX))
+    hipLaunchKernelGGL(sel_filter_kernel, dim3(1), dim3(2 * DRP_SEL_MAX_BYTES), 0, st, *fb, sc);
+  hipLaunchKernelGGL(sel_count_kernel, dim3((uint32_t)nblk), dim3(SEL_BLK), 0, st, P);
+  hipLaunchKernelGGL(sel_scan_kernel, dim3(1), dim3(SEL_BLK), 0, st, P, nblk);
+  hipLaunchKernelGGL(sel_scatter_kernel, dim3((uint32_t)nblk), dim3(SEL_BLK), 0, st, P);
+  drp_dbg_mark("select", st);
+  return hipGetLastError();
+}

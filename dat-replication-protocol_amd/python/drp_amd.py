@@ -28,7 +28,7 @@ EXPORTS = [
     "drp_decode_device", "drp_decode_batch", "drp_decode_stage", "drp_decode_stage_v", "drp_decode_fetch", "drp_decode_fetch_block",
     "drp_decode_fetch_block_ex", "drp_decode_fetch_keys",
     "drp_encode_size", "drp_encode_device",
-    "drp_encode_batch", "drp_index_scan", "drp_stream_stats_from_results", "drp_device",
+    "drp_encode_batch", "drp_select_device", "drp_relay_staged", "drp_index_scan", "drp_stream_stats_from_results", "drp_device",
     "drp_comm_id", "drp_comm_init_rank", "drp_comm_init_all", "drp_comm_destroy",
     "drp_index_allgather", "drp_index_allgather_multi", "drp_index_allgather_host", "drp_device_count",
     "drp_host_alloc", "drp_host_free",
@@ -36,6 +36,8 @@ EXPORTS = [
 KEY_POST_OFF, KEY_POST_HASH, KEY_POST_FLAGS = 0, 1, 2
 BLOB_SKIP_OFF, BLOB_SKIP_AUTO, BLOB_SKIP_ALWAYS = 0, 1, 2
 DRP_E_COMM = -7
+SEL_CHANGE_RANGE, SEL_SUBSET_EQ, SEL_SUBSET_NONE, SEL_KEY_PREFIX = 1, 2, 4, 8
+SEL_MAX_BYTES = 256
 COMM_ID_BYTES = 128
 
 P = C.c_void_p
@@ -73,6 +75,38 @@ class StreamStats(C.Structure):
 
 class Chunk(C.Structure):
     _fields_ = [("bytes", P), ("n", U64)]
+
+
+class Filter(C.Structure):
+    """drp_filter; make one with make_filter (it keeps the byte strings alive)."""
+    _fields_ = [("flags", U32), ("subset_len", U32), ("key_prefix_len", U32), ("reserved", U32),
+                ("change_min", U64), ("change_max", U64), ("subset", P), ("key_prefix", P)]
+
+
+def make_filter(change_range=None, subset=None, subset_none=False, key_prefix=None, flags=None):
+    """A drp_filter: change_range=(min, max) inclusive, subset=bytes (present and equal),
+    subset_none=True (absent), key_prefix=bytes; the conditions AND together. flags overrides
+    the flag word (tests of the error returns)."""
+    f = Filter()
+    fl = 0
+    if change_range is not None:
+        fl |= SEL_CHANGE_RANGE
+        f.change_min, f.change_max = int(change_range[0]), int(change_range[1])
+    f._keep = []
+    if subset is not None:
+        fl |= SEL_SUBSET_EQ
+        b = C.create_string_buffer(bytes(subset), max(1, len(subset)))
+        f._keep.append(b)
+        f.subset, f.subset_len = C.cast(b, P), len(subset)
+    if subset_none:
+        fl |= SEL_SUBSET_NONE
+    if key_prefix is not None:
+        fl |= SEL_KEY_PREFIX
+        b = C.create_string_buffer(bytes(key_prefix), max(1, len(key_prefix)))
+        f._keep.append(b)
+        f.key_prefix, f.key_prefix_len = C.cast(b, P), len(key_prefix)
+    f.flags = fl if flags is None else flags
+    return f
 
 
 class Timing(C.Structure):
@@ -124,6 +158,9 @@ def lib():
         L.drp_encode_device.argtypes = [P, C.POINTER(ChangeSrc), P, U64, U64, P, P, U64]
         L.drp_encode_batch.argtypes = [P, C.POINTER(ChangeSrc), P, U64, U64, P, U64,
                                        C.POINTER(U64)]
+        L.drp_select_device.argtypes = [P, P, U64, C.POINTER(Frames), C.POINTER(Changes), U64, C.POINTER(Filter),
+                                        C.POINTER(ChangeSrc), P, P]
+        L.drp_relay_staged.argtypes = [P, C.POINTER(Filter), P, U64, C.POINTER(U64), C.POINTER(U64)]
         L.drp_index_scan.argtypes = [P, P, U64, P]
         L.drp_stream_stats_from_results.argtypes = [P, P, P, U64, P]
         L.drp_device.argtypes = [P]
@@ -141,7 +178,7 @@ def lib():
                   "drp_set_strict", "drp_set_exact", "drp_set_key_post", "drp_set_blob_skip", "drp_decode_device",
                   "drp_decode_batch",
                   "drp_decode_stage", "drp_decode_stage_v", "drp_decode_fetch", "drp_encode_size",
-                  "drp_encode_device", "drp_encode_batch", "drp_index_scan",
+                  "drp_encode_device", "drp_encode_batch", "drp_select_device", "drp_relay_staged", "drp_index_scan",
                   "drp_stream_stats_from_results", "drp_device", "drp_comm_id", "drp_comm_init_rank",
                   "drp_comm_init_all", "drp_index_allgather", "drp_index_allgather_multi",
                   "drp_index_allgather_host", "drp_device_count"]:
@@ -312,6 +349,7 @@ class Ctx:
             buf = w if n else np.zeros(16, np.uint8)
             _chk("drp_decode_stage", self.L.drp_decode_stage(self.h, _p(buf), n, C.byref(carry), C.byref(nf),
                                                              C.byref(ef), C.byref(ec), C.byref(ed)))
+        self._staged_len = sum(len(c) for c in wire) if isinstance(wire, (list, tuple)) else n
         rows = int(nf.value) + (1 if ec.value in (ERR_CHANGE, ERR_REQUIRED) else 0)
         if block:
             names = ["payload_off", "payload_len", "type"] + COLS32 + COLS64 + ["flags"] + (["key_hash"] if key_hash else [])
@@ -399,6 +437,44 @@ class Ctx:
         _chk("drp_encode_batch", self.L.drp_encode_batch(self.h, C.byref(src), _p(hb), int(h.size), n,
                                                          _p(out), int(total.value), C.byref(written)))
         return out[:int(written.value)].tobytes()
+
+    # ---- select + re-encode (relay) ---------------------------------------------------
+    def select_device(self, wire_t, cols, n, filter, out_rows, sel_idx_t, n_selected_t):
+        """drp_select_device over torch CUDA tensors (asynchronous, on this ctx's stream): cols
+        holds the decoded columns (payload_off, type and the Change columns, as decode_device
+        wrote them), out_rows the drp_change_src columns to fill (n entries each: int64 offsets
+        and numbers, int32 lengths, uint8 flags), sel_idx_t (int64, n entries) may be None,
+        n_selected_t is an int64 tensor of one element."""
+        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
+        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
+                     tp(cols["flags"]), None)
+        dst = ChangeSrc(*[tp(out_rows[k]) for k in ["key_off", "key_len", "subset_off", "subset_len",
+                                                      "value_off", "value_len", "change", "from", "to", "flags"]])
+        self.order_after_torch(wire_t)
+        rc = self.L.drp_select_device(self.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n,
+                                      C.byref(filter) if filter is not None else None, C.byref(dst),
+                                      tp(sel_idx_t), tp(n_selected_t))
+        _chk("drp_select_device", rc)
+        self.order_torch_after(wire_t)
+
+    def relay_staged(self, filter=None, cap=None, out=None):
+        """drp_relay_staged over the batch last staged (decode_staged): returns (wire_bytes,
+        n_selected). cap=None: the staged batch's length, which is always enough (the canonical
+        encoding of a Change is never longer than the one received), so one call does it. A given
+        cap that is too small raises DrpError(DRP_E_CAPACITY) with .written = the size needed.
+        out: a host uint8 array to write into (at least cap bytes)."""
+        fp = C.byref(filter) if filter is not None else None
+        written, nsel = U64(), U64()
+        if cap is None:
+            cap = getattr(self, "_staged_len", 0)
+        buf = out if out is not None else np.zeros(max(16, cap), np.uint8)
+        rc = self.L.drp_relay_staged(self.h, fp, _p(buf), cap, C.byref(written), C.byref(nsel))
+        if rc != DRP_OK:
+            e = DrpError("drp_relay_staged", rc)
+            e.written = int(written.value)
+            raise e
+        return buf[:int(written.value)].tobytes(), int(nsel.value)
 
 
 class Comm:

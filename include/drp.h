@@ -14,6 +14,10 @@
  *   drp_encode_size / drp_encode_batch / drp_encode_device
  *       -> Encoder.change + Encoder._header (encode.js:102-117, 124-137)
  *          + messages.Change.encode (messages/index.js:5)
+ *   drp_select_device / drp_relay_staged
+ *       -> no reference counterpart (the reference has no relay): a predicate over the decoded
+ *          Change columns (schema messages/schema.proto:1-8: subset, change, key) and the encoder
+ *          above over the rows it keeps, the received wire serving as the encoder's heap.
  *   drp_stream_stats + drp_index_scan
  *       -> no reference counterpart (the reference is single-stream); they build the
  *          global frame index after the per-GPU stats tables are all-gathered.
@@ -37,6 +41,7 @@ extern "C" {
 /* libdrp is built with -fvisibility=hidden: the declarations below are its only exports. */
 #pragma GCC visibility push(default)
 
+/* Raised when an existing declaration or layout changes; added symbols do not raise it. */
 #define DRP_ABI_VERSION 5
 
 /* ---- return codes -------------------------------------------------------- */
@@ -308,10 +313,65 @@ int drp_encode_size(drp_ctx *ctx, const drp_change_src *src, uint64_t n, uint64_
  * range leaves [0, heap_bytes) sets frame_off[n] = UINT64_MAX and nothing is written. */
 int drp_encode_device(drp_ctx *ctx, const drp_change_src *src, const uint8_t *heap, uint64_t heap_bytes,
                       uint64_t n, uint64_t *frame_off, uint8_t *out, uint64_t cap);
-/* Synchronous; host or device pointers. DRP_E_INVAL if a row's range leaves the heap. */
+/* Synchronous; host or device pointers. DRP_E_INVAL if a row's range leaves the heap. Host columns
+ * or a host heap are staged through the ctx's input staging, which ends a staged decode's validity
+ * for drp_relay_staged / drp_decode_fetch_keys (see drp_relay_staged); drp_encode_size likewise. */
 int drp_encode_batch(drp_ctx *ctx, const drp_change_src *src, const uint8_t *heap,
                      uint64_t heap_bytes, uint64_t n, uint8_t *out, uint64_t cap,
                      uint64_t *written);
+
+/* ---- select + re-encode (relay) ------------------------------------------- */
+/* Which decoded Changes a relay keeps. A row is selected iff it is a Change frame
+ * ((type & 0x3F) == DRP_TYPE_CHANGE), DRP_F_BAD is clear and every condition enabled in `flags`
+ * holds (the conditions AND together). flags == 0 (or a NULL filter) selects every well-formed
+ * Change: the canonicalising re-encode. Unknown flag bits, DRP_SEL_SUBSET_EQ together with
+ * DRP_SEL_SUBSET_NONE, and a byte string longer than DRP_SEL_MAX_BYTES are DRP_E_INVAL. */
+#define DRP_SEL_CHANGE_RANGE 0x01 /* change_min <= change <= change_max (unsigned; min > max: nothing) */
+#define DRP_SEL_SUBSET_EQ 0x02    /* subset present and its bytes equal subset[0, subset_len) (an empty
+                                     subset matches subset_len == 0; an absent one never matches) */
+#define DRP_SEL_SUBSET_NONE 0x04  /* subset absent */
+#define DRP_SEL_KEY_PREFIX 0x08   /* key_len >= key_prefix_len and the key starts with key_prefix (length 0:
+                                     every key) */
+#define DRP_SEL_MAX_BYTES 256
+typedef struct drp_filter {
+  uint32_t flags; /* DRP_SEL_* */
+  uint32_t subset_len;
+  uint32_t key_prefix_len;
+  uint32_t reserved;
+  uint64_t change_min, change_max;
+  const uint8_t *subset;     /* HOST pointers (read before the call returns); may be NULL when the */
+  const uint8_t *key_prefix; /* length is 0 */
+} drp_filter;
+
+/* The selected rows of decoded rows [0, n), in stream order (a stable compaction), as encoder rows:
+ * out_rows' offsets are absolute into `bytes` (payload_off + key_off, likewise subset and value),
+ * flags are masked to DRP_F_SUBSET | DRP_F_VALUE (the key post-processing bits never reach the
+ * encoder), so drp_encode_device(ctx, out_rows, bytes, nbytes, *n_selected, ...) re-encodes them
+ * with the wire as its heap and no payload byte copied in between. Device pointers only;
+ * asynchronous on drp_stream(ctx). The arrays behind out_rows are caller-owned WRITABLE device
+ * memory of n entries each: they are written through the const pointers of drp_change_src (rows
+ * [0, *n_selected); the rest is left untouched). sel_idx (device, n entries, may be NULL) receives
+ * the source row of each selected row, n_selected (device) their count. frames / cols may be the
+ * flat multi-stream output of drp_decode_device with n = the rows it wrote (the streams' delivered
+ * frames end to end). A row whose key / subset range leaves [0, nbytes) is never read and never
+ * matches a byte condition. */
+int drp_select_device(drp_ctx *ctx, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                      const drp_changes *cols, uint64_t n, const drp_filter *filter, const drp_change_src *out_rows,
+                      uint64_t *sel_idx, uint64_t *n_selected);
+/* Select over the delivered rows of the batch last staged by drp_decode_stage / drp_decode_stage_v
+ * (nothing at or after an error frame, nor a malformed Change) and encode the selection as change
+ * frames into `out` (host or device pointer, capacity cap) with the staged wire as the heap.
+ * Synchronous. *written = the size needed, also when DRP_E_CAPACITY is returned (nothing is
+ * written to out then); *n_selected = the rows kept. The staged result stays valid: the caller can
+ * still drp_decode_fetch the frame table to forward blobs and to carry the tail. The same bytes in
+ * every drp_set_blob_skip mode. DRP_E_INVAL when no staged batch is held: before any stage, after
+ * a stage that failed, and once the staged bytes have left the device. They share the ctx's input
+ * staging with the encoder, so a drp_encode_batch or drp_encode_size whose columns or heap are HOST
+ * memory ends the staged batch for drp_relay_staged and drp_decode_fetch_keys (both then return
+ * DRP_E_INVAL; drp_decode_fetch* still work, the columns are kept elsewhere), as does the next
+ * decode call. drp_encode_device, drp_select_device and an encode from device memory do not. */
+int drp_relay_staged(drp_ctx *ctx, const drp_filter *filter, uint8_t *out, uint64_t cap, uint64_t *written,
+                     uint64_t *n_selected);
 
 /* ---- multi-GPU global index ---------------------------------------------- */
 /* stats[nranks*per_rank] (device): all-gathered per-stream tables in rank order.
