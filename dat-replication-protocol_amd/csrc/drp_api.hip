@@ -230,6 +230,11 @@ struct drp_ctx {
   const drp_changes *dco = nullptr;
   uint64_t dcap = 0, dfetched = 0;
   std::vector<uint64_t> host_tmp;
+  // fan-out: the filter table on its way to the device (page-locked; fan_ev: the copy of the last
+  // call has left it), and drp_fanout_staged's selected rows and splice ranks
+  PinBuf fan_tab;
+  hipEvent_t fan_ev = nullptr;
+  DevBuf fan_rows;
   // the staged host-batch decode: row 0 is a host-built blob continuation when nf0 == 1; GPU
   // rows follow, each piece's payload_off relative to the batch offset where that piece was
   // staged (pieces: {first GPU row, batch offset}; one piece unless blobs were skipped)
@@ -345,6 +350,9 @@ void drp_close(drp_ctx *c) {
   c->fetch_tmp.release();
   c->keybuf.release();
   c->keytext.release();
+  c->fan_rows.release();
+  c->fan_tab.release();
+  if (c->fan_ev) (void)hipEventDestroy(c->fan_ev);
   if (c->dstats) (void)hipFree(c->dstats);
   if (c->ctile) (void)hipFree(c->ctile);
   for (auto &e : c->ev) (void)hipEventDestroy(e);
@@ -2229,6 +2237,221 @@ int drp_relay_staged(drp_ctx *c, const drp_filter *filter, uint8_t *out, uint64_
   CHK(hipStreamSynchronize(st));  // (the one readback that sizes the encode)
   *n_selected = nsel;
   return drp_encode_batch(c, &rows, S.wire, S.wire_bytes, nsel, out, cap, written);
+}
+
+// ---- fan-out ------------------------------------------------------------------------------------
+// The filters, checked as select_filter checks one, into the ctx's page-locked table: nfilters
+// FanFilter records, then every filter's byte strings at 256-byte steps. The table travels by one
+// asynchronous copy, so before it is rewritten the copy of the previous call must have read it.
+static int fanout_filters(drp_ctx *c, const drp_filter *filters, uint32_t K, drp::FanParams &P) {
+  if (!filters || K == 0 || K > DRP_FANOUT_MAX) return DRP_E_INVAL;
+  const size_t o_bytes = al((size_t)K * sizeof(drp::FanFilter)), total = o_bytes + (size_t)K * drp::FAN_FBYTES;
+  std::vector<uint64_t> &h = c->host_tmp;  // (checked here first: a bad filter leaves the table alone)
+  h.assign((total + 7) / 8, 0);
+  uint8_t *tab = reinterpret_cast<uint8_t *>(h.data());
+  P.nfilters = K;
+  P.any_flags = P.any_bytes = 0;
+  for (uint32_t f = 0; f < K; f++) {
+    drp::SelectParams sp;
+    drp::SelectBytes fb;
+    memset(&sp, 0, sizeof(sp));
+    memset(&fb, 0, sizeof(fb));
+    if (const int rc = select_filter(&filters[f], sp, fb)) return rc;
+    drp::FanFilter F = {sp.fflags, sp.subset_len, sp.prefix_len, 0, sp.change_min, sp.change_max};
+    memcpy(tab + f * sizeof(F), &F, sizeof(F));
+    memcpy(tab + o_bytes + (size_t)f * drp::FAN_FBYTES, fb.b, drp::FAN_FBYTES);
+    P.any_flags |= sp.fflags;
+    if ((sp.fflags & DRP_SEL_SUBSET_EQ) && sp.subset_len) P.any_bytes |= DRP_SEL_SUBSET_EQ;
+    if ((sp.fflags & DRP_SEL_KEY_PREFIX) && sp.prefix_len) P.any_bytes |= DRP_SEL_KEY_PREFIX;
+  }
+  return DRP_OK;
+}
+
+// (after the scratch is placed) the checked table of fanout_filters to the device
+static int fanout_send_filters(drp_ctx *c, const drp::FanParams &P) {
+  const size_t total = al((size_t)P.nfilters * sizeof(drp::FanFilter)) + (size_t)P.nfilters * drp::FAN_FBYTES;
+  if (!c->fan_ev && hipEventCreateWithFlags(&c->fan_ev, hipEventDisableTiming) != hipSuccess) return DRP_E_HIP;
+  CHK(hipEventSynchronize(c->fan_ev));  // (never recorded: returns at once)
+  if (!c->fan_tab.ensure(total)) return DRP_E_NOMEM;
+  memcpy(c->fan_tab.p, c->host_tmp.data(), total);
+  // (filt is the scratch's first byte and the byte strings follow at the same offset as in the table)
+  CHK(hipMemcpyAsync(const_cast<drp::FanFilter *>(P.filt), c->fan_tab.p, total, hipMemcpyHostToDevice, c->st));
+  CHK(hipEventRecord(c->fan_ev, c->st));
+  return DRP_OK;
+}
+
+static void fanout_out(drp::FanParams &P, const drp_change_src *o, uint64_t rows_cap, uint64_t *sel_idx,
+                       uint64_t *row_base) {
+  drp::SelectParams sp;
+  select_out(sp, o, sel_idx, nullptr);
+  P.o_key_off = sp.o_key_off;
+  P.o_key_len = sp.o_key_len;
+  P.o_subset_off = sp.o_subset_off;
+  P.o_subset_len = sp.o_subset_len;
+  P.o_value_off = sp.o_value_off;
+  P.o_value_len = sp.o_value_len;
+  P.o_change = sp.o_change;
+  P.o_from = sp.o_from;
+  P.o_to = sp.o_to;
+  P.o_flags = sp.o_flags;
+  P.sel_idx = sel_idx;
+  P.rows_cap = rows_cap;
+  P.row_base = row_base;
+}
+
+int drp_fanout_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                      const drp_changes *cols, uint64_t n, const drp_filter *filters, uint32_t nfilters,
+                      const drp_change_src *out_rows, uint64_t rows_cap, uint64_t *sel_idx, uint64_t *row_base,
+                      const drp_splice *splice) {
+  if (!c || !frames || !cols || !out_rows || !row_base || (!bytes && nbytes)) return DRP_E_INVAL;
+  if (n && (!frames->payload_off || !frames->type || !cols->key_off || !cols->key_len || !cols->subset_off ||
+            !cols->subset_len || !cols->value_off || !cols->value_len || !cols->change || !cols->from || !cols->to ||
+            !cols->flags || !out_rows->key_off || !out_rows->key_len || !out_rows->subset_off ||
+            !out_rows->subset_len || !out_rows->value_off || !out_rows->value_len || !out_rows->change ||
+            !out_rows->from || !out_rows->to || !out_rows->flags))
+    return DRP_E_INVAL;
+  if (splice && (!splice->n_blobs || (splice->blob_cap && (!splice->blob_row || !splice->blob_rank)))) return DRP_E_INVAL;
+  drp::FanParams P;
+  memset(&P, 0, sizeof(P));
+  if (const int rc = fanout_filters(c, filters, nfilters, P)) return rc;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  // (the decode scratch: free between decodes, and every user is ordered on the ctx's stream)
+  if (!c->scratch.ensure(drp_fanout_scratch_bytes(n, nfilters))) return DRP_E_NOMEM;
+  P.bytes = bytes;
+  P.nbytes = nbytes;
+  P.payload_off = frames->payload_off;
+  P.type = frames->type;
+  P.cols = *cols;
+  P.n = n;
+  drp_fanout_place(&P, c->scratch.p);
+  fanout_out(P, out_rows, rows_cap, sel_idx, row_base);
+  if (const int rc = fanout_send_filters(c, P)) return rc;
+  CHK(drp_launch_fanout_count(&P, c->st));
+  CHK(drp_launch_fanout_scatter(&P, c->st));
+  if (splice) {
+    P.blob_row = splice->blob_row;
+    P.blob_rank = splice->blob_rank;
+    P.n_blobs = splice->n_blobs;
+    P.blob_cap = splice->blob_cap;
+    CHK(drp_launch_fanout_splice(&P, c->st));
+  }
+  return DRP_OK;
+}
+
+int drp_fanout_staged(drp_ctx *c, const drp_filter *filters, uint32_t nfilters, uint8_t *out, uint64_t cap,
+                      uint64_t *out_off, uint64_t *n_selected, uint64_t *blob_row, uint64_t *blob_pos,
+                      uint64_t blob_cap, uint64_t *n_blobs) {
+  if (!c || !out_off || !n_selected || (!out && cap)) return DRP_E_INVAL;
+  if (blob_row ? (!n_blobs || (!blob_pos && blob_cap)) : (n_blobs != nullptr)) return DRP_E_INVAL;
+  auto &S = c->staged;
+  if (!S.valid) return DRP_E_INVAL;
+  drp::FanParams P;
+  memset(&P, 0, sizeof(P));
+  if (const int rc = fanout_filters(c, filters, nfilters, P)) return rc;
+  const uint32_t K = nfilters;
+  for (uint32_t f = 0; f <= K; f++) out_off[f] = 0;
+  for (uint32_t f = 0; f < K; f++) n_selected[f] = 0;
+  if (n_blobs) *n_blobs = 0;
+  const uint64_t n = S.good;  // the delivered GPU rows (a carried blob's row 0 is built on the host)
+  if (!n) return DRP_OK;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  hipStream_t st = c->st;
+  // scratch (the decode's, free until the next decode): the kernels' words, row_base with the grand
+  // total and the splice kernel's blob count behind it, the piece table
+  const uint64_t np = S.pieces.size();
+  const size_t o_base = al(drp_fanout_scratch_bytes(n, K)), o_piece = o_base + al((K + 3) * 8),
+               o_end = o_piece + al(2 * np * 8);
+  if (!c->scratch.ensure(o_end)) return DRP_E_NOMEM;
+  P.bytes = S.wire;
+  P.nbytes = S.wire_bytes;
+  P.payload_off = S.fr.payload_off;
+  P.type = S.fr.type;
+  P.cols = S.co;
+  P.n = n;
+  drp_fanout_place(&P, c->scratch.p);
+  uint64_t *drb = c->scratch.at<uint64_t>(o_base);
+  P.row_base = drb;
+  P.gtotal = drb + K + 1;  // (one readback brings the outputs' bounds and the blob count)
+  if (const int rc = fanout_send_filters(c, P)) return rc;
+  std::vector<uint64_t> &h = c->host_tmp;  // (its filter table has been copied out)
+  if (np > 1) {
+    h.resize(2 * np);
+    for (uint64_t k = 0; k < np; k++) {
+      h[k] = S.pieces[k].first;
+      h[np + k] = S.pieces[k].second - S.base;
+    }
+    CHK(hipMemcpyAsync(c->scratch.at<uint64_t>(o_piece), h.data(), 2 * np * 8, hipMemcpyHostToDevice, st));
+    P.piece_row = c->scratch.at<uint64_t>(o_piece);
+    P.piece_shift = P.piece_row + np;
+    P.npieces = np;
+  } else {
+    P.shift0 = np ? S.pieces[0].second - S.base : 0;
+  }
+  CHK(drp_launch_fanout_count(&P, st));
+  uint64_t rb[DRP_FANOUT_MAX + 2];
+  CHK(hipMemcpyAsync(rb, drb, (K + 2) * 8, hipMemcpyDeviceToHost, st));
+  CHK(hipStreamSynchronize(st));  // (the one readback that sizes the rows and the encode)
+  const uint64_t total = rb[K], nb_true = rb[K + 1] - rb[K];
+  for (uint32_t f = 0; f < K; f++) n_selected[f] = rb[f + 1] - rb[f];
+  if (n_blobs) *n_blobs = nb_true;
+  const uint64_t nb = (blob_row && nb_true <= blob_cap) ? nb_true : 0;  // the splice entries to produce
+  // the selected rows (sized from the true total) and the splice kernel's outputs
+  const size_t col = al(total * 8), o_brow = 10 * col, o_rank = o_brow + al(nb * 8);
+  if (!c->fan_rows.ensure(o_rank + al((size_t)K * nb * 8) + 256)) return DRP_E_NOMEM;
+  drp_change_src rows;
+  {
+    size_t o = 0;
+    auto take = [&]() { void *p = c->fan_rows.at<char>(o); o += col; return p; };
+    rows.key_off = (const uint64_t *)take();
+    rows.key_len = (const uint32_t *)take();
+    rows.subset_off = (const uint64_t *)take();
+    rows.subset_len = (const uint32_t *)take();
+    rows.value_off = (const uint64_t *)take();
+    rows.value_len = (const uint32_t *)take();
+    rows.change = (const uint64_t *)take();
+    rows.from = (const uint64_t *)take();
+    rows.to = (const uint64_t *)take();
+    rows.flags = (const uint8_t *)take();
+  }
+  fanout_out(P, &rows, total, nullptr, drb);
+  CHK(drp_launch_fanout_scatter(&P, st));
+  uint64_t *drank = c->fan_rows.at<uint64_t>(o_rank);
+  if (nb) {
+    P.blob_row = c->fan_rows.at<uint64_t>(o_brow);
+    P.blob_rank = drank;
+    P.n_blobs = drb + K + 2;  // (a word of its own: the grand total is still read by the kernel)
+    P.blob_cap = nb;
+    P.row_bias = S.nf0;
+    CHK(drp_launch_fanout_splice(&P, st));
+  }
+  // one encode of all outputs; its bytes go to `out` or, for a host `out`, to the output staging,
+  // which need not be larger than the outputs can get (none is longer than the staged wire)
+  const bool odev = is_device_ptr(out);
+  uint64_t nonempty = 0;
+  for (uint32_t f = 0; f < K; f++) nonempty += n_selected[f] != 0;
+  const uint64_t dcap = odev ? cap : std::min<uint64_t>(cap, nonempty * S.wire_bytes);
+  const size_t o_gat = al((total + 1) * 8), gat_n = (size_t)K + 1 + (size_t)K * nb, o_out = o_gat + al(gat_n * 8);
+  if (!c->out_stage.ensure(o_out + (odev ? 0 : dcap + 64))) return DRP_E_NOMEM;
+  uint64_t *foff = c->out_stage.at<uint64_t>(0), *dgat = c->out_stage.at<uint64_t>(o_gat);
+  uint8_t *dout = odev ? out : c->out_stage.at<uint8_t>(o_out);
+  if (const int rc = drp_encode_device(c, &rows, S.wire, S.wire_bytes, total, foff, dout, dcap)) return rc;
+  // the outputs' bounds and the blobs' byte positions, gathered into one block for one readback
+  CHK(drp_launch_fanout_gather(foff, drb, K, drank, nb, dgat, dgat + K + 1, st));
+  h.resize(gat_n + nb);
+  CHK(hipMemcpyAsync(h.data(), dgat, gat_n * 8, hipMemcpyDeviceToHost, st));
+  if (nb) CHK(hipMemcpyAsync(h.data() + gat_n, P.blob_row, nb * 8, hipMemcpyDeviceToHost, st));
+  CHK(hipStreamSynchronize(st));
+  if (h[K] == ~0ull) return DRP_E_INVAL;  // a row's key/subset/value range is outside the wire
+  for (uint32_t f = 0; f <= K; f++) out_off[f] = h[f];
+  if (h[K] > cap) return DRP_E_CAPACITY;
+  for (uint64_t j = 0; j < nb; j++) blob_row[j] = h[gat_n + j];
+  for (uint32_t f = 0; f < K && nb; f++)
+    memcpy(blob_pos + (uint64_t)f * blob_cap, h.data() + K + 1 + (uint64_t)f * nb, nb * 8);
+  if (!odev && h[K]) {
+    CHK(hipMemcpyAsync(out, dout, h[K], hipMemcpyDeviceToHost, st));
+    CHK(hipStreamSynchronize(st));
+  }
+  return DRP_OK;
 }
 
 int drp_index_scan(drp_ctx *c, const drp_stream_stats *stats, uint64_t count, uint64_t *base) {

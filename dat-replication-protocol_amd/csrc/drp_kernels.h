@@ -141,6 +141,46 @@ struct SelectBytes {
   uint8_t b[2 * DRP_SEL_MAX_BYTES];
 };
 
+// drp_fanout.hip: up to DRP_FANOUT_MAX filters over one pass of the decoded rows. One filter of
+// the device table (drp_filter without its pointers; conditions that are off hold neutral values)
+struct FanFilter {
+  uint32_t flags, subset_len, prefix_len, reserved;
+  uint64_t change_min, change_max;
+};
+constexpr uint32_t FAN_FBYTES = 2 * DRP_SEL_MAX_BYTES;  // per filter: subset, then key prefix
+
+struct FanParams {
+  const uint8_t *bytes;  // the wire the columns point into
+  uint64_t nbytes;
+  const uint64_t *payload_off;
+  const uint8_t *type;
+  drp_changes cols;  // (read only)
+  uint64_t n;
+  uint32_t nfilters;
+  uint32_t any_flags;  // the OR of the filters' flags: the columns the count step reads
+  uint32_t any_bytes;  // DRP_SEL_SUBSET_EQ / DRP_SEL_KEY_PREFIX: some filter compares such bytes
+  const FanFilter *filt;  // [nfilters], device
+  const uint8_t *fbytes;  // [nfilters][FAN_FBYTES], device
+  // rows of a batch staged in pieces (as SelectParams)
+  const uint64_t *piece_row, *piece_shift;
+  uint64_t npieces, shift0;
+  // scratch: ballot words [nfilters + 1][nwords] (the last plane: the blob rows), counts
+  // [nfilters + 1][nwg] (scanned in place), the sums of every FAN_SCAN counts, the grand total
+  uint64_t *mask, *block_cnt, *bsum, *gtotal;
+  uint64_t nwg, nwords;
+  // outputs
+  uint64_t *o_key_off, *o_subset_off, *o_value_off;
+  uint32_t *o_key_len, *o_subset_len, *o_value_len;
+  uint64_t *o_change, *o_from, *o_to;
+  uint8_t *o_flags;
+  uint64_t *sel_idx;  // may be null
+  uint64_t rows_cap;
+  uint64_t *row_base;  // [nfilters + 1]
+  // splice table (fan_splice; blob_row null: none)
+  uint64_t *blob_row, *blob_rank, *n_blobs;
+  uint64_t blob_cap, row_bias;  // row_bias: added to every blob_row entry (rows the host put first)
+};
+
 }  // namespace drp
 
 extern "C" {
@@ -203,6 +243,19 @@ hipError_t drp_launch_key_post(const uint8_t *bytes, const uint64_t *tile_prefix
 uint64_t drp_select_scratch_bytes(uint64_t n);  // device scratch drp_launch_select needs for n rows
 uint32_t drp_select_known_flags(void);
 hipError_t drp_launch_select(const drp::SelectParams *P, const drp::SelectBytes *fb, void *scratch, hipStream_t st);
+// drp_fanout.hip. Scratch layout (drp_fanout_place sets P's scratch pointers from it): the filter
+// table, the byte strings, the ballot planes, the counts, the block sums, the grand total.
+uint64_t drp_fanout_scratch_bytes(uint64_t n, uint32_t nfilters);
+void drp_fanout_place(drp::FanParams *P, void *scratch);
+// count + scan: P->row_base[0 .. nfilters] and *P->gtotal (rows + blob rows) are written
+hipError_t drp_launch_fanout_count(const drp::FanParams *P, hipStream_t st);
+hipError_t drp_launch_fanout_scatter(const drp::FanParams *P, hipStream_t st);
+hipError_t drp_launch_fanout_splice(const drp::FanParams *P, hipStream_t st);
+// out_off[f] = frame_off[row_base[f]] (f <= nfilters); blob_pos[f * nb + j] = frame_off[row_base[f] +
+// rank[f * nb + j]] - out_off[f]
+hipError_t drp_launch_fanout_gather(const uint64_t *frame_off, const uint64_t *row_base, uint32_t nfilters,
+                                    const uint64_t *rank, uint64_t nb, uint64_t *out_off, uint64_t *blob_pos,
+                                    hipStream_t st);
 hipError_t drp_launch_index_scan(const drp_stream_stats *stats, uint64_t count, uint64_t *base,
                                  hipStream_t st);
 hipError_t drp_launch_stats_from_results(const drp_stream_result *res, const uint64_t *stream_off,

@@ -29,6 +29,7 @@ EXPORTS = [
     "drp_decode_fetch_block_ex", "drp_decode_fetch_keys",
     "drp_encode_size", "drp_encode_device",
     "drp_encode_batch", "drp_select_device", "drp_relay_staged", "drp_index_scan", "drp_stream_stats_from_results", "drp_device",
+    "drp_fanout_device", "drp_fanout_staged",
     "drp_comm_id", "drp_comm_init_rank", "drp_comm_init_all", "drp_comm_destroy",
     "drp_index_allgather", "drp_index_allgather_multi", "drp_index_allgather_host", "drp_device_count",
     "drp_host_alloc", "drp_host_free",
@@ -38,6 +39,7 @@ BLOB_SKIP_OFF, BLOB_SKIP_AUTO, BLOB_SKIP_ALWAYS = 0, 1, 2
 DRP_E_COMM = -7
 SEL_CHANGE_RANGE, SEL_SUBSET_EQ, SEL_SUBSET_NONE, SEL_KEY_PREFIX = 1, 2, 4, 8
 SEL_MAX_BYTES = 256
+FANOUT_MAX = 64
 COMM_ID_BYTES = 128
 
 P = C.c_void_p
@@ -109,6 +111,22 @@ def make_filter(change_range=None, subset=None, subset_none=False, key_prefix=No
     return f
 
 
+class Splice(C.Structure):
+    """drp_splice: the optional splice outputs of drp_fanout_device (device pointers)."""
+    _fields_ = [("blob_row", P), ("blob_rank", P), ("n_blobs", P), ("blob_cap", U64)]
+
+
+def filter_array(filters):
+    """A C array of drp_filter from make_filter results (None: the filter that keeps every
+    well-formed Change). Keeps the filters, and with them their byte strings, alive."""
+    arr = (Filter * max(1, len(filters)))()
+    arr._keep = list(filters)
+    for k, f in enumerate(filters):
+        if f is not None:
+            C.memmove(C.byref(arr, k * C.sizeof(Filter)), C.byref(f), C.sizeof(Filter))
+    return arr
+
+
 class Timing(C.Structure):
     _fields_ = [("decode_ms", C.c_float), ("finalize_ms", C.c_float), ("total_ms", C.c_float),
                 ("strict_reruns", U32), ("spec_repairs", U32), ("exact_retries", U32), ("verify_relisted", U32),
@@ -161,6 +179,9 @@ def lib():
         L.drp_select_device.argtypes = [P, P, U64, C.POINTER(Frames), C.POINTER(Changes), U64, C.POINTER(Filter),
                                         C.POINTER(ChangeSrc), P, P]
         L.drp_relay_staged.argtypes = [P, C.POINTER(Filter), P, U64, C.POINTER(U64), C.POINTER(U64)]
+        L.drp_fanout_device.argtypes = [P, P, U64, C.POINTER(Frames), C.POINTER(Changes), U64, C.POINTER(Filter), U32,
+                                        C.POINTER(ChangeSrc), U64, P, P, C.POINTER(Splice)]
+        L.drp_fanout_staged.argtypes = [P, C.POINTER(Filter), U32, P, U64, P, P, P, P, U64, P]
         L.drp_index_scan.argtypes = [P, P, U64, P]
         L.drp_stream_stats_from_results.argtypes = [P, P, P, U64, P]
         L.drp_device.argtypes = [P]
@@ -179,7 +200,7 @@ def lib():
                   "drp_decode_batch",
                   "drp_decode_stage", "drp_decode_stage_v", "drp_decode_fetch", "drp_encode_size",
                   "drp_encode_device", "drp_encode_batch", "drp_select_device", "drp_relay_staged", "drp_index_scan",
-                  "drp_stream_stats_from_results", "drp_device", "drp_comm_id", "drp_comm_init_rank",
+                  "drp_fanout_device", "drp_fanout_staged", "drp_stream_stats_from_results", "drp_device", "drp_comm_id", "drp_comm_init_rank",
                   "drp_comm_init_all", "drp_index_allgather", "drp_index_allgather_multi",
                   "drp_index_allgather_host", "drp_device_count"]:
             getattr(L, f).restype = C.c_int
@@ -475,6 +496,70 @@ class Ctx:
             e.written = int(written.value)
             raise e
         return buf[:int(written.value)].tobytes(), int(nsel.value)
+
+    # ---- fan-out: many filters over one batch --------------------------------------------
+    def fanout_device(self, wire_t, cols, n, filters, out_rows, rows_cap, sel_idx_t, row_base_t, splice=None):
+        """drp_fanout_device over torch CUDA tensors (asynchronous, on this ctx's stream): cols and
+        out_rows as select_device takes them (out_rows and sel_idx_t, which may be None, hold
+        rows_cap entries), filters a list of make_filter results (None: keep every Change),
+        row_base_t an int64 tensor of len(filters) + 1 entries. splice: None, or a dict of int64
+        tensors blob_row (blob_cap entries), blob_rank (len(filters) * blob_cap) and n_blobs (1)."""
+        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
+        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
+                     tp(cols["flags"]), None)
+        dst = ChangeSrc(*[tp(out_rows[k]) for k in ["key_off", "key_len", "subset_off", "subset_len",
+                                                      "value_off", "value_len", "change", "from", "to", "flags"]])
+        sp = None
+        if splice is not None:
+            sp = C.byref(Splice(tp(splice["blob_row"]), tp(splice["blob_rank"]), tp(splice["n_blobs"]),
+                                splice["blob_row"].numel() if splice["blob_row"] is not None else 0))
+        self.order_after_torch(wire_t)
+        rc = self.L.drp_fanout_device(self.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n,
+                                      filter_array(filters), len(filters), C.byref(dst), rows_cap, tp(sel_idx_t),
+                                      tp(row_base_t), sp)
+        _chk("drp_fanout_device", rc)
+        self.order_torch_after(wire_t)
+
+    def fanout_staged(self, filters, cap=None, splice=False, out=None, blob_cap=None):
+        """drp_fanout_staged over the batch last staged (decode_staged), filters a list of
+        make_filter results (None: keep every Change): returns ([wire bytes per filter],
+        [n_selected per filter], splice_or_None). cap=None: len(filters) times the staged batch's
+        length, which is always enough. A given cap that is too small raises
+        DrpError(DRP_E_CAPACITY) with .written = the size needed and .n_selected. splice=True: a
+        dict of n_blobs (the true count), blob_row (u64 per blob: its row as decode_staged numbers
+        them) and blob_pos (u64 [len(filters)][blobs]: its byte offset within each output), the two
+        arrays None when n_blobs exceeds blob_cap (None: as many as the staged batch can hold); raw:
+        the two arrays as they were passed to the library.
+        out: a host uint8 array to write into (at least cap bytes)."""
+        K = len(filters)
+        if cap is None:
+            cap = K * getattr(self, "_staged_len", 0)
+        buf = out if out is not None else np.zeros(max(16, cap), np.uint8)
+        out_off, nsel = np.zeros(K + 1, np.uint64), np.zeros(max(K, 1), np.uint64)
+        brow = bpos = nbl = None
+        if splice:
+            if blob_cap is None:
+                blob_cap = getattr(self, "_staged_len", 0) // 2 + 1  # (a blob frame is at least two bytes)
+            brow = np.full(max(blob_cap, 1), 0x5555555555555555, np.uint64)
+            bpos = np.full(max(K * blob_cap, 1), 0x5555555555555555, np.uint64)
+            nbl = np.zeros(1, np.uint64)
+        rc = self.L.drp_fanout_staged(self.h, filter_array(filters), K, _p(buf), cap, _p(out_off), _p(nsel),
+                                      _p(brow), _p(bpos), blob_cap or 0, _p(nbl))
+        if rc != DRP_OK:
+            e = DrpError("drp_fanout_staged", rc)
+            e.written = int(out_off[K]) if K <= FANOUT_MAX else 0
+            e.n_selected = [int(v) for v in nsel[:K]]
+            raise e
+        outs = [buf[int(out_off[f]):int(out_off[f + 1])].tobytes() for f in range(K)]
+        sp = None
+        if splice:
+            nb = int(nbl[0])
+            fits = nb <= blob_cap
+            sp = {"n_blobs": nb, "blob_row": brow[:nb].copy() if fits else None,
+                  "blob_pos": bpos[:K * blob_cap].reshape(K, blob_cap)[:, :nb].copy() if fits else None,
+                  "raw": (brow, bpos)}
+        return outs, [int(v) for v in nsel[:K]], sp
 
 
 class Comm:

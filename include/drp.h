@@ -18,6 +18,10 @@
  *       -> no reference counterpart (the reference has no relay): a predicate over the decoded
  *          Change columns (schema messages/schema.proto:1-8: subset, change, key) and the encoder
  *          above over the rows it keeps, the received wire serving as the encoder's heap.
+ *   drp_fanout_device / drp_fanout_staged
+ *       -> no reference counterpart: that select for many filters in one pass (a hub's peers), and
+ *          a splice table that keeps the blobs where Encoder.change / Encoder.blob put them between
+ *          the Changes (encode.js:77-107).
  *   drp_stream_stats + drp_index_scan
  *       -> no reference counterpart (the reference is single-stream); they build the
  *          global frame index after the per-GPU stats tables are all-gathered.
@@ -372,6 +376,53 @@ int drp_select_device(drp_ctx *ctx, const uint8_t *bytes, uint64_t nbytes, const
  * decode call. drp_encode_device, drp_select_device and an encode from device memory do not. */
 int drp_relay_staged(drp_ctx *ctx, const drp_filter *filter, uint8_t *out, uint64_t cap, uint64_t *written,
                      uint64_t *n_selected);
+
+/* ---- fan-out: many filters over one decoded batch ------------------------- */
+/* A hub relays one received batch to many peers, each with its own filter. The two entry points
+ * below evaluate up to DRP_FANOUT_MAX filters in one pass over the decoded rows (every column is
+ * read once, whatever the number of filters) and lay the kept rows of the filters end to end, so
+ * one encode produces every peer's bytes. No reference counterpart (the reference has no relay);
+ * the splice table restores the order encode.js:77-100 keeps between Changes and blobs. */
+#define DRP_FANOUT_MAX 64
+
+/* Optional splice outputs of drp_fanout_device (device pointers): where the blob frames of rows
+ * [0, n) (every row with (type & 0x3F) == DRP_TYPE_BLOB, partial ones included) belong in each
+ * output. */
+typedef struct drp_splice {
+  uint64_t *blob_row;  /* blob_cap entries: source row of each blob frame, in stream order */
+  uint64_t *blob_rank; /* nfilters * blob_cap: [f * blob_cap + j] = rows of output f before blob j */
+  uint64_t *n_blobs;   /* one entry: the true count (nothing is written to the arrays if > blob_cap) */
+  uint64_t blob_cap;
+} drp_splice;
+
+/* drp_select_device for nfilters filters at once (1 .. DRP_FANOUT_MAX; filters[f].flags == 0 selects
+ * every well-formed Change). Output f is rows [row_base[f], row_base[f + 1]) of out_rows and of
+ * sel_idx (device, may be NULL), each a stable compaction as drp_select_device's; row_base (device,
+ * nfilters + 1 entries) is always written and carries the true counts. out_rows' arrays and sel_idx
+ * hold rows_cap entries: if row_base[nfilters] > rows_cap nothing is written to them, otherwise rows
+ * at or beyond row_base[nfilters] are left untouched. drp_encode_device(ctx, out_rows, bytes, nbytes,
+ * row_base[nfilters], frame_off, ...) then encodes every output in one call: output f is
+ * out[frame_off[row_base[f]], frame_off[row_base[f + 1]]). splice may be NULL. Device pointers only
+ * (filters and the drp_splice struct itself are HOST memory, read before the call returns);
+ * asynchronous on drp_stream(ctx). DRP_E_INVAL: nfilters out of range, a filter drp_select_device
+ * rejects, the NULL pointers drp_select_device rejects, a NULL row_base. */
+int drp_fanout_device(drp_ctx *ctx, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                      const drp_changes *cols, uint64_t n, const drp_filter *filters, uint32_t nfilters,
+                      const drp_change_src *out_rows, uint64_t rows_cap, uint64_t *sel_idx, uint64_t *row_base,
+                      const drp_splice *splice);
+/* drp_relay_staged for nfilters filters at once, over the batch last staged (the same rows, the same
+ * validity rules and DRP_E_INVAL cases, the same bytes in every drp_set_blob_skip mode). Synchronous.
+ * The outputs lie end to end in `out` (host or device pointer, capacity cap): output f is
+ * out[out_off[f], out_off[f + 1]) and holds n_selected[f] Changes (out_off: HOST, nfilters + 1;
+ * n_selected: HOST, nfilters). DRP_E_CAPACITY: nothing is written to out, out_off[nfilters] = the
+ * size needed, n_selected is valid. Splice table (blob_row NULL: none; all HOST): blob_row[j] = the
+ * row, as drp_decode_fetch numbers them, of the batch's j-th blob frame (a leading continuation,
+ * fetch row 0 with DRP_FRAME_CONT, is not listed: it precedes every output); blob_pos[f * blob_cap +
+ * j] = the byte offset within output f at which that frame belongs. *n_blobs = the true count; if it
+ * exceeds blob_cap the two arrays are not written and the call still succeeds for out. */
+int drp_fanout_staged(drp_ctx *ctx, const drp_filter *filters, uint32_t nfilters, uint8_t *out, uint64_t cap,
+                      uint64_t *out_off, uint64_t *n_selected, uint64_t *blob_row, uint64_t *blob_pos,
+                      uint64_t blob_cap, uint64_t *n_blobs);
 
 /* ---- multi-GPU global index ---------------------------------------------- */
 /* stats[nranks*per_rank] (device): all-gathered per-stream tables in rank order.

@@ -11,10 +11,19 @@ probe, and the host relay through drp_relay_staged against the host round trip i
               (b) drp_decode_stage + drp_relay_staged
               and a check that both produce the same bytes.
 
+  fan-out     (--fanout-out) drp_fanout_device over the same decoded rows with K = 1, 8, 64 filters
+              change >= m_f (m_f spread over the stream's 1..100) against K back-to-back
+              drp_select_device calls, alternating, HIP events, the device leg's warm-up and
+              repeat counts; one K = 64 run of 64 distinct 8-byte key prefixes (the byte
+              conditions); and on the host batch drp_fanout_staged with K = 16 against 16
+              drp_relay_staged calls over the same staged batch, alternating, wall clock, with a
+              check that the bytes are the same. Written to --fanout-out as its own JSON line.
+
 Prints one JSON line (and writes it to --out). Needs an MI355X: there is no CPU path.
 
   hipcc -O3 --offload-arch=gfx950 scripts/probe_bw.hip -o exp/probe_bw
-  python scripts/bench_relay.py --probe exp/probe_bw --out profiles/relay/relay_bench.json
+  python scripts/bench_relay.py --probe exp/probe_bw --out profiles/relay/relay_bench.json \\
+      --fanout-out profiles/relay/fanout_bench.json
 """
 import argparse
 import ctypes as C
@@ -47,7 +56,8 @@ def run_probe(path):
     return res
 
 
-def device_leg(ctx, drp_amd, torch, S, frames, iters):
+def device_setup(ctx, drp_amd, torch, S, frames):
+    """frames C2 frames resident in HBM and decoded: (wire_t, cols, n)."""
     dev = torch.device("cuda", 0)
     wire = S.c2_stream(frames, seed=1)
     wire_t = torch.from_numpy(wire).to(dev)
@@ -67,6 +77,12 @@ def device_leg(ctx, drp_amd, torch, S, frames, iters):
     ctx.decode_device(wire_t, so_t, en_t, cols, cap, res_t)
     r = drp_amd.StreamResult.from_buffer_copy(res_t.cpu().numpy().tobytes())
     assert r.frames == n and r.err_code == 0, (r.frames, r.err_code)
+    return wire_t, cols, n
+
+
+def device_leg(ctx, drp_amd, torch, decoded, iters):
+    dev = torch.device("cuda", 0)
+    wire_t, cols, n = decoded
     rows = {k: torch.zeros(n, dtype=(torch.int32 if k.endswith("_len") else torch.uint8 if k == "flags"
                                       else torch.int64), device=dev) for k in SRC_KEYS}
     nsel_t = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -159,6 +175,168 @@ def host_leg(ctx, drp_amd, S, mib, runs):
             "same_bytes": same}
 
 
+def _stat(ts):
+    return {"median": statistics.median(ts), "min": min(ts), "max": max(ts)}
+
+
+def _row_tensors(torch, dev, room):
+    return {k: torch.zeros(room, dtype=(torch.int32 if k.endswith("_len") else torch.uint8 if k == "flags"
+                                         else torch.int64), device=dev) for k in SRC_KEYS}
+
+
+def fanout_device_leg(ctx, drp_amd, torch, decoded, iters):
+    """drp_fanout_device with K filters against K back-to-back drp_select_device calls over the
+    same decoded rows; the library is called directly (no per-call stream ordering in between)."""
+    dev = torch.device("cuda", 0)
+    wire_t, cols, n = decoded
+    L = ctx.L
+    tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    fr = drp_amd.Frames(tp(cols["payload_off"]), tp(cols["payload_len"]), tp(cols["type"]))
+    co = drp_amd.Changes(*[tp(cols[k]) for k in drp_amd.COLS32], tp(cols["change"]), tp(cols["from"]),
+                         tp(cols["to"]), tp(cols["flags"]), None)
+    ext = ctx._ext(dev)
+    one = _row_tensors(torch, dev, n)  # a single select's rows (every call of the sequence reuses them)
+    one_src = drp_amd.ChangeSrc(*[tp(one[k]) for k in SRC_KEYS])
+    nsel_t = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record(ext)
+        fn()
+        e1.record(ext)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def closed_form(m):  # rows with change = i % 100 + 1 >= m
+        keep = 100 - m + 1
+        return (n // 100) * keep + max(0, n % 100 - (m - 1))
+
+    res = {}
+    for K in (1, 8, 64):
+        ms = [1 + (f * 100) // K for f in range(K)]
+        flt = [drp_amd.make_filter(change_range=(m, 2**64 - 1)) for m in ms]
+        arr = drp_amd.filter_array(flt)
+        counts = [closed_form(m) for m in ms]
+        total = sum(counts)
+        many = _row_tensors(torch, dev, total)
+        many_src = drp_amd.ChangeSrc(*[tp(many[k]) for k in SRC_KEYS])
+        rb_t = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+
+        def fan():
+            rc = L.drp_fanout_device(ctx.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n, arr, K,
+                                     C.byref(many_src), total, None, tp(rb_t), None)
+            assert rc == 0, rc
+
+        def seq():
+            for f in flt:
+                rc = L.drp_select_device(ctx.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n, C.byref(f),
+                                         C.byref(one_src), None, tp(nsel_t))
+                assert rc == 0, rc
+
+        tf, ts = [], []
+        for it in range(iters + 3):  # (three warm-ups, as the device leg; alternating)
+            a, b = timed(fan), timed(seq)
+            if it >= 3:
+                tf.append(a)
+                ts.append(b)
+        rb = rb_t.cpu().numpy()
+        assert [int(rb[f + 1] - rb[f]) for f in range(K)] == counts, "fan-out counts"
+        assert int(nsel_t.cpu()[0]) == counts[-1]
+        # the last filter's output against the sequence's last select (the same rows, the same order)
+        a0 = int(rb[K - 1])
+        for k in ("change", "key_off", "flags"):
+            assert bool(torch.equal(many[k][a0:a0 + counts[-1]], one[k][:counts[-1]])), k
+        model = n * 10 + (K + 1) * n // 8 * 2 + n * 57 + total * WRITE_B  # count, ballots (written, read), scatter
+        res[f"K{K}"] = {"filters": K, "rows_out": total, "fanout_ms": _stat(tf), "sequential_ms": _stat(ts),
+                        "sequential_over_fanout": statistics.median(ts) / statistics.median(tf),
+                        "ranges_overlap": not (max(tf) < min(ts) or max(ts) < min(tf)),
+                        "fanout_model_bytes": model, "fanout_model_TBps": model / statistics.median(tf) / 1e9}
+        many = many_src = None  # (tens of GB at K = 64: freed before the next K allocates)
+        torch.cuda.empty_cache()
+    # the byte conditions: 64 distinct 8-byte key prefixes (each the first 8 of the 10 key digits: 100 rows)
+    K = 64
+    ps = [(f * (n // 100)) // K for f in range(K)]
+    flt = [drp_amd.make_filter(key_prefix=b"%08d" % p) for p in ps]
+    arr = drp_amd.filter_array(flt)
+    counts = [max(0, min(n, p * 100 + 100) - p * 100) for p in ps]
+    total = sum(counts)
+    many = _row_tensors(torch, dev, total)
+    many_src = drp_amd.ChangeSrc(*[tp(many[k]) for k in SRC_KEYS])
+    rb_t = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+
+    def fan_bytes():
+        rc = L.drp_fanout_device(ctx.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n, arr, K,
+                                 C.byref(many_src), total, None, tp(rb_t), None)
+        assert rc == 0, rc
+
+    tb = [timed(fan_bytes) for _ in range(iters + 3)][3:]
+    rb = rb_t.cpu().numpy()
+    assert [int(rb[f + 1] - rb[f]) for f in range(K)] == counts, "key prefix counts"
+    res["K64_key_prefix8"] = {"filters": K, "rows_out": total, "fanout_ms": _stat(tb)}
+    res["frames"] = n
+    res["iters"] = iters
+    return res
+
+
+def fanout_host_leg(ctx, drp_amd, S, mib, runs, K=16):
+    """drp_fanout_staged with K filters against K drp_relay_staged calls over the same staged batch
+    (staged once per timed run, outside the timed part: it is the same for both)."""
+    L = ctx.L
+    nbytes = mib << 20
+    wire = S.c2_stream(nbytes // 86 + 1, seed=1)[:nbytes].copy()
+    ms = [1 + (f * 100) // K for f in range(K)]
+    flt = [drp_amd.make_filter(change_range=(m, 2**64 - 1)) for m in ms]
+    arr = drp_amd.filter_array(flt)
+    U64, U32 = C.c_uint64, C.c_uint32
+    out_f, out_s = np.zeros(K * nbytes, np.uint8), np.zeros(K * nbytes, np.uint8)
+    off_f, nsel_f = np.zeros(K + 1, np.uint64), np.zeros(K, np.uint64)
+
+    def stage():
+        carry = drp_amd.Carry(0, 0, 0, 0, 0)
+        nf, ef, ec, ed = U64(), U64(), U32(), U32()
+        rc = L.drp_decode_stage(ctx.h, drp_amd._p(wire), nbytes, C.byref(carry), C.byref(nf), C.byref(ef),
+                                C.byref(ec), C.byref(ed))
+        assert rc == 0 and ec.value == 0, (rc, ec.value)
+
+    def fan():
+        rc = L.drp_fanout_staged(ctx.h, arr, K, drp_amd._p(out_f), out_f.size, drp_amd._p(off_f), drp_amd._p(nsel_f),
+                                 None, None, 0, None)
+        assert rc == 0, rc
+
+    def seq():
+        at, ns = 0, []
+        for f in flt:
+            written, nsel = U64(), U64()
+            rc = L.drp_relay_staged(ctx.h, C.byref(f), drp_amd._p(out_s[at:]), out_s.size - at, C.byref(written),
+                                    C.byref(nsel))
+            assert rc == 0, rc
+            at += int(written.value)
+            ns.append(int(nsel.value))
+        return at, ns
+
+    tf, ts = [], []
+    same = False
+    for it in range(runs + 2):  # (two warm-ups; alternating)
+        stage()
+        t0 = time.perf_counter()
+        fan()
+        t1 = time.perf_counter()
+        at, ns = seq()
+        t2 = time.perf_counter()
+        if it == 1:
+            same = (int(off_f[K]) == at and ns == [int(v) for v in nsel_f] and
+                    out_f[:at].tobytes() == out_s[:at].tobytes())
+            assert same, (int(off_f[K]), at)
+        if it >= 2:
+            tf.append((t1 - t0) * 1e3)
+            ts.append((t2 - t1) * 1e3)
+    return {"batch_bytes": nbytes, "filters": K, "out_bytes": int(off_f[K]), "rows_out": int(nsel_f.sum()),
+            "runs": runs, "fanout_staged_ms": _stat(tf), "sequential_relay_ms": _stat(ts),
+            "sequential_over_fanout": statistics.median(ts) / statistics.median(tf),
+            "ranges_overlap": not (max(tf) < min(ts) or max(ts) < min(tf)), "same_bytes": same}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20_000_000)
@@ -167,6 +345,7 @@ def main():
     ap.add_argument("--runs", type=int, default=11)
     ap.add_argument("--probe", default=None, help="a built scripts/probe_bw.hip")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--fanout-out", default=None, help="run the fan-out legs too and write their JSON line here")
     a = ap.parse_args()
     res = {"bench": "relay"}
     if a.probe:
@@ -179,10 +358,21 @@ def main():
     import drp_amd
     with drp_amd.Ctx(0) as ctx:
         ctx.set_blob_skip(drp_amd.BLOB_SKIP_OFF)
-        res["device"] = device_leg(ctx, drp_amd, torch, S, a.frames, a.iters)
+        decoded = device_setup(ctx, drp_amd, torch, S, a.frames)
+        res["device"] = device_leg(ctx, drp_amd, torch, decoded, a.iters)
         if a.probe and "cols_rd" in res["probe_bw"]:
             res["device"]["over_cols_rd"] = res["device"]["model_TBps"] / res["probe_bw"]["cols_rd"]["TBps"]
+        fan = None
+        if a.fanout_out:
+            fan = {"bench": "relay_fanout", "device": fanout_device_leg(ctx, drp_amd, torch, decoded, a.iters)}
+        del decoded
+        torch.cuda.empty_cache()
         res["host"] = host_leg(ctx, drp_amd, S, a.host_mib, a.runs)
+        if fan is not None:
+            fan["host"] = fanout_host_leg(ctx, drp_amd, S, a.host_mib, a.runs)
+            with open(a.fanout_out, "w") as f:
+                f.write(json.dumps(fan) + "\n")
+            print(json.dumps(fan))
     line = json.dumps(res)
     print(line)
     if a.out:
