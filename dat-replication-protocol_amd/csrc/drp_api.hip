@@ -220,6 +220,7 @@ struct drp_ctx {
   DevBuf keytext;   // drp_decode_fetch_keys: the key text
   double frames_per_byte = 0;  // density of the last staged batch (sizes the next one's columns)
   int blob_skip = DRP_BLOB_SKIP_AUTO;
+  uint64_t latest_hash_mask = ~0ull;  // drp_set_latest_hash_mask (test hook)
   bool blob_heavy = false;     // the last host batch was mostly blob payload (AUTO: stage in pieces)
   uint64_t blob_run = 0;       // bytes from a piece's start to its blob's payload, last seen
   uint64_t piece_span = 0;     // batch bytes one blob-skipping piece covered on average, last seen
@@ -414,6 +415,12 @@ int drp_set_strict(drp_ctx *c, int strict) {
 int drp_set_blob_skip(drp_ctx *c, int mode) {
   if (!c || mode < DRP_BLOB_SKIP_OFF || mode > DRP_BLOB_SKIP_ALWAYS) return DRP_E_INVAL;
   c->blob_skip = mode;
+  return DRP_OK;
+}
+
+int drp_set_latest_hash_mask(drp_ctx *c, uint64_t mask) {
+  if (!c) return DRP_E_INVAL;
+  c->latest_hash_mask = mask;
   return DRP_OK;
 }
 
@@ -2141,9 +2148,10 @@ static void select_out(drp::SelectParams &P, const drp_change_src *o, uint64_t *
   P.n_selected = n_selected;
 }
 
-int drp_select_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
-                      const drp_changes *cols, uint64_t n, const drp_filter *filter, const drp_change_src *out_rows,
-                      uint64_t *sel_idx, uint64_t *n_selected) {
+// drp_select_device, or with `latest` drp_latest_device: the same arguments and checks
+static int select_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                         const drp_changes *cols, uint64_t n, const drp_filter *filter, const drp_change_src *out_rows,
+                         uint64_t *sel_idx, uint64_t *n_selected, bool latest) {
   if (!c || !frames || !cols || !out_rows || !n_selected || (!bytes && nbytes)) return DRP_E_INVAL;
   if (n && (!frames->payload_off || !frames->type || !cols->key_off || !cols->key_len || !cols->subset_off ||
             !cols->subset_len || !cols->value_off || !cols->value_len || !cols->change || !cols->from || !cols->to ||
@@ -2158,7 +2166,7 @@ int drp_select_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const d
   if (const int rc = select_filter(filter, P, fb)) return rc;
   if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
   // (the decode scratch: free between decodes, and every user is ordered on the ctx's stream)
-  if (!c->scratch.ensure(drp_select_scratch_bytes(n))) return DRP_E_NOMEM;
+  if (!c->scratch.ensure(latest ? drp_latest_scratch_bytes(n) : drp_select_scratch_bytes(n))) return DRP_E_NOMEM;
   P.bytes = bytes;
   P.nbytes = nbytes;
   P.payload_off = frames->payload_off;
@@ -2166,12 +2174,26 @@ int drp_select_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const d
   P.cols = *cols;
   P.n = n;
   select_out(P, out_rows, sel_idx, n_selected);
-  CHK(drp_launch_select(&P, &fb, c->scratch.p, c->st));
+  if (latest) CHK(drp_launch_latest(&P, &fb, c->latest_hash_mask, c->scratch.p, c->st));
+  else CHK(drp_launch_select(&P, &fb, c->scratch.p, c->st));
   return DRP_OK;
 }
 
-int drp_relay_staged(drp_ctx *c, const drp_filter *filter, uint8_t *out, uint64_t cap, uint64_t *written,
-                     uint64_t *n_selected) {
+int drp_select_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                      const drp_changes *cols, uint64_t n, const drp_filter *filter, const drp_change_src *out_rows,
+                      uint64_t *sel_idx, uint64_t *n_selected) {
+  return select_device(c, bytes, nbytes, frames, cols, n, filter, out_rows, sel_idx, n_selected, false);
+}
+
+int drp_latest_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                      const drp_changes *cols, uint64_t n, const drp_filter *filter, const drp_change_src *out_rows,
+                      uint64_t *sel_idx, uint64_t *n_selected) {
+  return select_device(c, bytes, nbytes, frames, cols, n, filter, out_rows, sel_idx, n_selected, true);
+}
+
+// drp_relay_staged, or with `latest` drp_latest_staged: the latest-per-key step in the select's place
+static int relay_staged(drp_ctx *c, const drp_filter *filter, uint8_t *out, uint64_t cap, uint64_t *written,
+                        uint64_t *n_selected, bool latest) {
   if (!c || !written || !n_selected || (!out && cap)) return DRP_E_INVAL;
   auto &S = c->staged;
   if (!S.valid) return DRP_E_INVAL;
@@ -2189,7 +2211,7 @@ int drp_relay_staged(drp_ctx *c, const drp_filter *filter, uint8_t *out, uint64_
   // scratch (the decode's, free until the next decode): the kernel's words, the count, the piece
   // table, the selected rows' columns
   const uint64_t np = S.pieces.size();
-  const size_t o_cnt = al(drp_select_scratch_bytes(n)), o_piece = o_cnt + 256, o_rows = o_piece + al(2 * np * 8),
+  const size_t o_cnt = al(latest ? drp_latest_scratch_bytes(n) : drp_select_scratch_bytes(n)), o_piece = o_cnt + 256, o_rows = o_piece + al(2 * np * 8),
                o_end = o_rows + 10 * al(n * 8);
   if (!c->scratch.ensure(o_end)) return DRP_E_NOMEM;
   uint64_t *dcnt = c->scratch.at<uint64_t>(o_cnt);
@@ -2231,12 +2253,23 @@ int drp_relay_staged(drp_ctx *c, const drp_filter *filter, uint8_t *out, uint64_
   P.cols = S.co;
   P.n = n;
   select_out(P, &rows, nullptr, dcnt);
-  CHK(drp_launch_select(&P, &fb, c->scratch.p, st));
+  if (latest) CHK(drp_launch_latest(&P, &fb, c->latest_hash_mask, c->scratch.p, st));
+  else CHK(drp_launch_select(&P, &fb, c->scratch.p, st));
   uint64_t nsel = 0;
   CHK(hipMemcpyAsync(&nsel, dcnt, 8, hipMemcpyDeviceToHost, st));
   CHK(hipStreamSynchronize(st));  // (the one readback that sizes the encode)
   *n_selected = nsel;
   return drp_encode_batch(c, &rows, S.wire, S.wire_bytes, nsel, out, cap, written);
+}
+
+int drp_relay_staged(drp_ctx *c, const drp_filter *filter, uint8_t *out, uint64_t cap, uint64_t *written,
+                     uint64_t *n_selected) {
+  return relay_staged(c, filter, out, cap, written, n_selected, false);
+}
+
+int drp_latest_staged(drp_ctx *c, const drp_filter *filter, uint8_t *out, uint64_t cap, uint64_t *written,
+                      uint64_t *n_selected) {
+  return relay_staged(c, filter, out, cap, written, n_selected, true);
 }
 
 // ---- fan-out ------------------------------------------------------------------------------------

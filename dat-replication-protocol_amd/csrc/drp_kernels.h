@@ -141,6 +141,21 @@ struct SelectBytes {
   uint8_t b[2 * DRP_SEL_MAX_BYTES];
 };
 
+// drp_latest.hip: the select's candidates grouped by (subset presence, subset bytes, key bytes) in
+// an insert-only open-addressing table, the row with the greatest (change, row) of every group kept
+struct LatestParams {
+  SelectParams sel;  // the select's parameters: predicate, scratch and outputs as there
+  // table: nslots (a power of two >= 2 n) slots of three words, all zero before the insert step:
+  //   [0] rep: hash tag | (the row that claimed the slot + 1); [1] the greatest change of the
+  //   group; [2] the greatest row + 1 among those that carry it
+  uint64_t *tab;
+  uint64_t nslots;
+  uint64_t *slot;      // [n] the slot of row i's group, LAT_NONE for a row that is no candidate
+  uint64_t hash_mask;  // ANDed with the row hash before the tag and the start slot are taken (test hook)
+  uint64_t tag_mask;   // rep's hash bits: the high 32 when n < 2^32 - 1 (rows fit the low 32), else none
+};
+constexpr uint64_t LAT_NONE = ~0ull;
+
 // drp_fanout.hip: up to DRP_FANOUT_MAX filters over one pass of the decoded rows. One filter of
 // the device table (drp_filter without its pointers; conditions that are off hold neutral values)
 struct FanFilter {
@@ -243,6 +258,14 @@ hipError_t drp_launch_key_post(const uint8_t *bytes, const uint64_t *tile_prefix
 uint64_t drp_select_scratch_bytes(uint64_t n);  // device scratch drp_launch_select needs for n rows
 uint32_t drp_select_known_flags(void);
 hipError_t drp_launch_select(const drp::SelectParams *P, const drp::SelectBytes *fb, void *scratch, hipStream_t st);
+// its pieces, for drp_latest.hip: the scratch pointers and the filter's bytes (n > 0), and the scan
+// and scatter over the ballot words and workgroup counts already in P's scratch
+hipError_t drp_select_place(drp::SelectParams *P, const drp::SelectBytes *fb, void *scratch, hipStream_t st);
+hipError_t drp_launch_select_compact(const drp::SelectParams *P, hipStream_t st);
+// drp_latest.hip. Scratch: the select's (drp_select_scratch_bytes(n)), then slot[n], then the table.
+uint64_t drp_latest_scratch_bytes(uint64_t n);
+hipError_t drp_launch_latest(const drp::SelectParams *P, const drp::SelectBytes *fb, uint64_t hash_mask,
+                             void *scratch, hipStream_t st);
 // drp_fanout.hip. Scratch layout (drp_fanout_place sets P's scratch pointers from it): the filter
 // table, the byte strings, the ballot planes, the counts, the block sums, the grand total.
 uint64_t drp_fanout_scratch_bytes(uint64_t n, uint32_t nfilters);

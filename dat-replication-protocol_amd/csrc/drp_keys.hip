@@ -14,69 +14,7 @@
 namespace drp {
 namespace keys {
 
-constexpr uint64_t P1 = 11400714785074694791ull, P2 = 14029467366897019727ull, P3 = 1609587929392839161ull,
-                   P4 = 9650029242287828579ull, P5 = 2870177450012600261ull;
-
-__device__ __forceinline__ uint64_t rotl(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
-__device__ __forceinline__ uint64_t round1(uint64_t acc, uint64_t in) { return rotl(acc + in * P2, 31) * P1; }
-__device__ __forceinline__ uint64_t merge(uint64_t acc, uint64_t v) { return (acc ^ round1(0, v)) * P1 + P4; }
-
-// little-endian reads of byte-addressed global memory (keys have any alignment)
-__device__ __forceinline__ uint64_t rd64(const uint8_t *p) {
-  uint64_t v = 0;
-#pragma unroll
-  for (int i = 0; i < 8; i++) v |= (uint64_t)p[i] << (8 * i);
-  return v;
-}
-__device__ __forceinline__ uint32_t rd32(const uint8_t *p) {
-  return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-
-// XXH64, seed 0 (the published algorithm; tests check it against python-xxhash)
-__device__ uint64_t xxh64(const uint8_t *p, uint32_t len) {
-  const uint8_t *end = p + len;
-  uint64_t h;
-  if (len >= 32) {
-    uint64_t v1 = P1 + P2, v2 = P2, v3 = 0, v4 = 0 - P1;
-    const uint8_t *lim = end - 32;
-    do {
-      v1 = round1(v1, rd64(p));
-      v2 = round1(v2, rd64(p + 8));
-      v3 = round1(v3, rd64(p + 16));
-      v4 = round1(v4, rd64(p + 24));
-      p += 32;
-    } while (p <= lim);
-    h = rotl(v1, 1) + rotl(v2, 7) + rotl(v3, 12) + rotl(v4, 18);
-    h = merge(h, v1);
-    h = merge(h, v2);
-    h = merge(h, v3);
-    h = merge(h, v4);
-  } else {
-    h = P5;
-  }
-  h += len;
-  while (p + 8 <= end) {
-    h ^= round1(0, rd64(p));
-    h = rotl(h, 27) * P1 + P4;
-    p += 8;
-  }
-  if (p + 4 <= end) {
-    h ^= (uint64_t)rd32(p) * P1;
-    h = rotl(h, 23) * P2 + P3;
-    p += 4;
-  }
-  while (p < end) {
-    h ^= (uint64_t)(*p) * P5;
-    h = rotl(h, 11) * P1;
-    p++;
-  }
-  h ^= h >> 33;
-  h *= P2;
-  h ^= h >> 29;
-  h *= P3;
-  h ^= h >> 32;
-  return h;
-}
+using namespace xxh;  // (XXH64: drp_device.h)
 
 // DRP_F_KEY_ASCII | DRP_F_KEY_UTF8 for the key bytes
 __device__ uint32_t key_class(const uint8_t *p, uint32_t len) {

@@ -12,61 +12,11 @@
 // the order of the rows is kept. The columns are read one 1 / 4 / 8-byte element per lane,
 // consecutive lanes consecutive elements; step (1) reads only the columns the filter names and
 // step (3) only the rows kept (the byte compares read wire bytes only of rows whose lengths match).
-#include "drp_device.h"
-#include "drp_kernels.h"
+#include "drp_select.h"  // (the predicate: sel_pred, sel_shift, SEL_BLK)
 
 namespace drp {
 
-constexpr uint32_t SEL_BLK = 1024, SEL_WAVES = SEL_BLK / 64;
 constexpr uint32_t SEL_KNOWN = DRP_SEL_CHANGE_RANGE | DRP_SEL_SUBSET_EQ | DRP_SEL_SUBSET_NONE | DRP_SEL_KEY_PREFIX;
-
-// what row i's payload offsets lack to be offsets into P.bytes
-__device__ __forceinline__ uint64_t sel_shift(const SelectParams &P, uint64_t i) {
-  if (P.npieces <= 1) return P.shift0;
-  uint64_t lo = 0, hi = P.npieces;  // piece_row[lo] <= i < piece_row[hi]
-  while (hi - lo > 1) {
-    const uint64_t mid = (lo + hi) >> 1;
-    if (P.piece_row[mid] <= i) lo = mid;
-    else hi = mid;
-  }
-  return P.piece_shift[lo];
-}
-
-// wire bytes [off, off + len) == ref[0, len); a range outside the wire matches nothing
-__device__ __forceinline__ bool sel_bytes_eq(const SelectParams &P, uint64_t off, uint32_t len, const uint8_t *ref) {
-  if ((uint64_t)len > P.nbytes || off > P.nbytes - len) return false;
-  const uint8_t *w = P.bytes + off;
-  for (uint32_t k = 0; k < len; k++)
-    if (w[k] != ref[k]) return false;
-  return true;
-}
-
-__device__ __forceinline__ bool sel_pred(const SelectParams &P, uint64_t i) {
-  const drp_changes &c = P.cols;
-  if ((P.type[i] & 0x3F) != DRP_TYPE_CHANGE) return false;
-  const uint32_t fl = c.flags[i];
-  if (fl & DRP_F_BAD) return false;
-  const uint32_t ff = P.fflags;
-  if (ff & DRP_SEL_CHANGE_RANGE) {
-    const uint64_t v = c.change[i];
-    if (v < P.change_min || v > P.change_max) return false;
-  }
-  if ((ff & DRP_SEL_SUBSET_NONE) && (fl & DRP_F_SUBSET)) return false;
-  if (ff & DRP_SEL_SUBSET_EQ) {
-    if (!(fl & DRP_F_SUBSET) || c.subset_len[i] != P.subset_len) return false;
-  }
-  if ((ff & DRP_SEL_KEY_PREFIX) && c.key_len[i] < P.prefix_len) return false;
-  // the byte compares last: only rows whose lengths match read the wire
-  if ((ff & DRP_SEL_SUBSET_EQ) && P.subset_len) {
-    const uint64_t off = P.payload_off[i] + sel_shift(P, i) + c.subset_off[i];
-    if (!sel_bytes_eq(P, off, P.subset_len, P.subset)) return false;
-  }
-  if ((ff & DRP_SEL_KEY_PREFIX) && P.prefix_len) {
-    const uint64_t off = P.payload_off[i] + sel_shift(P, i) + c.key_off[i];
-    if (!sel_bytes_eq(P, off, P.prefix_len, P.prefix)) return false;
-  }
-  return true;
-}
 
 // the filter's byte strings into device memory (they travel as launch arguments: no host buffer
 // to keep alive behind an asynchronous copy)
@@ -163,21 +113,34 @@ extern "C" uint64_t drp_select_scratch_bytes(uint64_t n) {
 
 extern "C" void drp_dbg_mark(const char *name, hipStream_t st);  // (drp_api.hip: DRP_WATCHDOG)
 
+// P's scratch pointers into `scratch` and the filter's byte strings onto the device (n > 0)
+extern "C" hipError_t drp_select_place(SelectParams *P, const SelectBytes *fb, void *scratch, hipStream_t st) {
+  if (sel_nblk(P->n) >= (1ull << 31)) return hipErrorInvalidValue;
+  uint8_t *sc = static_cast<uint8_t *>(scratch);
+  P->subset = sc;
+  P->prefix = sc + DRP_SEL_MAX_BYTES;
+  P->mask = reinterpret_cast<uint64_t *>(sc + 2 * DRP_SEL_MAX_BYTES);
+  P->block_cnt = reinterpret_cast<uint64_t *>(sc + 2 * DRP_SEL_MAX_BYTES + sel_mask_bytes(P->n));
+  if (P->fflags & (DRP_SEL_SUBSET_EQ | DRP_SEL_KEY_PREFIX))
+    hipLaunchKernelGGL(sel_filter_kernel, dim3(1), dim3(2 * DRP_SEL_MAX_BYTES), 0, st, *fb, sc);
+  return hipSuccess;
+}
+
+// steps (2) and (3) over the ballot words and workgroup counts a step (1) has left in P's scratch
+extern "C" hipError_t drp_launch_select_compact(const SelectParams *Pp, hipStream_t st) {
+  const SelectParams &P = *Pp;
+  const uint64_t nblk = sel_nblk(P.n);
+  hipLaunchKernelGGL(sel_scan_kernel, dim3(1), dim3(SEL_BLK), 0, st, P, nblk);
+  hipLaunchKernelGGL(sel_scatter_kernel, dim3((uint32_t)nblk), dim3(SEL_BLK), 0, st, P);
+  return hipGetLastError();
+}
+
 extern "C" hipError_t drp_launch_select(const SelectParams *Pp, const SelectBytes *fb, void *scratch, hipStream_t st) {
   SelectParams P = *Pp;
   if (P.n == 0) return hipMemsetAsync(P.n_selected, 0, 8, st);
-  const uint64_t nblk = sel_nblk(P.n);
-  if (nblk >= (1ull << 31)) return hipErrorInvalidValue;
-  uint8_t *sc = static_cast<uint8_t *>(scratch);
-  P.subset = sc;
-  P.prefix = sc + DRP_SEL_MAX_BYTES;
-  P.mask = reinterpret_cast<uint64_t *>(sc + 2 * DRP_SEL_MAX_BYTES);
-  P.block_cnt = reinterpret_cast<uint64_t *>(sc + 2 * DRP_SEL_MAX_BYTES + sel_mask_bytes(P.n));
-  if (P.fflags & (DRP_SEL_SUBSET_EQ | DRP_SEL_KEY_PREFIX))
-    hipLaunchKernelGGL(sel_filter_kernel, dim3(1), dim3(2 * DRP_SEL_MAX_BYTES), 0, st, *fb, sc);
-  hipLaunchKernelGGL(sel_count_kernel, dim3((uint32_t)nblk), dim3(SEL_BLK), 0, st, P);
-  hipLaunchKernelGGL(sel_scan_kernel, dim3(1), dim3(SEL_BLK), 0, st, P, nblk);
-  hipLaunchKernelGGL(sel_scatter_kernel, dim3((uint32_t)nblk), dim3(SEL_BLK), 0, st, P);
+  if (const hipError_t e = drp_select_place(&P, fb, scratch, st)) return e;
+  hipLaunchKernelGGL(sel_count_kernel, dim3((uint32_t)sel_nblk(P.n)), dim3(SEL_BLK), 0, st, P);
+  const hipError_t e = drp_launch_select_compact(&P, st);  // (the last error of all the launches)
   drp_dbg_mark("select", st);
-  return hipGetLastError();
+  return e;
 }

@@ -30,6 +30,7 @@ EXPORTS = [
     "drp_encode_size", "drp_encode_device",
     "drp_encode_batch", "drp_select_device", "drp_relay_staged", "drp_index_scan", "drp_stream_stats_from_results", "drp_device",
     "drp_fanout_device", "drp_fanout_staged",
+    "drp_latest_device", "drp_latest_staged", "drp_set_latest_hash_mask",
     "drp_comm_id", "drp_comm_init_rank", "drp_comm_init_all", "drp_comm_destroy",
     "drp_index_allgather", "drp_index_allgather_multi", "drp_index_allgather_host", "drp_device_count",
     "drp_host_alloc", "drp_host_free",
@@ -182,6 +183,9 @@ def lib():
         L.drp_fanout_device.argtypes = [P, P, U64, C.POINTER(Frames), C.POINTER(Changes), U64, C.POINTER(Filter), U32,
                                         C.POINTER(ChangeSrc), U64, P, P, C.POINTER(Splice)]
         L.drp_fanout_staged.argtypes = [P, C.POINTER(Filter), U32, P, U64, P, P, P, P, U64, P]
+        L.drp_latest_device.argtypes = L.drp_select_device.argtypes
+        L.drp_latest_staged.argtypes = L.drp_relay_staged.argtypes
+        L.drp_set_latest_hash_mask.argtypes = [P, U64]
         L.drp_index_scan.argtypes = [P, P, U64, P]
         L.drp_stream_stats_from_results.argtypes = [P, P, P, U64, P]
         L.drp_device.argtypes = [P]
@@ -200,7 +204,8 @@ def lib():
                   "drp_decode_batch",
                   "drp_decode_stage", "drp_decode_stage_v", "drp_decode_fetch", "drp_encode_size",
                   "drp_encode_device", "drp_encode_batch", "drp_select_device", "drp_relay_staged", "drp_index_scan",
-                  "drp_fanout_device", "drp_fanout_staged", "drp_stream_stats_from_results", "drp_device", "drp_comm_id", "drp_comm_init_rank",
+                  "drp_fanout_device", "drp_fanout_staged", "drp_latest_device", "drp_latest_staged",
+                  "drp_set_latest_hash_mask", "drp_stream_stats_from_results", "drp_device", "drp_comm_id", "drp_comm_init_rank",
                   "drp_comm_init_all", "drp_index_allgather", "drp_index_allgather_multi",
                   "drp_index_allgather_host", "drp_device_count"]:
             getattr(L, f).restype = C.c_int
@@ -460,7 +465,7 @@ class Ctx:
         return out[:int(written.value)].tobytes()
 
     # ---- select + re-encode (relay) ---------------------------------------------------
-    def select_device(self, wire_t, cols, n, filter, out_rows, sel_idx_t, n_selected_t):
+    def select_device(self, wire_t, cols, n, filter, out_rows, sel_idx_t, n_selected_t, _fn="drp_select_device"):
         """drp_select_device over torch CUDA tensors (asynchronous, on this ctx's stream): cols
         holds the decoded columns (payload_off, type and the Change columns, as decode_device
         wrote them), out_rows the drp_change_src columns to fill (n entries each: int64 offsets
@@ -473,13 +478,13 @@ class Ctx:
         dst = ChangeSrc(*[tp(out_rows[k]) for k in ["key_off", "key_len", "subset_off", "subset_len",
                                                       "value_off", "value_len", "change", "from", "to", "flags"]])
         self.order_after_torch(wire_t)
-        rc = self.L.drp_select_device(self.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n,
-                                      C.byref(filter) if filter is not None else None, C.byref(dst),
-                                      tp(sel_idx_t), tp(n_selected_t))
-        _chk("drp_select_device", rc)
+        rc = getattr(self.L, _fn)(self.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n,
+                                  C.byref(filter) if filter is not None else None, C.byref(dst),
+                                  tp(sel_idx_t), tp(n_selected_t))
+        _chk(_fn, rc)
         self.order_torch_after(wire_t)
 
-    def relay_staged(self, filter=None, cap=None, out=None):
+    def relay_staged(self, filter=None, cap=None, out=None, _fn="drp_relay_staged"):
         """drp_relay_staged over the batch last staged (decode_staged): returns (wire_bytes,
         n_selected). cap=None: the staged batch's length, which is always enough (the canonical
         encoding of a Change is never longer than the one received), so one call does it. A given
@@ -490,12 +495,29 @@ class Ctx:
         if cap is None:
             cap = getattr(self, "_staged_len", 0)
         buf = out if out is not None else np.zeros(max(16, cap), np.uint8)
-        rc = self.L.drp_relay_staged(self.h, fp, _p(buf), cap, C.byref(written), C.byref(nsel))
+        rc = getattr(self.L, _fn)(self.h, fp, _p(buf), cap, C.byref(written), C.byref(nsel))
         if rc != DRP_OK:
-            e = DrpError("drp_relay_staged", rc)
+            e = DrpError(_fn, rc)
             e.written = int(written.value)
             raise e
         return buf[:int(written.value)].tobytes(), int(nsel.value)
+
+    # ---- latest per key (relay fan-in) ---------------------------------------------------
+    def latest_device(self, wire_t, cols, n, filter, out_rows, sel_idx_t, n_selected_t):
+        """drp_latest_device: select_device's arguments; of the rows the filter keeps, the one with
+        the greatest change per (subset, key), in row order."""
+        self.select_device(wire_t, cols, n, filter, out_rows, sel_idx_t, n_selected_t, _fn="drp_latest_device")
+
+    def latest_staged(self, filter=None, cap=None, out=None):
+        """drp_latest_staged over the batch last staged: relay_staged's arguments, results and
+        errors, for the latest Change per (subset, key). cap=None: the staged batch's length, which
+        is always enough (the winners are a subset of what relay_staged encodes)."""
+        return self.relay_staged(filter, cap, out, _fn="drp_latest_staged")
+
+    def set_latest_hash_mask(self, mask):
+        """Test hook: the row hash of latest_device / latest_staged is ANDed with mask before it
+        picks a slot (default all ones); results are identical for every mask."""
+        _chk("drp_set_latest_hash_mask", self.L.drp_set_latest_hash_mask(self.h, mask & 0xFFFFFFFFFFFFFFFF))
 
     # ---- fan-out: many filters over one batch --------------------------------------------
     def fanout_device(self, wire_t, cols, n, filters, out_rows, rows_cap, sel_idx_t, row_base_t, splice=None):

@@ -22,6 +22,9 @@
  *       -> no reference counterpart: that select for many filters in one pass (a hub's peers), and
  *          a splice table that keeps the blobs where Encoder.change / Encoder.blob put them between
  *          the Changes (encode.js:77-107).
+ *   drp_latest_device / drp_latest_staged
+ *       -> no reference counterpart: of the Changes that select keeps, the one with the greatest
+ *          `change` per (subset, key) (schema messages/schema.proto:1-8), a hub's fan-in.
  *   drp_stream_stats + drp_index_scan
  *       -> no reference counterpart (the reference is single-stream); they build the
  *          global frame index after the per-GPU stats tables are all-gathered.
@@ -423,6 +426,41 @@ int drp_fanout_device(drp_ctx *ctx, const uint8_t *bytes, uint64_t nbytes, const
 int drp_fanout_staged(drp_ctx *ctx, const drp_filter *filters, uint32_t nfilters, uint8_t *out, uint64_t cap,
                       uint64_t *out_off, uint64_t *n_selected, uint64_t *blob_row, uint64_t *blob_pos,
                       uint64_t blob_cap, uint64_t *n_blobs);
+
+/* ---- latest per key: one Change per (subset, key) (relay fan-in) ----------- */
+/* A replication feed is a log: the same (subset, key) is written again and again, and a hub that
+ * catches a peer up, or merges the feeds of several peers, wants every key's current Change only.
+ * No reference counterpart (the reference has no relay); the fields read are subset, key and change
+ * of messages/schema.proto:1-8.
+ *   Candidates: the rows drp_select_device selects with the same filter (a NULL filter or flags == 0:
+ * every well-formed Change) whose key range and, with DRP_F_SUBSET, subset range lie inside
+ * [0, nbytes); a row whose range leaves the wire is never read and is no candidate.
+ *   Identity: subset presence (DRP_F_SUBSET), the subset bytes and the key bytes, as whole byte
+ * strings: an absent and a present empty subset differ, "a" and "ab" differ, an empty key is a key.
+ *   Winner: of the candidates of one identity the one with the greatest `change` (unsigned 64-bit);
+ * on a tie the greatest row index (the later row of a stream, the later stream of flat multi-stream
+ * columns). With DRP_SEL_CHANGE_RANGE and change_max = T the result is the snapshot at version T. */
+
+/* drp_select_device with that reduction behind the predicate: the winners of rows [0, n) in
+ * increasing row order, written as drp_select_device writes its rows (out_rows' offsets absolute
+ * into `bytes`, flags masked to DRP_F_SUBSET | DRP_F_VALUE, sel_idx and n_selected as there). The
+ * result is a function of the input alone. Device pointers only; asynchronous on drp_stream(ctx).
+ * The argument rules and DRP_E_INVAL cases are drp_select_device's. The grouping table comes from
+ * the ctx's scratch (8 bytes per row and 24 bytes for each of the 2 n slots, rounded up to a power
+ * of two): DRP_E_NOMEM if it cannot be allocated. */
+int drp_latest_device(drp_ctx *ctx, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                      const drp_changes *cols, uint64_t n, const drp_filter *filter, const drp_change_src *out_rows,
+                      uint64_t *sel_idx, uint64_t *n_selected);
+/* drp_relay_staged with the latest-per-key step between select and encode: over the same rows of
+ * the batch last staged, with the same validity rules and DRP_E_INVAL cases, the same
+ * DRP_E_CAPACITY contract (*written = the size needed, nothing written to out) and the same bytes
+ * in every drp_set_blob_skip mode. Synchronous. *n_selected = the winners. */
+int drp_latest_staged(drp_ctx *ctx, const drp_filter *filter, uint8_t *out, uint64_t cap, uint64_t *written,
+                      uint64_t *n_selected);
+/* The row hash of the two calls above is ANDed with `mask` before it picks a slot of the grouping
+ * table (default: all ones; 0: every row starts at the same slot). Results are identical for
+ * every mask. Test hook. */
+int drp_set_latest_hash_mask(drp_ctx *ctx, uint64_t mask);
 
 /* ---- multi-GPU global index ---------------------------------------------- */
 /* stats[nranks*per_rank] (device): all-gathered per-stream tables in rank order.

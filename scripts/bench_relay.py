@@ -19,6 +19,17 @@ probe, and the host relay through drp_relay_staged against the host round trip i
               drp_relay_staged calls over the same staged batch, alternating, wall clock, with a
               check that the bytes are the same. Written to --fanout-out as its own JSON line.
 
+  latest      (--latest-out) the latest-per-key compaction. Device: --frames decoded C2-shaped rows
+              whose keys repeat, three key pools (frames / 16 keys, frames / 1024 keys, and frames / 16
+              keys with one hot key on 10 % of the rows); drp_latest_device against drp_select_device
+              with the same (NULL) filter, alternating, HIP events, the device leg's warm-up and
+              repeat counts; the winners checked against a numpy sort of (key, change, row). Host:
+              a --host-mib batch of the frames / 16 stream, staged once per pair, (a) drp_decode_fetch +
+              grouping in numpy (lexsort over key hash / change / row, the groups' bytes verified) +
+              drp_encode_batch against (b) drp_latest_staged, alternating, wall clock, the bytes
+              checked to be the same. Written to --latest-out as its own JSON line. With
+              --latest-only the relay and fan-out legs are left out (a run under a kernel trace).
+
 Prints one JSON line (and writes it to --out). Needs an MI355X: there is no CPU path.
 
   hipcc -O3 --offload-arch=gfx950 scripts/probe_bw.hip -o exp/probe_bw
@@ -56,10 +67,12 @@ def run_probe(path):
     return res
 
 
-def device_setup(ctx, drp_amd, torch, S, frames):
-    """frames C2 frames resident in HBM and decoded: (wire_t, cols, n)."""
+def device_setup(ctx, drp_amd, torch, S, frames, wire=None):
+    """frames C2 frames (or the given wire of as many frames) resident in HBM and decoded:
+    (wire_t, cols, n)."""
     dev = torch.device("cuda", 0)
-    wire = S.c2_stream(frames, seed=1)
+    if wire is None:
+        wire = S.c2_stream(frames, seed=1)
     wire_t = torch.from_numpy(wire).to(dev)
     n = frames
     cap = n + 64
@@ -337,6 +350,201 @@ def fanout_host_leg(ctx, drp_amd, S, mib, runs, K=16):
             "ranges_overlap": not (max(tf) < min(ts) or max(ts) < min(tf)), "same_bytes": same}
 
 
+# ---- latest per key ---------------------------------------------------------------------------
+
+def keyed_c2_stream(key_ids, seed=1):
+    """_streams.c2_stream's 86-byte frames with row i's key the 10 digits of key_ids[i]: change =
+    i % 100 + 1 (so a key's rows tie now and then), from = i % 128, to = (i + 1) % 128, 64 random
+    value bytes."""
+    n = len(key_ids)
+    i = np.arange(n, dtype=np.int64)
+    a = np.zeros((n, 86), np.uint8)
+    a[:, 0], a[:, 1], a[:, 2], a[:, 3] = 85, 1, 0x12, 10
+    for k in range(10):
+        a[:, 4 + k] = 48 + (key_ids // 10 ** (9 - k)) % 10
+    a[:, 14], a[:, 15] = 0x18, (i % 100) + 1
+    a[:, 16], a[:, 17] = 0x20, i % 128
+    a[:, 18], a[:, 19] = 0x28, (i + 1) % 128
+    a[:, 20], a[:, 21] = 0x32, 64
+    a[:, 22:] = np.random.default_rng(seed).integers(0, 256, size=(n, 64), dtype=np.uint8)
+    return a.reshape(-1)
+
+
+def latest_pools(n, seed=7):
+    """The three key pools of the device leg: name -> key id of every row."""
+    rng = np.random.default_rng(seed)
+    p16 = rng.integers(0, max(1, n // 16), n, dtype=np.int64)
+    hot = p16.copy()
+    hot[rng.random(n) < 0.10] = 0
+    return {"keys_n_over_16": p16, "keys_n_over_1024": rng.integers(0, max(1, n // 1024), n, dtype=np.int64),
+            "hot_key_10pct": hot}
+
+
+def latest_winners(key_ids):
+    """Per key the row with the greatest (change, row), change = row % 100 + 1: rows, increasing."""
+    n = len(key_ids)
+    assert n < 1 << 25 and int(key_ids.max()) < 1 << 31
+    i = np.arange(n, dtype=np.int64)
+    packed = np.sort((key_ids << 32) | ((i % 100 + 1) << 25) | i)
+    last = np.flatnonzero(np.append(packed[1:] >> 32 != packed[:-1] >> 32, True))
+    return np.sort(packed[last] & ((1 << 25) - 1))
+
+
+def latest_device_leg(ctx, drp_amd, torch, frames, iters):
+    dev = torch.device("cuda", 0)
+    L = ctx.L
+    tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    res = {"frames": frames, "iters": iters}
+    for name, key_ids in latest_pools(frames).items():
+        wire = keyed_c2_stream(key_ids)
+        want = latest_winners(key_ids)
+        wire_t, cols, n = device_setup(ctx, drp_amd, torch, None, frames, wire=wire)
+        del wire
+        fr = drp_amd.Frames(tp(cols["payload_off"]), tp(cols["payload_len"]), tp(cols["type"]))
+        co = drp_amd.Changes(*[tp(cols[k]) for k in drp_amd.COLS32], tp(cols["change"]), tp(cols["from"]),
+                             tp(cols["to"]), tp(cols["flags"]), None)
+        rows = _row_tensors(torch, dev, n)
+        src = drp_amd.ChangeSrc(*[tp(rows[k]) for k in SRC_KEYS])
+        idx_t = torch.zeros(n, dtype=torch.int64, device=dev)
+        nsel_t = torch.zeros(1, dtype=torch.int64, device=dev)
+        ext = ctx._ext(dev)
+
+        def timed(fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record(ext)
+            rc = fn(ctx.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n, None, C.byref(src), tp(idx_t),
+                    tp(nsel_t))
+            e1.record(ext)
+            e1.synchronize()
+            assert rc == 0, rc
+            return e0.elapsed_time(e1)
+
+        tl, ts = [], []
+        for it in range(iters + 3):  # (three warm-ups, as the device leg; alternating, the latest call last)
+            b, a = timed(L.drp_select_device), timed(L.drp_latest_device)
+            if it >= 3:
+                tl.append(a)
+                ts.append(b)
+        nsel = int(nsel_t.cpu()[0])
+        assert nsel == len(want), (name, nsel, len(want))
+        assert np.array_equal(idx_t[:nsel].cpu().numpy(), want), name
+        assert np.array_equal(rows["change"][:nsel].cpu().numpy(), want % 100 + 1), name
+        res[name] = {"keys": int(len(np.unique(key_ids))), "winners": nsel, "latest_ms": _stat(tl), "select_ms": _stat(ts),
+                     "latest_over_select": statistics.median(tl) / statistics.median(ts),
+                     "scratch_bytes": int(n * 8 + 24 * (1 << int(2 * n - 1).bit_length()))}
+        print("latest", name, res[name]["latest_ms"], file=sys.stderr, flush=True)
+        del wire_t, cols, rows, idx_t
+        torch.cuda.empty_cache()
+    return res
+
+
+def _field_hash(wire, off, ln, mult):
+    """A u64 hash of wire[off, off + ln) per row (the length and a multiplier per byte position)."""
+    h = ln.astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+    for width in np.unique(ln):
+        if width:
+            r = np.flatnonzero(ln == width)
+            m = wire[off[r][:, None] + np.arange(width, dtype=np.uint64)]
+            h[r] += (m.astype(np.uint64) * mult[:width]).sum(axis=1, dtype=np.uint64)
+    return h
+
+
+def _fields_equal(wire, off_a, off_b, ln):
+    """wire[off_a, off_a + ln) == wire[off_b, off_b + ln) for every row."""
+    for width in np.unique(ln):
+        if width:
+            r = np.flatnonzero(ln == width)
+            k = np.arange(width, dtype=np.uint64)
+            if not np.array_equal(wire[off_a[r][:, None] + k], wire[off_b[r][:, None] + k]):
+                return False
+    return True
+
+
+def host_latest_rows(wire, host, n):
+    """The host grouping path (a) does: the rows to keep, increasing. Per well-formed Change a hash of
+    (subset presence, subset bytes, key bytes), a lexsort over (hash, change, row), every group's
+    bytes verified against its first row, the last row of every group."""
+    cand = np.flatnonzero(((host["type"][:n] & 0x3F) == 1) & ((host["flags"][:n] & 4) == 0))
+    po = host["payload_off"][cand]
+    has = (host["flags"][cand] & 1).astype(np.uint64)
+    koff, klen = po + host["key_off"][cand], host["key_len"][cand]
+    soff, slen = po + host["subset_off"][cand], host["subset_len"][cand] * has.astype(np.uint32)
+    mult = np.random.default_rng(5).integers(1, 1 << 63, size=int(max(klen.max(), slen.max(), 1)), dtype=np.uint64) | np.uint64(1)
+    h = _field_hash(wire, koff, klen, mult) * np.uint64(0xC2B2AE3D27D4EB4F) + _field_hash(wire, soff, slen, mult) + has
+    order = np.lexsort((cand, host["change"][cand], h))
+    hs = h[order]
+    first = np.append(True, hs[1:] != hs[:-1])
+    leader = order[np.maximum.accumulate(np.where(first, np.arange(len(order)), 0))]
+    assert np.array_equal(has[order], has[leader]) and np.array_equal(klen[order], klen[leader]) and \
+        np.array_equal(slen[order], slen[leader]) and _fields_equal(wire, koff[order], koff[leader], klen[order]) and \
+        _fields_equal(wire, soff[order], soff[leader], slen[order]), "hash collision"
+    return np.sort(cand[order[np.append(first[1:], True)]])
+
+
+def latest_host_leg(ctx, drp_amd, mib, runs):
+    L = ctx.L
+    nbytes = mib << 20
+    frames = nbytes // 86 + 1
+    wire = keyed_c2_stream(latest_pools(frames)["keys_n_over_16"])[:nbytes].copy()
+    host = drp_amd.alloc_host_outputs(nbytes // 86 + 8)
+    fr, co = drp_amd._structs(host, drp_amd._p)
+    out_a, out_b = np.zeros(nbytes, np.uint8), np.zeros(nbytes, np.uint8)
+    U64, U32 = C.c_uint64, C.c_uint32
+
+    def stage():
+        carry = drp_amd.Carry(0, 0, 0, 0, 0)
+        nf, ef, ec, ed = U64(), U64(), U32(), U32()
+        rc = L.drp_decode_stage(ctx.h, drp_amd._p(wire), nbytes, C.byref(carry), C.byref(nf), C.byref(ef),
+                                C.byref(ec), C.byref(ed))
+        assert rc == 0 and ec.value == 0, (rc, ec.value)
+        return int(nf.value)
+
+    def path_a(n):
+        assert L.drp_decode_fetch(ctx.h, C.byref(fr), C.byref(co), 0, n) == 0
+        keep = host_latest_rows(wire, host, n)
+        po = host["payload_off"][keep]
+        cols = {}
+        for k in ["key", "subset", "value"]:
+            cols[k + "_off"] = po + host[k + "_off"][keep]
+            cols[k + "_len"] = host[k + "_len"][keep]
+        for k in ["change", "from", "to"]:
+            cols[k] = host[k][keep]
+        cols["flags"] = host["flags"][keep] & 3
+        src = drp_amd.ChangeSrc(*[drp_amd._p(np.ascontiguousarray(cols[k])) for k in SRC_KEYS])
+        written = U64()
+        rc = L.drp_encode_batch(ctx.h, C.byref(src), drp_amd._p(wire), nbytes, len(keep), drp_amd._p(out_a), nbytes,
+                                C.byref(written))
+        assert rc == 0, rc
+        return int(written.value), len(keep)
+
+    def path_b():
+        written, nsel = U64(), U64()
+        rc = L.drp_latest_staged(ctx.h, None, drp_amd._p(out_b), nbytes, C.byref(written), C.byref(nsel))
+        assert rc == 0, rc
+        return int(written.value), int(nsel.value)
+
+    ta, tb, same = [], [], False
+    for it in range(runs + 2):  # (two warm-ups; staged once per pair; (b) first: (a)'s host encode ends the staged batch)
+        t0 = time.perf_counter()
+        n = stage()
+        t1 = time.perf_counter()
+        rb = path_b()
+        t2 = time.perf_counter()
+        ra = path_a(n)
+        t3 = time.perf_counter()
+        if it == 1:
+            same = ra == rb and out_a[:ra[0]].tobytes() == out_b[:rb[0]].tobytes()
+            assert same, (ra, rb)
+        if it >= 2:  # each path with the stage it needs
+            tb.append((t2 - t0) * 1e3)
+            ta.append((t1 - t0 + t3 - t2) * 1e3)
+    return {"batch_bytes": nbytes, "rows": n, "winners": ra[1], "out_bytes": ra[0], "runs": runs,
+            "a_stage_fetch_group_encode_ms": _stat(ta), "b_stage_latest_ms": _stat(tb),
+            "a_over_b": statistics.median(ta) / statistics.median(tb), "ranges_overlap": not max(tb) < min(ta),
+            "same_bytes": same}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20_000_000)
@@ -346,7 +554,11 @@ def main():
     ap.add_argument("--probe", default=None, help="a built scripts/probe_bw.hip")
     ap.add_argument("--out", default=None)
     ap.add_argument("--fanout-out", default=None, help="run the fan-out legs too and write their JSON line here")
+    ap.add_argument("--latest-out", default=None, help="run the latest-per-key legs too and write their JSON line here")
+    ap.add_argument("--latest-only", action="store_true", help="with --latest-out: leave the other legs out")
     a = ap.parse_args()
+    if a.latest_only and not a.latest_out:
+        ap.error("--latest-only needs --latest-out")
     res = {"bench": "relay"}
     if a.probe:
         res["probe_bw"] = run_probe(a.probe)
@@ -356,6 +568,18 @@ def main():
     torch.cuda.init()
     import _streams as S
     import drp_amd
+    if a.latest_out:
+        with drp_amd.Ctx(0) as ctx:
+            ctx.set_blob_skip(drp_amd.BLOB_SKIP_OFF)
+            lat = {"bench": "relay_latest", "device": latest_device_leg(ctx, drp_amd, torch, a.frames, a.iters),
+                   "host": latest_host_leg(ctx, drp_amd, a.host_mib, a.runs)}
+            if a.probe:
+                lat["probe_bw"] = res["probe_bw"]
+        with open(a.latest_out, "w") as f:
+            f.write(json.dumps(lat) + "\n")
+        print(json.dumps(lat))
+        if a.latest_only:
+            return
     with drp_amd.Ctx(0) as ctx:
         ctx.set_blob_skip(drp_amd.BLOB_SKIP_OFF)
         decoded = device_setup(ctx, drp_amd, torch, S, a.frames)
