@@ -829,6 +829,9 @@ __global__ __launch_bounds__(NT, DRP_K1G_WAVES) void spec_claims(DecodeParams P)
 #define DRP_FCAP 512
 #endif
 constexpr uint32_t FCAP = DRP_FCAP;
+#ifndef DRP_HALO_WAVE
+#define DRP_HALO_WAVE 0  // the wave whose lanes build the halo's live masks (A/B: 1, the second wave)
+#endif
 constexpr uint16_t NX_TAILB = 0xFFFB, NX_TAILC = 0xFFFC;  // the node's frame runs past the stream end
 // Chain exits (32-bit): a node index | its offset << 16 (offset < 0x4000: the tile and its halo), or
 constexpr uint32_t RX_NONE = 0xFFFFFFFFu;  // no chain
@@ -851,6 +854,17 @@ __device__ __forceinline__ uint32_t masks16(const uint4 v) {  // m | s << 16
   const uint32_t m = gather_msb(v.x & H, v.y & H, v.z & H, v.w & H);
   const uint32_t s = gather_msb(le2_bytes(v.x), le2_bytes(v.y), le2_bytes(v.z), le2_bytes(v.w));
   return m | (s << 16);
+}
+// The live positions of one 16-byte block from its masks16 word w and the next block's wn: bit p is
+// set when a varint of 1..3 bytes starts at byte p and an id <= 2 follows it. With m / s the
+// 32 positions of both blocks: X = ~m & (s >> 1) (a terminator, then an id), and
+// live = X | (m & (X >> 1 | ((m >> 1) & (X >> 2)))); positions 0..15 need m bits 0..17 and
+// s bits 1..18, so the next block's low bits are all the lookahead (tests/test_claims_halo_masks.py
+// pins this against the 64-position form the tile's threads use).
+__host__ __device__ __forceinline__ uint32_t halo_live16(uint32_t w, uint32_t wn) {
+  const uint32_t m = (w & 0xFFFFu) | (wn << 16), s = (w >> 16) | (wn & 0xFFFF0000u);
+  const uint32_t X = ~m & (s >> 1);
+  return (X | (m & ((X >> 1) | ((m >> 1) & (X >> 2))))) & 0xFFFFu;
 }
 
 
@@ -978,7 +992,7 @@ __device__ __forceinline__ uint32_t fwalk(const uint32_t *lnd, uint32_t x, uint3
 // round per frame of the tile: with cap, the rounds stop there and flink returns true (E, R, n
 // then unsettled; the caller takes claims_fast's pointer-jumping form instead).
 __device__ __forceinline__ bool flink(const uint32_t *lnd, uint32_t s1r, uint32_t g, uint32_t &E, uint32_t &R,
-                                      uint32_t &n, bool &rs, uint32_t *wl, uint32_t *fl, uint32_t *overflow,
+                                      uint32_t &n, bool &rs, uint32_t *wl, uint32_t *fl,
                                       unsigned long long *stats = nullptr, uint32_t cap = ~0u) {
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
   const uint64_t below = (1ull << lane) - 1ull;
@@ -1022,7 +1036,7 @@ __device__ __forceinline__ bool flink(const uint32_t *lnd, uint32_t s1r, uint32_
       break;
     }
     if (round > NT + 2) {  // cannot happen: entries settle thread by thread
-      if (tid == 0) atomicOr(overflow, F_WAIT);
+      if (tid == 0) atomicOr(DRP_KARG(overflow), F_WAIT);
       break;
     }
     if (ch) {
@@ -1173,9 +1187,9 @@ __device__ __forceinline__ uint32_t fast_claims_jump(const DecodeParams &P, uint
   eb_o = 0xFFu;
   en_o = 0;
   ecn_o = 0;
-  P.ent[ix] = 0xFF;
-  P.ent_n[ix] = 0;
-  P.ent_c[ix] = 0;
+  DRP_KARG(ent)[ix] = 0xFF;
+  DRP_KARG(ent_n)[ix] = 0;
+  DRP_KARG(ent_c)[ix] = 0;
   cl_o = 0;
   if (tid == NTT - 1) {
     uint64_t cl = C_ID;
@@ -1187,7 +1201,7 @@ __device__ __forceinline__ uint32_t fast_claims_jump(const DecodeParams &P, uint
       else if (code & JT_TERM) cl = MARK_TERM | (A + (code & ~JT_TERM));
       else cl = A + code;
     }
-    P.claim[t] = cl;
+    DRP_KARG(claim)[t] = cl;
     cl_o = cl;
   }
   return FC_OK;
@@ -1368,7 +1382,7 @@ __device__ __forceinline__ void fast_records(const DecodeParams &P, uint64_t t, 
     uint32_t w[CR_WORDS];
     bad = !crec_frame(reinterpret_cast<const uint32_t *>(S.img), f & 0x3FFFu, min(se_rel, IMG), (f >> 14) & 3u,
                       (f >> 16) & 1u, w);
-    uint32_t *rr = P.rec + t * CR_TILE_WORDS + tid;
+    uint32_t *rr = DRP_KARG(rec) + t * CR_TILE_WORDS + tid;
     if (DRP_CREC_STAGE == 1) {  // (A/B: keep the decode, store nothing)
       if ((w[0] ^ w[2] ^ w[3] ^ w[4] ^ w[5]) == 0x7FFFFFFFu && !bad) rr[0] = w[1];
       bad = true;
@@ -1385,7 +1399,7 @@ __device__ __forceinline__ void fast_records(const DecodeParams &P, uint64_t t, 
   const uint64_t bm = __ballot(bad);
   if (lane == 0) S.xw[6 + wid] = bm != 0;
   bsync();
-  if (tid == 0) P.tile_rec[t] = (NT == 2 * WAVE ? S.xw[6] | S.xw[7] : S.xw[6]) ? REC_NONE : 0u;
+  if (tid == 0) DRP_KARG(tile_rec)[t] = (NT == 2 * WAVE ? S.xw[6] | S.xw[7] : S.xw[6]) ? REC_NONE : 0u;
 }
 
 // bits of the 64 positions from base (tile-relative) that lie in [lo, hi)
@@ -1455,34 +1469,29 @@ __device__ __forceinline__ uint32_t fast_claims(const DecodeParams &P, const Til
   // Halo nodes (DRP_HALO_NODES): the halo's live positions join the list as HV more "threads", so
   // the survival check of the tile's last frames does not stop at the tile end (their chains
   // would otherwise leave the list within KSTRONG frames and stay undecided, and the link would
-  // reach their threads one round at a time). Lanes 0..HV-1 of wave 0 build their masks.
-  uint64_t hlive = 0;
-  if (tid < HV) {
-    uint32_t hk[5];
-#pragma unroll
-    for (int k = 0; k < 5; k++) hk[k] = hmx[tid * 4 + k];
-    const uint64_t hM0 = (uint64_t)(hk[0] & 0xFFFFu) | ((uint64_t)(hk[1] & 0xFFFFu) << 16) |
-                         ((uint64_t)(hk[2] & 0xFFFFu) << 32) | ((uint64_t)(hk[3] & 0xFFFFu) << 48);
-    const uint64_t hS0 = (uint64_t)(hk[0] >> 16) | ((uint64_t)(hk[1] >> 16) << 16) | ((uint64_t)(hk[2] >> 16) << 32) |
-                         ((uint64_t)(hk[3] >> 16) << 48);
-    const uint64_t hM1 = hk[4] & 0xFFFFu, hS1 = hk[4] >> 16;
-    const uint64_t hX0 = ~hM0 & ((hS0 >> 1) | (hS1 << 63)), hX1 = ~hM1 & (hS1 >> 1);
-    const uint64_t hXs1 = (hX0 >> 1) | (hX1 << 63), hXs2 = (hX0 >> 2) | (hX1 << 62), hMs1 = (hM0 >> 1) | (hM1 << 63);
-    hlive = hX0 | (hM0 & (hXs1 | (hMs1 & hXs2)));
+  // reach their threads one round at a time). HALO / 16 lanes of one wave take a 16-byte block
+  // each (a wave64 instruction costs the same with 8 lanes active as with 32, and the 32-bit
+  // algebra half of the 64-bit one; the list loop below runs 2 trips on C2 instead of ~5); the
+  // masks land in lmw[NT + h] as four 16-bit pieces: the 64 positions of halo "thread" h.
+  constexpr uint32_t HB = HALO / 16, HW0 = (NT == 2 * WAVE && DRP_HALO_WAVE) ? WAVE : 0u;
+  const uint32_t hl = tid - HW0;  // this thread's halo block (>= HB: none)
+  uint32_t hlive = 0;
+  if (hl < HB - 1u) {  // (the image's last 16 bytes: no lookahead, never listed)
+    hlive = halo_live16(hmx[hl], hmx[hl + 1]);
     if (EDGE)
-      hlive = (hlive & range_bits(TILE + tid * SEGB, lo_rel, hi_rel)) | range_bits(TILE + tid * SEGB, fo_rel, hi_rel);
-    if (tid == HV - 1) hlive &= (1ull << (SEGB - 16)) - 1ull;  // (the image's last 16 bytes: no lookahead)
+      hlive = (hlive & (uint32_t)range_bits(TILE + hl * 16u, lo_rel, hi_rel) & 0xFFFFu) |
+              ((uint32_t)range_bits(TILE + hl * 16u, fo_rel, hi_rel) & 0xFFFFu);
   }
   // ---- the tile's (and halo's) live positions as an LDS list -----------------------------------
   const uint32_t cnt = (uint32_t)__builtin_popcountll(live);
   const uint32_t cpre = wave_scan_dpp(cnt);
-  const uint32_t hcnt = (uint32_t)__builtin_popcountll(hlive);
+  const uint32_t hcnt = (uint32_t)__builtin_popcount(hlive);
   uint32_t hpre = 0;
-  if (wid == 0) hpre = wave_scan_dpp(hcnt);  // (the halo's threads are wave 0's: wave-uniform)
+  if (wid == HW0 / WAVE) hpre = wave_scan_dpp(hcnt);  // (the halo's lanes are one wave's: wave-uniform)
   if (lane == 63) xw[wid] = cpre;
-  if (tid == 63) xw[2] = hpre;
+  if (tid == HW0 + 63u) xw[2] = hpre;
   lmw[tid] = live;
-  if (tid < HV) lmw[NT + tid] = hlive;
+  if (hl < HB) reinterpret_cast<uint16_t *>(lmw + NT)[hl] = (uint16_t)hlive;
   bsync();  // (also: mx reads done)
   const uint32_t off = cpre - cnt + (wid ? xw[0] : 0u);
   const uint32_t ttotal = NT == 2 * WAVE ? xw[0] + xw[1] : xw[0];  // the tile's nodes
@@ -1500,12 +1509,12 @@ __device__ __forceinline__ uint32_t fast_claims(const DecodeParams &P, const Til
       bits &= bits - 1;
     }
   }
-  if (tid < HV) {
-    uint64_t bits = hlive;
+  if (hl < HB) {
+    uint32_t bits = hlive;
     uint32_t i = ttotal + hpre - hcnt;
-    loff[NT + tid] = (uint16_t)i;
+    if (!(hl & 3u)) loff[NT + hl / 4u] = (uint16_t)i;  // (the first block of a 64-byte halo "thread")
     while (bits) {
-      lpos[i++] = (uint16_t)(TILE + tid * SEGB + (uint32_t)__builtin_ctzll(bits));
+      lpos[i++] = (uint16_t)(TILE + hl * 16u + (uint32_t)__builtin_ctz(bits));
       bits &= bits - 1;
     }
   }
@@ -1700,20 +1709,21 @@ __device__ __forceinline__ uint32_t fast_claims(const DecodeParams &P, const Til
   }
   uint32_t E = g;
   bool rs = false;
-  if (flink(lnd, s1r, g, E, R, n, rs, wl, fl, P.overflow, P.stats, DRP_FL_CAP)) {
+  if (flink(lnd, s1r, g, E, R, n, rs, wl, fl, P.stats, DRP_FL_CAP)) {
     // the rounds did not settle: past P.jump_min such tiles in this launch (an input with a second
     // framing throughout: every tile), pointer jumping; before it (clean streams have a few, whose
     // predictions rely on the restarts and rule 3 below), the rounds go on
     // (an atomic only below the threshold: one word takes ~88 atomics per us, and on a cascade
     // every tile gets here)
     if (tid == 0) {
-      uint32_t c = __hip_atomic_load(&P.counter[12], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (c < P.jump_min) c = atomicAdd(&P.counter[12], 1u);
+      uint32_t *c12 = DRP_KARG(counter) + 12;
+      uint32_t c = __hip_atomic_load(c12, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (c < DRP_KARG(jump_min)) c = atomicAdd(c12, 1u);
       xw[6] = c;
     }
     bsync();
-    if (xw[6] >= P.jump_min) return fast_claims_jump<NT>(P, t, G.A, S, g, ttotal, total, eb_o, en_o, ecn_o, cl_o);
-    flink(lnd, s1r, g, E, R, n, rs, wl, fl, P.overflow, P.stats);
+    if (xw[6] >= DRP_KARG(jump_min)) return fast_claims_jump<NT>(P, t, G.A, S, g, ttotal, total, eb_o, en_o, ecn_o, cl_o);
+    flink(lnd, s1r, g, E, R, n, rs, wl, fl, P.stats);
   }
   // restarts from deferred candidates, decided in HBM (big frames), as in spec_claims
   const Img m{buf, P.bytes, G.A, G.se, false};
@@ -1731,7 +1741,7 @@ __device__ __forceinline__ uint32_t fast_claims(const DecodeParams &P, const Til
         uint64_t r;
         uint32_t k;
         bool f;
-        if (strong<false>(m, G.A + lb + o, G.A + s1r, r, k, f, P.kstrong_hbm) == S_OK) {
+        if (strong<false>(m, G.A + lb + o, G.A + s1r, r, k, f, DRP_KARG(kstrong_hbm)) == S_OK) {
           g = (off + (uint32_t)__builtin_popcountll(live & ((1ull << o) - 1ull))) | ((lb + o) << 16);
           E = g;
           R = fwalk(lnd, g, s1r, n);
@@ -1739,7 +1749,7 @@ __device__ __forceinline__ uint32_t fast_claims(const DecodeParams &P, const Til
         }
       }
     }
-    flink(lnd, s1r, g, E, R, n, rs, wl, fl, P.overflow);
+    flink(lnd, s1r, g, E, R, n, rs, wl, fl);
     block_any_last(E == RX_NONE && defer && !any_above(S0m, S1m, tid), rx_node(E) && rx_off(E) < s1r, need, js,
                    xf);
   }
@@ -1756,7 +1766,7 @@ __device__ __forceinline__ uint32_t fast_claims(const DecodeParams &P, const Til
       E = RX_NONE;
       R = RX_NONE;
       n = 0;
-      flink(lnd, s1r, mine ? g : RX_NONE, E, R, n, rs, wl, fl, P.overflow);
+      flink(lnd, s1r, mine ? g : RX_NONE, E, R, n, rs, wl, fl);
       const uint32_t nb = block_sum_u32(mine ? (n & 0xFFFFu) : 0u, xf);
       if (nb < 2 || !mine) {
         E = Ea;
@@ -1773,9 +1783,9 @@ __device__ __forceinline__ uint32_t fast_claims(const DecodeParams &P, const Til
     eb_o = carrier ? (((rx_off(E) - lb) & 63u) | (rs ? 0x40u : 0u)) : 0xFFu;
     en_o = carrier ? (n & 0xFFFFu) : 0u;
     ecn_o = carrier ? (n >> 16) : 0u;
-    P.ent[ix] = (uint8_t)eb_o;
-    P.ent_n[ix] = (uint8_t)en_o;
-    P.ent_c[ix] = (uint8_t)ecn_o;
+    DRP_KARG(ent)[ix] = (uint8_t)eb_o;
+    DRP_KARG(ent_n)[ix] = (uint8_t)en_o;
+    DRP_KARG(ent_c)[ix] = (uint8_t)ecn_o;
   }
   cl_o = 0;
   if (tid == NT - 1) {
@@ -1790,7 +1800,7 @@ __device__ __forceinline__ uint32_t fast_claims(const DecodeParams &P, const Til
     } else if (rx_node(R)) {
       cl = G.A + rx_off(R);
     }
-    P.claim[t] = cl;
+    DRP_KARG(claim)[t] = cl;
     cl_o = cl;
   }
   if (!EDGE && REC) fast_records(P, t, S, E, en_o, s1r, se_rel, v, hv);

@@ -96,6 +96,20 @@ __device__ __forceinline__ T ldc(const T *p) {
   return *reinterpret_cast<const __attribute__((address_space(4))) T *>(reinterpret_cast<uintptr_t>(p));
 }
 
+// A DecodeParams field read from the kernel's argument segment at the place of its use (one scalar
+// load; for kernels whose first argument is their DecodeParams, by value). The empty asm keeps the
+// compiler from loading the field with the early ones: claims_fast's fields of the late and rare
+// paths (claim, stats, overflow, jump_min, rec, ...) otherwise sit in SGPRs from the tile's load on
+// and are spilled to VGPR lanes and back with v_writelane / v_readlane, which are VALU instructions
+// on the path of every tile.
+template <class T>
+__device__ __forceinline__ T karg_at(uint32_t off) {
+  uintptr_t k = reinterpret_cast<uintptr_t>(__builtin_amdgcn_kernarg_segment_ptr());
+  asm volatile("" : "+s"(k));
+  return *reinterpret_cast<const __attribute__((address_space(4))) T *>(k + off);
+}
+#define DRP_KARG(field) karg_at<decltype(DecodeParams::field)>((uint32_t)offsetof(DecodeParams, field))
+
 struct TileGeo {
   uint64_t s, tf, so, se, A, e0;
 };
