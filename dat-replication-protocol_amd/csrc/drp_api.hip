@@ -1,4 +1,5 @@
-// drp_api.hip — the extern "C" boundary of libdrp (include/drp.h).
+// drp_api.hip — the extern "C" boundary of libdrp (include/drp.h): the context's life cycle, decode,
+// fetch and encode. The relay entry points (select, latest per key, fan-out) are in drp_relay.hip.
 //
 // Owns one HIP stream + scratch per device context and launches the decode / encode
 // kernels. A decode is one pass: the kernel resolves every tile's entry exactly
@@ -16,10 +17,16 @@
 #include <vector>
 
 #include "../../include/drp.h"
+#include "drp_ctx.h"
 #include "drp_kernels.h"
 
+using drp::al;
 using drp::DecodeParams;
+using drp::DevBuf;
 using drp::EncodeParams;
+using drp::is_device_ptr;
+using drp::is_pinned_host;
+using drp::PinBuf;
 
 namespace {
 
@@ -80,59 +87,6 @@ hipError_t sync_watch(hipStream_t st, const char *where) {
   return e;
 }
 
-struct DevBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  bool ensure(size_t n) {
-    if (n <= cap) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = n + n / 4 + 4096;
-    if (hipMalloc(&p, want) != hipSuccess) {
-      p = nullptr;
-      (void)hipGetLastError();  // (the failure is reported by the caller, not by a later launch)
-      return false;
-    }
-    cap = want;
-    return true;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  template <class T>
-  T *at(size_t off) const {
-    return reinterpret_cast<T *>(static_cast<char *>(p) + off);
-  }
-};
-
-// Page-locked host memory that only grows (the gather buffer of chunked host batches).
-struct PinBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  bool ensure(size_t n) {
-    if (n <= cap) return true;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-    size_t want = n + n / 4 + 4096;
-    if (hipHostMalloc(&p, want, hipHostMallocDefault) != hipSuccess) {
-      p = nullptr;
-      (void)hipGetLastError();
-      return false;
-    }
-    cap = want;
-    return true;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
 // A host batch: one buffer, or the caller's chunks laid end to end (drp_decode_stage_v).
 struct HostSrc {
   const uint8_t *flat = nullptr;
@@ -141,28 +95,6 @@ struct HostSrc {
   uint64_t n = 0;
 };
 
-bool is_device_ptr(const void *p) {
-  if (!p) return false;
-  hipPointerAttribute_t a;
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
-}
-
-// page-locked host memory (the DMA engine reads it directly, without a staging copy)
-bool is_pinned_host(const void *p) {
-  hipPointerAttribute_t a;
-  if (!p || hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return a.type == hipMemoryTypeHost;
-}
-
-size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
-
 double now_ms() {
   timespec ts;
   clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -170,101 +102,6 @@ double now_ms() {
 }
 
 }  // namespace
-
-struct drp_ctx {
-  int device = 0;
-  hipStream_t st = nullptr;
-  hipEvent_t ev[4] = {};
-  hipEvent_t hev[2] = {};  // a staged piece's H2D
-  // pipelined staging (stage_pieces): the copy stream and one event per chunk (created on first use)
-  hipStream_t cst = nullptr;
-  hipEvent_t pev[32] = {};
-  // their early fetches: a fetch stream, the event behind a piece's last row writes, and a pinned
-  // bounce buffer the rows land in before a worker thread copies them into the caller's columns
-  hipStream_t fst = nullptr;
-  hipEvent_t fev = nullptr;
-  PinBuf fbounce;
-  uint64_t pipe_chunk = 128ull << 20;  // DRP_PIPE_CHUNK (MiB; 0: no pipelining)
-  uint32_t B = 128;
-  int strict = 0;
-  int exact = 0;  // 1: always the exact kernel (decode_tiles), never the speculative one
-  int key_post = 0;  // DRP_KEY_POST_*: key hashes and/or key flags on every decode
-  // claims_fast's structural check of long frames: on after a decode whose frames average
-  // >= 512 bytes (or none yet); DRP_CHANGE_CHECKS=0/1 forces it (A/B, tests)
-  int change_checks = 1, change_checks_env = -1;
-  int cus = 256;
-  uint32_t waves_per_cu = 16;
-  // test / measurement knobs, read once by drp_open (never on a decode): DRP_KSTRONG_HBM weakens
-  // predictions, DRP_DIRTY_CAP caps the repair dirty lists, DRP_STATS / DRP_TRACE_FILE collect
-  // kernel counters and per-tile traces into dstats (allocated here when asked for)
-  uint32_t kstrong_hbm = 0;
-  uint32_t cascade_min = 4096;  // DRP_CASCADE_MIN (tests: small cascades)
-  int64_t jump_min = -1;        // DRP_JUMP_MIN (-1: max(64, tiles / 512))
-  // claims kernel: the region walkers (drp_walk.hip) for batches of at least walk_min tiles,
-  // claims_fast below; DRP_CLAIMS=walk / fast forces one (A/B, tests)
-  uint64_t walk_min = 32768;
-  int claims_mode = 0;  // 0 auto, 2 fast, 3 hop
-  int crec = 1;         // claims_fast's per-frame records and the record emission (DRP_CREC=0: off)
-  DevBuf recbuf;
-  uint64_t dirty_cap = ~0ull;
-  bool stats = false;
-  const char *trace_file = nullptr;
-  unsigned long long *dstats = nullptr;
-  uint32_t *ctile = nullptr;  // segmented repair: per-tile candidate positions (grown on demand)
-  uint64_t ctile_cap = 0;
-  DevBuf scratch, in_stage, out_stage, aux;
-  PinBuf gather;  // chunked host batches: the staged ranges, gathered (drp_decode_stage_v)
-  DevBuf dec_cols;  // device columns of the staged host-batch decode (drp_decode_stage)
-  DevBuf fetch_tmp; // drp_decode_fetch_block: the caller's block layout, packed on the device
-  DevBuf keybuf;    // drp_decode_fetch_keys: per-row key lengths and positions
-  DevBuf keytext;   // drp_decode_fetch_keys: the key text
-  double frames_per_byte = 0;  // density of the last staged batch (sizes the next one's columns)
-  int blob_skip = DRP_BLOB_SKIP_AUTO;
-  uint64_t latest_hash_mask = ~0ull;  // drp_set_latest_hash_mask (test hook)
-  bool blob_heavy = false;     // the last host batch was mostly blob payload (AUTO: stage in pieces)
-  uint64_t blob_run = 0;       // bytes from a piece's start to its blob's payload, last seen
-  uint64_t piece_span = 0;     // batch bytes one blob-skipping piece covered on average, last seen
-  drp_timing timing = {};
-  // drp_decode_batch's host columns while it stages (pipelined pieces fetch their rows into them
-  // during the copy; dfetched: rows already there)
-  const drp_frames *dfr = nullptr;
-  const drp_changes *dco = nullptr;
-  uint64_t dcap = 0, dfetched = 0;
-  std::vector<uint64_t> host_tmp;
-  // fan-out: the filter table on its way to the device (page-locked; fan_ev: the copy of the last
-  // call has left it), and drp_fanout_staged's selected rows and splice ranks
-  PinBuf fan_tab;
-  hipEvent_t fan_ev = nullptr;
-  DevBuf fan_rows;
-  // the staged host-batch decode: row 0 is a host-built blob continuation when nf0 == 1; GPU
-  // rows follow, each piece's payload_off relative to the batch offset where that piece was
-  // staged (pieces: {first GPU row, batch offset}; one piece unless blobs were skipped)
-  struct Staged {
-    uint64_t rows = 0, nf0 = 0, cap = 0;
-    std::vector<std::pair<uint64_t, uint64_t>> pieces;
-    const uint8_t *dev = nullptr;  // the last piece's bytes on the device (a one-piece batch: all of it)
-    // drp_relay_staged: the batch's bytes from batch offset `base` on as they lie on the device
-    // (every piece at its own batch offset, the skipped blob payloads as holes), the delivered GPU
-    // rows (no malformed Change), and whether a staged batch is held at all
-    const uint8_t *wire = nullptr;
-    uint64_t wire_bytes = 0, base = 0, good = 0;
-    bool valid = false;
-    uint64_t off0 = 0;
-    uint32_t len0 = 0;
-    uint8_t ty0 = 0;
-    drp_frames fr = {};
-    drp_changes co = {};
-  } staged;
-};
-
-#define CHK(x)                                                                     \
-  do {                                                                             \
-    hipError_t e_ = (x);                                                           \
-    if (e_ != hipSuccess) {                                                        \
-      if (getenv("DRP_DEBUG")) fprintf(stderr, "drp: %s -> %s\n", #x, hipGetErrorString(e_)); \
-      return DRP_E_HIP;                                                            \
-    }                                                                              \
-  } while (0)
 
 extern "C" {
 
@@ -2104,388 +1941,6 @@ int drp_encode_batch(drp_ctx *c, const drp_change_src *src, const uint8_t *heap,
   return DRP_OK;
 }
 
-// drp_filter -> the select kernel's parameters and byte strings (DRP_E_INVAL: unknown bits,
-// EQ together with NONE, a string longer than DRP_SEL_MAX_BYTES or missing)
-static int select_filter(const drp_filter *f, drp::SelectParams &P, drp::SelectBytes &fb) {
-  P.fflags = 0;
-  P.subset_len = P.prefix_len = 0;
-  P.change_min = 0;
-  P.change_max = ~0ull;
-  if (!f) return DRP_OK;
-  if (f->flags & ~drp_select_known_flags()) return DRP_E_INVAL;
-  if ((f->flags & DRP_SEL_SUBSET_EQ) && (f->flags & DRP_SEL_SUBSET_NONE)) return DRP_E_INVAL;
-  P.fflags = f->flags;
-  if (f->flags & DRP_SEL_CHANGE_RANGE) {
-    P.change_min = f->change_min;
-    P.change_max = f->change_max;
-  }
-  if (f->flags & DRP_SEL_SUBSET_EQ) {
-    if (f->subset_len > DRP_SEL_MAX_BYTES || (f->subset_len && !f->subset)) return DRP_E_INVAL;
-    P.subset_len = f->subset_len;
-    if (f->subset_len) memcpy(fb.b, f->subset, f->subset_len);
-  }
-  if (f->flags & DRP_SEL_KEY_PREFIX) {
-    if (f->key_prefix_len > DRP_SEL_MAX_BYTES || (f->key_prefix_len && !f->key_prefix)) return DRP_E_INVAL;
-    P.prefix_len = f->key_prefix_len;
-    if (f->key_prefix_len) memcpy(fb.b + DRP_SEL_MAX_BYTES, f->key_prefix, f->key_prefix_len);
-  }
-  return DRP_OK;
-}
-
-static void select_out(drp::SelectParams &P, const drp_change_src *o, uint64_t *sel_idx, uint64_t *n_selected) {
-  // (the caller's arrays are writable device memory behind drp_change_src's const pointers)
-  P.o_key_off = const_cast<uint64_t *>(o->key_off);
-  P.o_key_len = const_cast<uint32_t *>(o->key_len);
-  P.o_subset_off = const_cast<uint64_t *>(o->subset_off);
-  P.o_subset_len = const_cast<uint32_t *>(o->subset_len);
-  P.o_value_off = const_cast<uint64_t *>(o->value_off);
-  P.o_value_len = const_cast<uint32_t *>(o->value_len);
-  P.o_change = const_cast<uint64_t *>(o->change);
-  P.o_from = const_cast<uint64_t *>(o->from);
-  P.o_to = const_cast<uint64_t *>(o->to);
-  P.o_flags = const_cast<uint8_t *>(o->flags);
-  P.sel_idx = sel_idx;
-  P.n_selected = n_selected;
-}
-
-// drp_select_device, or with `latest` drp_latest_device: the same arguments and checks
-static int select_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
-                         const drp_changes *cols, uint64_t n, const drp_filter *filter, const drp_change_src *out_rows,
-                         uint64_t *sel_idx, uint64_t *n_selected, bool latest) {
-  if (!c || !frames || !cols || !out_rows || !n_selected || (!bytes && nbytes)) return DRP_E_INVAL;
-  if (n && (!frames->payload_off || !frames->type || !cols->key_off || !cols->key_len || !cols->subset_off ||
-            !cols->subset_len || !cols->value_off || !cols->value_len || !cols->change || !cols->from || !cols->to ||
-            !cols->flags || !out_rows->key_off || !out_rows->key_len || !out_rows->subset_off ||
-            !out_rows->subset_len || !out_rows->value_off || !out_rows->value_len || !out_rows->change ||
-            !out_rows->from || !out_rows->to || !out_rows->flags))
-    return DRP_E_INVAL;
-  drp::SelectParams P;
-  drp::SelectBytes fb;
-  memset(&P, 0, sizeof(P));
-  memset(&fb, 0, sizeof(fb));
-  if (const int rc = select_filter(filter, P, fb)) return rc;
-  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
-  // (the decode scratch: free between decodes, and every user is ordered on the ctx's stream)
-  if (!c->scratch.ensure(latest ? drp_latest_scratch_bytes(n) : drp_select_scratch_bytes(n))) return DRP_E_NOMEM;
-  P.bytes = bytes;
-  P.nbytes = nbytes;
-  P.payload_off = frames->payload_off;
-  P.type = frames->type;
-  P.cols = *cols;
-  P.n = n;
-  select_out(P, out_rows, sel_idx, n_selected);
-  if (latest) CHK(drp_launch_latest(&P, &fb, c->latest_hash_mask, c->scratch.p, c->st));
-  else CHK(drp_launch_select(&P, &fb, c->scratch.p, c->st));
-  return DRP_OK;
-}
-
-int drp_select_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
-                      const drp_changes *cols, uint64_t n, const drp_filter *filter, const drp_change_src *out_rows,
-                      uint64_t *sel_idx, uint64_t *n_selected) {
-  return select_device(c, bytes, nbytes, frames, cols, n, filter, out_rows, sel_idx, n_selected, false);
-}
-
-int drp_latest_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
-                      const drp_changes *cols, uint64_t n, const drp_filter *filter, const drp_change_src *out_rows,
-                      uint64_t *sel_idx, uint64_t *n_selected) {
-  return select_device(c, bytes, nbytes, frames, cols, n, filter, out_rows, sel_idx, n_selected, true);
-}
-
-// drp_relay_staged, or with `latest` drp_latest_staged: the latest-per-key step in the select's place
-static int relay_staged(drp_ctx *c, const drp_filter *filter, uint8_t *out, uint64_t cap, uint64_t *written,
-                        uint64_t *n_selected, bool latest) {
-  if (!c || !written || !n_selected || (!out && cap)) return DRP_E_INVAL;
-  auto &S = c->staged;
-  if (!S.valid) return DRP_E_INVAL;
-  drp::SelectParams P;
-  drp::SelectBytes fb;
-  memset(&P, 0, sizeof(P));
-  memset(&fb, 0, sizeof(fb));
-  if (const int rc = select_filter(filter, P, fb)) return rc;
-  *written = 0;
-  *n_selected = 0;
-  const uint64_t n = S.good;  // the delivered GPU rows (a carried blob's row 0 is built on the host)
-  if (!n) return DRP_OK;
-  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
-  hipStream_t st = c->st;
-  // scratch (the decode's, free until the next decode): the kernel's words, the count, the piece
-  // table, the selected rows' columns
-  const uint64_t np = S.pieces.size();
-  const size_t o_cnt = al(latest ? drp_latest_scratch_bytes(n) : drp_select_scratch_bytes(n)), o_piece = o_cnt + 256, o_rows = o_piece + al(2 * np * 8),
-               o_end = o_rows + 10 * al(n * 8);
-  if (!c->scratch.ensure(o_end)) return DRP_E_NOMEM;
-  uint64_t *dcnt = c->scratch.at<uint64_t>(o_cnt);
-  drp_change_src rows;
-  {
-    size_t o = o_rows;
-    auto take = [&](size_t w) { void *p = c->scratch.at<char>(o); o += al(n * w); return p; };
-    rows.key_off = (const uint64_t *)take(8);
-    rows.key_len = (const uint32_t *)take(4);
-    rows.subset_off = (const uint64_t *)take(8);
-    rows.subset_len = (const uint32_t *)take(4);
-    rows.value_off = (const uint64_t *)take(8);
-    rows.value_len = (const uint32_t *)take(4);
-    rows.change = (const uint64_t *)take(8);
-    rows.from = (const uint64_t *)take(8);
-    rows.to = (const uint64_t *)take(8);
-    rows.flags = (const uint8_t *)take(1);
-  }
-  // a piece's payload offsets are relative to the batch offset it was staged at; the staged bytes
-  // start at batch offset S.base (a leading blob continuation never reaches the device)
-  if (np > 1) {
-    std::vector<uint64_t> &h = c->host_tmp;
-    h.resize(2 * np);
-    for (uint64_t k = 0; k < np; k++) {
-      h[k] = S.pieces[k].first;
-      h[np + k] = S.pieces[k].second - S.base;
-    }
-    CHK(hipMemcpyAsync(c->scratch.at<uint64_t>(o_piece), h.data(), 2 * np * 8, hipMemcpyHostToDevice, st));
-    P.piece_row = c->scratch.at<uint64_t>(o_piece);
-    P.piece_shift = P.piece_row + np;
-    P.npieces = np;
-  } else {
-    P.shift0 = np ? S.pieces[0].second - S.base : 0;
-  }
-  P.bytes = S.wire;
-  P.nbytes = S.wire_bytes;
-  P.payload_off = S.fr.payload_off;
-  P.type = S.fr.type;
-  P.cols = S.co;
-  P.n = n;
-  select_out(P, &rows, nullptr, dcnt);
-  if (latest) CHK(drp_launch_latest(&P, &fb, c->latest_hash_mask, c->scratch.p, st));
-  else CHK(drp_launch_select(&P, &fb, c->scratch.p, st));
-  uint64_t nsel = 0;
-  CHK(hipMemcpyAsync(&nsel, dcnt, 8, hipMemcpyDeviceToHost, st));
-  CHK(hipStreamSynchronize(st));  // (the one readback that sizes the encode)
-  *n_selected = nsel;
-  return drp_encode_batch(c, &rows, S.wire, S.wire_bytes, nsel, out, cap, written);
-}
-
-int drp_relay_staged(drp_ctx *c, const drp_filter *filter, uint8_t *out, uint64_t cap, uint64_t *written,
-                     uint64_t *n_selected) {
-  return relay_staged(c, filter, out, cap, written, n_selected, false);
-}
-
-int drp_latest_staged(drp_ctx *c, const drp_filter *filter, uint8_t *out, uint64_t cap, uint64_t *written,
-                      uint64_t *n_selected) {
-  return relay_staged(c, filter, out, cap, written, n_selected, true);
-}
-
-// ---- fan-out ------------------------------------------------------------------------------------
-// The filters, checked as select_filter checks one, into the ctx's page-locked table: nfilters
-// FanFilter records, then every filter's byte strings at 256-byte steps. The table travels by one
-// asynchronous copy, so before it is rewritten the copy of the previous call must have read it.
-static int fanout_filters(drp_ctx *c, const drp_filter *filters, uint32_t K, drp::FanParams &P) {
-  if (!filters || K == 0 || K > DRP_FANOUT_MAX) return DRP_E_INVAL;
-  const size_t o_bytes = al((size_t)K * sizeof(drp::FanFilter)), total = o_bytes + (size_t)K * drp::FAN_FBYTES;
-  std::vector<uint64_t> &h = c->host_tmp;  // (checked here first: a bad filter leaves the table alone)
-  h.assign((total + 7) / 8, 0);
-  uint8_t *tab = reinterpret_cast<uint8_t *>(h.data());
-  P.nfilters = K;
-  P.any_flags = P.any_bytes = 0;
-  for (uint32_t f = 0; f < K; f++) {
-    drp::SelectParams sp;
-    drp::SelectBytes fb;
-    memset(&sp, 0, sizeof(sp));
-    memset(&fb, 0, sizeof(fb));
-    if (const int rc = select_filter(&filters[f], sp, fb)) return rc;
-    drp::FanFilter F = {sp.fflags, sp.subset_len, sp.prefix_len, 0, sp.change_min, sp.change_max};
-    memcpy(tab + f * sizeof(F), &F, sizeof(F));
-    memcpy(tab + o_bytes + (size_t)f * drp::FAN_FBYTES, fb.b, drp::FAN_FBYTES);
-    P.any_flags |= sp.fflags;
-    if ((sp.fflags & DRP_SEL_SUBSET_EQ) && sp.subset_len) P.any_bytes |= DRP_SEL_SUBSET_EQ;
-    if ((sp.fflags & DRP_SEL_KEY_PREFIX) && sp.prefix_len) P.any_bytes |= DRP_SEL_KEY_PREFIX;
-  }
-  return DRP_OK;
-}
-
-// (after the scratch is placed) the checked table of fanout_filters to the device
-static int fanout_send_filters(drp_ctx *c, const drp::FanParams &P) {
-  const size_t total = al((size_t)P.nfilters * sizeof(drp::FanFilter)) + (size_t)P.nfilters * drp::FAN_FBYTES;
-  if (!c->fan_ev && hipEventCreateWithFlags(&c->fan_ev, hipEventDisableTiming) != hipSuccess) return DRP_E_HIP;
-  CHK(hipEventSynchronize(c->fan_ev));  // (never recorded: returns at once)
-  if (!c->fan_tab.ensure(total)) return DRP_E_NOMEM;
-  memcpy(c->fan_tab.p, c->host_tmp.data(), total);
-  // (filt is the scratch's first byte and the byte strings follow at the same offset as in the table)
-  CHK(hipMemcpyAsync(const_cast<drp::FanFilter *>(P.filt), c->fan_tab.p, total, hipMemcpyHostToDevice, c->st));
-  CHK(hipEventRecord(c->fan_ev, c->st));
-  return DRP_OK;
-}
-
-static void fanout_out(drp::FanParams &P, const drp_change_src *o, uint64_t rows_cap, uint64_t *sel_idx,
-                       uint64_t *row_base) {
-  drp::SelectParams sp;
-  select_out(sp, o, sel_idx, nullptr);
-  P.o_key_off = sp.o_key_off;
-  P.o_key_len = sp.o_key_len;
-  P.o_subset_off = sp.o_subset_off;
-  P.o_subset_len = sp.o_subset_len;
-  P.o_value_off = sp.o_value_off;
-  P.o_value_len = sp.o_value_len;
-  P.o_change = sp.o_change;
-  P.o_from = sp.o_from;
-  P.o_to = sp.o_to;
-  P.o_flags = sp.o_flags;
-  P.sel_idx = sel_idx;
-  P.rows_cap = rows_cap;
-  P.row_base = row_base;
-}
-
-int drp_fanout_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
-                      const drp_changes *cols, uint64_t n, const drp_filter *filters, uint32_t nfilters,
-                      const drp_change_src *out_rows, uint64_t rows_cap, uint64_t *sel_idx, uint64_t *row_base,
-                      const drp_splice *splice) {
-  if (!c || !frames || !cols || !out_rows || !row_base || (!bytes && nbytes)) return DRP_E_INVAL;
-  if (n && (!frames->payload_off || !frames->type || !cols->key_off || !cols->key_len || !cols->subset_off ||
-            !cols->subset_len || !cols->value_off || !cols->value_len || !cols->change || !cols->from || !cols->to ||
-            !cols->flags || !out_rows->key_off || !out_rows->key_len || !out_rows->subset_off ||
-            !out_rows->subset_len || !out_rows->value_off || !out_rows->value_len || !out_rows->change ||
-            !out_rows->from || !out_rows->to || !out_rows->flags))
-    return DRP_E_INVAL;
-  if (splice && (!splice->n_blobs || (splice->blob_cap && (!splice->blob_row || !splice->blob_rank)))) return DRP_E_INVAL;
-  drp::FanParams P;
-  memset(&P, 0, sizeof(P));
-  if (const int rc = fanout_filters(c, filters, nfilters, P)) return rc;
-  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
-  // (the decode scratch: free between decodes, and every user is ordered on the ctx's stream)
-  if (!c->scratch.ensure(drp_fanout_scratch_bytes(n, nfilters))) return DRP_E_NOMEM;
-  P.bytes = bytes;
-  P.nbytes = nbytes;
-  P.payload_off = frames->payload_off;
-  P.type = frames->type;
-  P.cols = *cols;
-  P.n = n;
-  drp_fanout_place(&P, c->scratch.p);
-  fanout_out(P, out_rows, rows_cap, sel_idx, row_base);
-  if (const int rc = fanout_send_filters(c, P)) return rc;
-  CHK(drp_launch_fanout_count(&P, c->st));
-  CHK(drp_launch_fanout_scatter(&P, c->st));
-  if (splice) {
-    P.blob_row = splice->blob_row;
-    P.blob_rank = splice->blob_rank;
-    P.n_blobs = splice->n_blobs;
-    P.blob_cap = splice->blob_cap;
-    CHK(drp_launch_fanout_splice(&P, c->st));
-  }
-  return DRP_OK;
-}
-
-int drp_fanout_staged(drp_ctx *c, const drp_filter *filters, uint32_t nfilters, uint8_t *out, uint64_t cap,
-                      uint64_t *out_off, uint64_t *n_selected, uint64_t *blob_row, uint64_t *blob_pos,
-                      uint64_t blob_cap, uint64_t *n_blobs) {
-  if (!c || !out_off || !n_selected || (!out && cap)) return DRP_E_INVAL;
-  if (blob_row ? (!n_blobs || (!blob_pos && blob_cap)) : (n_blobs != nullptr)) return DRP_E_INVAL;
-  auto &S = c->staged;
-  if (!S.valid) return DRP_E_INVAL;
-  drp::FanParams P;
-  memset(&P, 0, sizeof(P));
-  if (const int rc = fanout_filters(c, filters, nfilters, P)) return rc;
-  const uint32_t K = nfilters;
-  for (uint32_t f = 0; f <= K; f++) out_off[f] = 0;
-  for (uint32_t f = 0; f < K; f++) n_selected[f] = 0;
-  if (n_blobs) *n_blobs = 0;
-  const uint64_t n = S.good;  // the delivered GPU rows (a carried blob's row 0 is built on the host)
-  if (!n) return DRP_OK;
-  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
-  hipStream_t st = c->st;
-  // scratch (the decode's, free until the next decode): the kernels' words, row_base with the grand
-  // total and the splice kernel's blob count behind it, the piece table
-  const uint64_t np = S.pieces.size();
-  const size_t o_base = al(drp_fanout_scratch_bytes(n, K)), o_piece = o_base + al((K + 3) * 8),
-               o_end = o_piece + al(2 * np * 8);
-  if (!c->scratch.ensure(o_end)) return DRP_E_NOMEM;
-  P.bytes = S.wire;
-  P.nbytes = S.wire_bytes;
-  P.payload_off = S.fr.payload_off;
-  P.type = S.fr.type;
-  P.cols = S.co;
-  P.n = n;
-  drp_fanout_place(&P, c->scratch.p);
-  uint64_t *drb = c->scratch.at<uint64_t>(o_base);
-  P.row_base = drb;
-  P.gtotal = drb + K + 1;  // (one readback brings the outputs' bounds and the blob count)
-  if (const int rc = fanout_send_filters(c, P)) return rc;
-  std::vector<uint64_t> &h = c->host_tmp;  // (its filter table has been copied out)
-  if (np > 1) {
-    h.resize(2 * np);
-    for (uint64_t k = 0; k < np; k++) {
-      h[k] = S.pieces[k].first;
-      h[np + k] = S.pieces[k].second - S.base;
-    }
-    CHK(hipMemcpyAsync(c->scratch.at<uint64_t>(o_piece), h.data(), 2 * np * 8, hipMemcpyHostToDevice, st));
-    P.piece_row = c->scratch.at<uint64_t>(o_piece);
-    P.piece_shift = P.piece_row + np;
-    P.npieces = np;
-  } else {
-    P.shift0 = np ? S.pieces[0].second - S.base : 0;
-  }
-  CHK(drp_launch_fanout_count(&P, st));
-  uint64_t rb[DRP_FANOUT_MAX + 2];
-  CHK(hipMemcpyAsync(rb, drb, (K + 2) * 8, hipMemcpyDeviceToHost, st));
-  CHK(hipStreamSynchronize(st));  // (the one readback that sizes the rows and the encode)
-  const uint64_t total = rb[K], nb_true = rb[K + 1] - rb[K];
-  for (uint32_t f = 0; f < K; f++) n_selected[f] = rb[f + 1] - rb[f];
-  if (n_blobs) *n_blobs = nb_true;
-  const uint64_t nb = (blob_row && nb_true <= blob_cap) ? nb_true : 0;  // the splice entries to produce
-  // the selected rows (sized from the true total) and the splice kernel's outputs
-  const size_t col = al(total * 8), o_brow = 10 * col, o_rank = o_brow + al(nb * 8);
-  if (!c->fan_rows.ensure(o_rank + al((size_t)K * nb * 8) + 256)) return DRP_E_NOMEM;
-  drp_change_src rows;
-  {
-    size_t o = 0;
-    auto take = [&]() { void *p = c->fan_rows.at<char>(o); o += col; return p; };
-    rows.key_off = (const uint64_t *)take();
-    rows.key_len = (const uint32_t *)take();
-    rows.subset_off = (const uint64_t *)take();
-    rows.subset_len = (const uint32_t *)take();
-    rows.value_off = (const uint64_t *)take();
-    rows.value_len = (const uint32_t *)take();
-    rows.change = (const uint64_t *)take();
-    rows.from = (const uint64_t *)take();
-    rows.to = (const uint64_t *)take();
-    rows.flags = (const uint8_t *)take();
-  }
-  fanout_out(P, &rows, total, nullptr, drb);
-  CHK(drp_launch_fanout_scatter(&P, st));
-  uint64_t *drank = c->fan_rows.at<uint64_t>(o_rank);
-  if (nb) {
-    P.blob_row = c->fan_rows.at<uint64_t>(o_brow);
-    P.blob_rank = drank;
-    P.n_blobs = drb + K + 2;  // (a word of its own: the grand total is still read by the kernel)
-    P.blob_cap = nb;
-    P.row_bias = S.nf0;
-    CHK(drp_launch_fanout_splice(&P, st));
-  }
-  // one encode of all outputs; its bytes go to `out` or, for a host `out`, to the output staging,
-  // which need not be larger than the outputs can get (none is longer than the staged wire)
-  const bool odev = is_device_ptr(out);
-  uint64_t nonempty = 0;
-  for (uint32_t f = 0; f < K; f++) nonempty += n_selected[f] != 0;
-  const uint64_t dcap = odev ? cap : std::min<uint64_t>(cap, nonempty * S.wire_bytes);
-  const size_t o_gat = al((total + 1) * 8), gat_n = (size_t)K + 1 + (size_t)K * nb, o_out = o_gat + al(gat_n * 8);
-  if (!c->out_stage.ensure(o_out + (odev ? 0 : dcap + 64))) return DRP_E_NOMEM;
-  uint64_t *foff = c->out_stage.at<uint64_t>(0), *dgat = c->out_stage.at<uint64_t>(o_gat);
-  uint8_t *dout = odev ? out : c->out_stage.at<uint8_t>(o_out);
-  if (const int rc = drp_encode_device(c, &rows, S.wire, S.wire_bytes, total, foff, dout, dcap)) return rc;
-  // the outputs' bounds and the blobs' byte positions, gathered into one block for one readback
-  CHK(drp_launch_fanout_gather(foff, drb, K, drank, nb, dgat, dgat + K + 1, st));
-  h.resize(gat_n + nb);
-  CHK(hipMemcpyAsync(h.data(), dgat, gat_n * 8, hipMemcpyDeviceToHost, st));
-  if (nb) CHK(hipMemcpyAsync(h.data() + gat_n, P.blob_row, nb * 8, hipMemcpyDeviceToHost, st));
-  CHK(hipStreamSynchronize(st));
-  if (h[K] == ~0ull) return DRP_E_INVAL;  // a row's key/subset/value range is outside the wire
-  for (uint32_t f = 0; f <= K; f++) out_off[f] = h[f];
-  if (h[K] > cap) return DRP_E_CAPACITY;
-  for (uint64_t j = 0; j < nb; j++) blob_row[j] = h[gat_n + j];
-  for (uint32_t f = 0; f < K && nb; f++)
-    memcpy(blob_pos + (uint64_t)f * blob_cap, h.data() + K + 1 + (uint64_t)f * nb, nb * 8);
-  if (!odev && h[K]) {
-    CHK(hipMemcpyAsync(out, dout, h[K], hipMemcpyDeviceToHost, st));
-    CHK(hipStreamSynchronize(st));
-  }
-  return DRP_OK;
-}
 
 int drp_index_scan(drp_ctx *c, const drp_stream_stats *stats, uint64_t count, uint64_t *base) {
   if (!c || (!stats && count) || (!base && count)) return DRP_E_INVAL;

@@ -3697,7 +3697,6 @@ extern "C" uint32_t drp_spec_miss_bit(void) { return spec::F_MISS; }
 extern "C" uint32_t drp_spec_cascade_bit(void) { return spec::F_CASCADE; }
 
 // Claims and verification only (the host checks the prediction before anything is emitted).
-extern "C" void drp_dbg_mark(const char *name, hipStream_t st);  // (drp_api.hip: DRP_WATCHDOG)
 
 extern "C" hipError_t drp_launch_spec_head(const DecodeParams *P, uint64_t nt_max, uint64_t nstreams,
                                            uint32_t *tile_stream, hipStream_t st) {

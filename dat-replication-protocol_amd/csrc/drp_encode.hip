@@ -615,7 +615,6 @@ using namespace drp;
 // the capacity allows; blocks past the real end exit at once)
 extern "C" uint64_t drp_encode_out_blocks(uint64_t cap) { return (cap + 15) / ENC_BS + 2; }
 
-extern "C" void drp_dbg_mark(const char *name, hipStream_t st);  // (drp_api.hip: DRP_WATCHDOG)
 
 extern "C" hipError_t drp_launch_encode(const EncodeParams *Pp, hipStream_t st) {
   EncodeParams P = *Pp;

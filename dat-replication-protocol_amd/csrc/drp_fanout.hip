@@ -21,8 +21,7 @@
 //  (4) fan_splice: blob j's row and, per filter, the rows of that output before it, from the same
 //      ballot words and scanned counts (no predicate is evaluated again).
 // No global atomics (same-address atomics serialise across the 8 XCDs); every loop is bounded.
-#include "drp_device.h"
-#include "drp_kernels.h"
+#include "drp_select.h"  // (pred_load / pred_conds, row_load / row_store)
 
 namespace drp {
 
@@ -32,90 +31,41 @@ constexpr uint32_t FAN_SCAN = 1024;                                            /
 constexpr uint32_t FAN_PLANES = DRP_FANOUT_MAX + 1;                            // the filters and the blob rows
 static_assert(FAN_CHUNKS == 64, "fan_prefix scans one ballot word per lane");
 
-// what row i's payload offsets lack to be offsets into P.bytes (sel_shift of drp_select.hip)
-__device__ __forceinline__ uint64_t fan_shift(const FanParams &P, uint64_t i) {
-  if (P.npieces <= 1) return P.shift0;
-  uint64_t lo = 0, hi = P.npieces;  // piece_row[lo] <= i < piece_row[hi]
-  while (hi - lo > 1) {
-    const uint64_t mid = (lo + hi) >> 1;
-    if (P.piece_row[mid] <= i) lo = mid;
-    else hi = mid;
-  }
-  return P.piece_shift[lo];
-}
-
-// wire bytes [off, off + len) == ref[0, len); a range outside the wire matches nothing
-__device__ __forceinline__ bool fan_bytes_eq(const FanParams &P, uint64_t off, uint32_t len, const uint8_t *ref) {
-  if ((uint64_t)len > P.nbytes || off > P.nbytes - len) return false;
-  const uint8_t *w = P.bytes + off;
-  for (uint32_t k = 0; k < len; k++)
-    if (w[k] != ref[k]) return false;
-  return true;
-}
-
-// the columns of one row the predicates read (loaded once, whatever the number of filters)
-struct FanRow {
-  uint64_t change, sub_at, key_at;  // sub_at / key_at: the subset's / key's offset into P.bytes
-  uint32_t flags, subset_len, key_len;
-};
-
-// sel_pred's conditions on a well-formed Change row, the byte compares last
-__device__ __forceinline__ bool fan_pred(const FanParams &P, const FanFilter &F, uint32_t f, const FanRow &r) {
-  const uint32_t ff = F.flags;
-  if ((ff & DRP_SEL_CHANGE_RANGE) && (r.change < F.change_min || r.change > F.change_max)) return false;
-  if ((ff & DRP_SEL_SUBSET_NONE) && (r.flags & DRP_F_SUBSET)) return false;
-  if ((ff & DRP_SEL_SUBSET_EQ) && (!(r.flags & DRP_F_SUBSET) || r.subset_len != F.subset_len)) return false;
-  if ((ff & DRP_SEL_KEY_PREFIX) && r.key_len < F.prefix_len) return false;
-  const uint8_t *fb = P.fbytes + (size_t)f * FAN_FBYTES;
-  if ((ff & DRP_SEL_SUBSET_EQ) && F.subset_len && !fan_bytes_eq(P, r.sub_at, F.subset_len, fb)) return false;
-  if ((ff & DRP_SEL_KEY_PREFIX) && F.prefix_len && !fan_bytes_eq(P, r.key_at, F.prefix_len, fb + DRP_SEL_MAX_BYTES))
-    return false;
-  return true;
-}
-
 // (1) the ballot word of every (filter, 64 rows) and the rows kept per (filter, workgroup)
 __global__ __launch_bounds__(FAN_BLK) void fan_count_kernel(const FanParams P) {
-  __shared__ FanFilter sf[DRP_FANOUT_MAX];
+  __shared__ RowFilter sf[DRP_FANOUT_MAX];
   __shared__ uint32_t wcnt[FAN_PLANES][FAN_WAVES];
+  const RowSrc &S = P.src;
   const uint32_t K = P.nfilters, wv = uniform32(threadIdx.x >> 6), lane = lane_id();
-  if (threadIdx.x < K * (sizeof(FanFilter) / 4))  // (K * 8 <= 512 words)
+  if (threadIdx.x < K * (sizeof(RowFilter) / 4))  // (K * 8 <= 512 words)
     reinterpret_cast<uint32_t *>(sf)[threadIdx.x] = reinterpret_cast<const uint32_t *>(P.filt)[threadIdx.x];
   const uint64_t word0 = (uint64_t)blockIdx.x * FAN_CHUNKS + wv * FAN_RPL;  // (< nwords: the grid is nwg)
-  FanRow row[FAN_RPL];
+  PredRow row[FAN_RPL];
   bool ok[FAN_RPL], blob[FAN_RPL];
-  const drp_changes &c = P.cols;
 #pragma unroll
   for (uint32_t r = 0; r < FAN_RPL; r++) {
     const uint64_t i = (word0 + r) * 64 + lane;
     ok[r] = blob[r] = false;
-    row[r] = FanRow{0, 0, 0, 0, 0, 0};
-    if (i < P.n) {
-      const uint32_t ty = P.type[i] & 0x3Fu;
+    row[r] = PredRow{0, 0, 0, 0, 0, 0};
+    if (i < S.n) {
+      const uint32_t ty = S.type[i] & 0x3Fu;
       blob[r] = ty == DRP_TYPE_BLOB;
       if (ty == DRP_TYPE_CHANGE) {
-        row[r].flags = c.flags[i];
+        row[r].flags = S.cols.flags[i];
         ok[r] = !(row[r].flags & DRP_F_BAD);
       }
     }
-    if (ok[r]) {
-      if (P.any_flags & DRP_SEL_CHANGE_RANGE) row[r].change = c.change[i];
-      if (P.any_flags & DRP_SEL_SUBSET_EQ) row[r].subset_len = c.subset_len[i];
-      if (P.any_flags & DRP_SEL_KEY_PREFIX) row[r].key_len = c.key_len[i];
-      if (P.any_bytes) {
-        const uint64_t base = P.payload_off[i] + fan_shift(P, i);
-        if (P.any_bytes & DRP_SEL_SUBSET_EQ) row[r].sub_at = base + c.subset_off[i];
-        if (P.any_bytes & DRP_SEL_KEY_PREFIX) row[r].key_at = base + c.key_off[i];
-      }
-    }
+    if (ok[r]) pred_load(S, i, P.any_flags, P.any_bytes, row[r]);
   }
   __syncthreads();
   for (uint32_t f = 0; f < K; f++) {  // (wave-uniform: K is a launch argument)
-    const FanFilter F = sf[f];
+    const RowFilter F = sf[f];
+    const uint8_t *fb = P.fbytes + (size_t)f * FAN_FBYTES;
     uint64_t *mrow = P.mask + (uint64_t)f * P.nwords + word0;
     uint32_t cnt = 0;
 #pragma unroll
     for (uint32_t r = 0; r < FAN_RPL; r++) {
-      const bool keep = ok[r] && fan_pred(P, F, f, row[r]);
+      const bool keep = ok[r] && pred_conds(S, F, fb, fb + DRP_SEL_MAX_BYTES, row[r]);
       const uint64_t b = __ballot(keep);
       if (lane == 0) mrow[r] = b;
       cnt += (uint32_t)__popcll(b);
@@ -223,7 +173,6 @@ __global__ __launch_bounds__(FAN_BLK) void fan_scatter_kernel(const FanParams P)
   fan_prefix(P, K, words, pre, base);
   const uint32_t wv = uniform32(threadIdx.x >> 6), lane = lane_id();
   const uint64_t below = (1ull << lane) - 1ull;
-  const drp_changes &c = P.cols;
 #pragma unroll 1
   for (uint32_t r = 0; r < FAN_RPL; r++) {
     const uint32_t ch = wv * FAN_RPL + r;
@@ -231,26 +180,12 @@ __global__ __launch_bounds__(FAN_BLK) void fan_scatter_kernel(const FanParams P)
     for (uint32_t f = 0; f < K; f++) any |= words[f][ch];  // (wave-uniform LDS reads)
     if (!((any >> lane) & 1ull)) continue;  // (kept by no filter; a bit is only ever set for a row < n)
     const uint64_t i = ((uint64_t)blockIdx.x * FAN_CHUNKS + ch) * 64 + lane;
-    const uint64_t at = P.payload_off[i] + fan_shift(P, i);
-    const uint64_t key_off = at + c.key_off[i], subset_off = at + c.subset_off[i], value_off = at + c.value_off[i];
-    const uint32_t key_len = c.key_len[i], subset_len = c.subset_len[i], value_len = c.value_len[i];
-    const uint64_t change = c.change[i], from = c.from[i], to = c.to[i];
-    const uint8_t flags = (uint8_t)(c.flags[i] & (DRP_F_SUBSET | DRP_F_VALUE));
+    const EncRow row = row_load(P.src, i);
     for (uint32_t f = 0; f < K; f++) {
       const uint64_t b = words[f][ch];
       if (!((b >> lane) & 1ull)) continue;
       const uint64_t slot = base[f] + pre[f][ch] + (uint32_t)__popcll(b & below);  // (< row_base[K] <= rows_cap)
-      P.o_key_off[slot] = key_off;
-      P.o_key_len[slot] = key_len;
-      P.o_subset_off[slot] = subset_off;
-      P.o_subset_len[slot] = subset_len;
-      P.o_value_off[slot] = value_off;
-      P.o_value_len[slot] = value_len;
-      P.o_change[slot] = change;
-      P.o_from[slot] = from;
-      P.o_to[slot] = to;
-      P.o_flags[slot] = flags;
-      if (P.sel_idx) P.sel_idx[slot] = i;
+      row_store(P.out, slot, row, i);
     }
   }
 }
@@ -307,7 +242,7 @@ struct FanLayout {
   FanLayout(uint64_t n, uint32_t K) {
     const uint64_t nwg = fan_nwg(n), planes = (uint64_t)K + 1, m = planes * nwg;
     filt = 0;
-    fbytes = fan_al((uint64_t)K * sizeof(FanFilter));
+    fbytes = fan_al((uint64_t)K * sizeof(RowFilter));
     mask = fbytes + (uint64_t)K * FAN_FBYTES;
     cnt = mask + fan_al(planes * nwg * FAN_CHUNKS * 8);
     bsum = cnt + fan_al(m * 8);
@@ -320,23 +255,21 @@ struct FanLayout {
 extern "C" uint64_t drp_fanout_scratch_bytes(uint64_t n, uint32_t nfilters) { return FanLayout(n, nfilters).end; }
 
 extern "C" void drp_fanout_place(FanParams *P, void *scratch) {
-  const FanLayout L(P->n, P->nfilters);
+  const FanLayout L(P->src.n, P->nfilters);
   uint8_t *sc = static_cast<uint8_t *>(scratch);
-  P->filt = reinterpret_cast<const FanFilter *>(sc + L.filt);
+  P->filt = reinterpret_cast<const RowFilter *>(sc + L.filt);
   P->fbytes = sc + L.fbytes;
   P->mask = reinterpret_cast<uint64_t *>(sc + L.mask);
   P->block_cnt = reinterpret_cast<uint64_t *>(sc + L.cnt);
   P->bsum = reinterpret_cast<uint64_t *>(sc + L.bsum);
   P->gtotal = reinterpret_cast<uint64_t *>(sc + L.tot);
-  P->nwg = fan_nwg(P->n);
+  P->nwg = fan_nwg(P->src.n);
   P->nwords = P->nwg * FAN_CHUNKS;
 }
 
-extern "C" void drp_dbg_mark(const char *name, hipStream_t st);  // (drp_api.hip: DRP_WATCHDOG)
-
 extern "C" hipError_t drp_launch_fanout_count(const FanParams *Pp, hipStream_t st) {
   const FanParams &P = *Pp;
-  if (P.n == 0) {  // no rows: every output and the blob list are empty
+  if (P.src.n == 0) {  // no rows: every output and the blob list are empty
     hipError_t e = hipMemsetAsync(P.row_base, 0, ((size_t)P.nfilters + 1) * 8, st);
     if (e == hipSuccess) e = hipMemsetAsync(P.gtotal, 0, 8, st);
     return e;
@@ -351,14 +284,14 @@ extern "C" hipError_t drp_launch_fanout_count(const FanParams *Pp, hipStream_t s
 }
 
 extern "C" hipError_t drp_launch_fanout_scatter(const FanParams *Pp, hipStream_t st) {
-  if (Pp->n == 0) return hipSuccess;
+  if (Pp->src.n == 0) return hipSuccess;
   hipLaunchKernelGGL(fan_scatter_kernel, dim3((uint32_t)Pp->nwg), dim3(FAN_BLK), 0, st, *Pp);
   drp_dbg_mark("fanout_scatter", st);
   return hipGetLastError();
 }
 
 extern "C" hipError_t drp_launch_fanout_splice(const FanParams *Pp, hipStream_t st) {
-  if (Pp->n == 0) return hipMemsetAsync(Pp->n_blobs, 0, 8, st);
+  if (Pp->src.n == 0) return hipMemsetAsync(Pp->n_blobs, 0, 8, st);
   hipLaunchKernelGGL(fan_splice_kernel, dim3((uint32_t)Pp->nwg), dim3(FAN_BLK), 0, st, *Pp);
   drp_dbg_mark("fanout_splice", st);
   return hipGetLastError();

@@ -109,36 +109,58 @@ struct EncodeParams {
   uint64_t nob;  // output blocks the grid covers (from cap)
 };
 
-// drp_select.hip: predicate + stable compaction of decoded Change rows into encoder rows
-struct SelectParams {
-  const uint8_t *bytes;  // the wire the columns point into
+// The relay kernels (drp_select.hip, drp_latest.hip, drp_fanout.hip) share their row source, their
+// row destination and their filter record; drp_select.h holds the device code over them.
+// The decoded rows and the wire their columns point into
+struct RowSrc {
+  const uint8_t *bytes;
   uint64_t nbytes;
   const uint64_t *payload_off;
   const uint8_t *type;
   drp_changes cols;  // (read only)
   uint64_t n;
-  // filter (drp_filter; its byte strings in device memory, placed by the launcher)
-  uint32_t fflags, subset_len, prefix_len;
-  uint64_t change_min, change_max;
-  const uint8_t *subset, *prefix;
   // rows of a batch staged in pieces: piece k holds rows [piece_row[k], piece_row[k + 1]) and its
   // payload offsets are piece_shift[k] short of offsets into `bytes` (npieces <= 1: shift0 for all)
   const uint64_t *piece_row, *piece_shift;
   uint64_t npieces, shift0;
-  // scratch (placed by the launcher): one ballot word per 64 rows, one count per workgroup
-  uint64_t *mask, *block_cnt;
-  // outputs
+};
+
+// encoder rows (drp_change_src, offsets absolute into the wire) and each one's source row
+struct RowOut {
   uint64_t *o_key_off, *o_subset_off, *o_value_off;
   uint32_t *o_key_len, *o_subset_len, *o_value_len;
   uint64_t *o_change, *o_from, *o_to;
   uint8_t *o_flags;
   uint64_t *sel_idx;  // may be null
+};
+
+// one filter (drp_filter without its pointers; conditions that are off hold neutral values)
+struct RowFilter {
+  uint32_t flags, subset_len, prefix_len, reserved;
+  uint64_t change_min, change_max;
+};
+static_assert(sizeof(RowFilter) == 32, "the fan-out's device table holds 32-byte records");
+// DRP_SEL_SUBSET_EQ / DRP_SEL_KEY_PREFIX where the filter compares such bytes (a non-empty string)
+__host__ __device__ inline uint32_t filter_bytes(const RowFilter &F) {
+  return ((F.flags & DRP_SEL_SUBSET_EQ) && F.subset_len ? DRP_SEL_SUBSET_EQ : 0u) |
+         ((F.flags & DRP_SEL_KEY_PREFIX) && F.prefix_len ? DRP_SEL_KEY_PREFIX : 0u);
+}
+constexpr uint32_t FAN_FBYTES = 2 * DRP_SEL_MAX_BYTES;  // per filter: subset, then key prefix
+
+// drp_select.hip: predicate + stable compaction of decoded Change rows into encoder rows
+struct SelectParams {
+  RowSrc src;
+  RowFilter f;
+  const uint8_t *subset, *prefix;  // its byte strings in device memory, placed by the launcher
+  // scratch (placed by the launcher): one ballot word per 64 rows, one count per workgroup
+  uint64_t *mask, *block_cnt;
+  RowOut out;
   uint64_t *n_selected;
 };
 
 // the filter's byte strings as launch arguments: subset, then key prefix
 struct SelectBytes {
-  uint8_t b[2 * DRP_SEL_MAX_BYTES];
+  uint8_t b[FAN_FBYTES];
 };
 
 // drp_latest.hip: the select's candidates grouped by (subset presence, subset bytes, key bytes) in
@@ -156,39 +178,19 @@ struct LatestParams {
 };
 constexpr uint64_t LAT_NONE = ~0ull;
 
-// drp_fanout.hip: up to DRP_FANOUT_MAX filters over one pass of the decoded rows. One filter of
-// the device table (drp_filter without its pointers; conditions that are off hold neutral values)
-struct FanFilter {
-  uint32_t flags, subset_len, prefix_len, reserved;
-  uint64_t change_min, change_max;
-};
-constexpr uint32_t FAN_FBYTES = 2 * DRP_SEL_MAX_BYTES;  // per filter: subset, then key prefix
-
+// drp_fanout.hip: up to DRP_FANOUT_MAX filters over one pass of the decoded rows
 struct FanParams {
-  const uint8_t *bytes;  // the wire the columns point into
-  uint64_t nbytes;
-  const uint64_t *payload_off;
-  const uint8_t *type;
-  drp_changes cols;  // (read only)
-  uint64_t n;
+  RowSrc src;
   uint32_t nfilters;
   uint32_t any_flags;  // the OR of the filters' flags: the columns the count step reads
   uint32_t any_bytes;  // DRP_SEL_SUBSET_EQ / DRP_SEL_KEY_PREFIX: some filter compares such bytes
-  const FanFilter *filt;  // [nfilters], device
+  const RowFilter *filt;  // [nfilters], device
   const uint8_t *fbytes;  // [nfilters][FAN_FBYTES], device
-  // rows of a batch staged in pieces (as SelectParams)
-  const uint64_t *piece_row, *piece_shift;
-  uint64_t npieces, shift0;
   // scratch: ballot words [nfilters + 1][nwords] (the last plane: the blob rows), counts
   // [nfilters + 1][nwg] (scanned in place), the sums of every FAN_SCAN counts, the grand total
   uint64_t *mask, *block_cnt, *bsum, *gtotal;
   uint64_t nwg, nwords;
-  // outputs
-  uint64_t *o_key_off, *o_subset_off, *o_value_off;
-  uint32_t *o_key_len, *o_subset_len, *o_value_len;
-  uint64_t *o_change, *o_from, *o_to;
-  uint8_t *o_flags;
-  uint64_t *sel_idx;  // may be null
+  RowOut out;
   uint64_t rows_cap;
   uint64_t *row_base;  // [nfilters + 1]
   // splice table (fan_splice; blob_row null: none)
@@ -199,6 +201,7 @@ struct FanParams {
 }  // namespace drp
 
 extern "C" {
+void drp_dbg_mark(const char *name, hipStream_t st);  // (drp_api.hip: a named event under DRP_WATCHDOG)
 // regions a decode's prologue fills (drp_launch_prologue): byte value, 4-byte multiples
 struct ClearSet {
   static constexpr uint32_t CAP = 12;  // (a decode fills up to 9: with records, the density sample and DRP_STATS)

@@ -34,12 +34,8 @@ namespace drp {
 // the three words of slot s
 __device__ __forceinline__ uint64_t *lat_word(const LatestParams &L, uint64_t s, uint32_t w) { return L.tab + 3 * s + w; }
 
-__device__ __forceinline__ bool lat_in_wire(const SelectParams &P, uint64_t off, uint32_t len) {
-  return (uint64_t)len <= P.nbytes && off <= P.nbytes - len;
-}
-
 // wire bytes [a, a + len) == [b, b + len) (both ranges inside the wire)
-__device__ __forceinline__ bool lat_bytes_eq(const SelectParams &P, uint64_t a, uint64_t b, uint32_t len) {
+__device__ __forceinline__ bool lat_bytes_eq(const RowSrc &P, uint64_t a, uint64_t b, uint32_t len) {
   const uint8_t *x = P.bytes + a, *y = P.bytes + b;
   if (len < 8) {
     for (uint32_t k = 0; k < len; k++)
@@ -53,29 +49,29 @@ __device__ __forceinline__ bool lat_bytes_eq(const SelectParams &P, uint64_t a, 
 }
 
 // candidate row j (it claimed a slot: its ranges are inside the wire) has this identity
-__device__ __forceinline__ bool lat_same(const SelectParams &P, uint64_t j, bool has, uint64_t koff, uint32_t klen,
+__device__ __forceinline__ bool lat_same(const RowSrc &P, uint64_t j, bool has, uint64_t koff, uint32_t klen,
                                          uint64_t soff, uint32_t slen) {
   const drp_changes &c = P.cols;
   if (((c.flags[j] & DRP_F_SUBSET) != 0) != has || c.key_len[j] != klen) return false;
   if (has && c.subset_len[j] != slen) return false;
-  const uint64_t base = P.payload_off[j] + sel_shift(P, j);
+  const uint64_t base = P.payload_off[j] + row_shift(P, j);
   if (!lat_bytes_eq(P, base + c.key_off[j], koff, klen)) return false;
   return !has || lat_bytes_eq(P, base + c.subset_off[j], soff, slen);
 }
 
 __global__ __launch_bounds__(SEL_BLK) void lat_insert_kernel(const LatestParams L) {
-  const SelectParams &P = L.sel;
+  const RowSrc &P = L.sel.src;
   const uint64_t i = (uint64_t)blockIdx.x * SEL_BLK + threadIdx.x;
   if (i >= P.n) return;
   uint64_t mine = LAT_NONE;
-  if (sel_pred(P, i)) {
+  if (sel_pred(L.sel, i)) {
     const drp_changes &c = P.cols;
     const bool has = (c.flags[i] & DRP_F_SUBSET) != 0;
-    const uint64_t base = P.payload_off[i] + sel_shift(P, i);
+    const uint64_t base = P.payload_off[i] + row_shift(P, i);
     const uint64_t koff = base + c.key_off[i], soff = base + c.subset_off[i];
     const uint32_t klen = c.key_len[i], slen = has ? c.subset_len[i] : 0;
     // a row whose key or subset range leaves the wire is never read and is no candidate
-    if (lat_in_wire(P, koff, klen) && (!has || lat_in_wire(P, soff, slen))) {
+    if (wire_has(P, koff, klen) && (!has || wire_has(P, soff, slen))) {
       uint64_t h = xxh::xxh64(P.bytes + koff, klen);
       if (has) h = xxh::merge(h, xxh::xxh64(P.bytes + soff, slen));  // (an empty subset still changes h)
       h &= L.hash_mask;
@@ -107,37 +103,23 @@ __global__ __launch_bounds__(SEL_BLK) void lat_insert_kernel(const LatestParams 
 
 __global__ __launch_bounds__(SEL_BLK) void lat_pick_kernel(const LatestParams L) {
   const uint64_t i = (uint64_t)blockIdx.x * SEL_BLK + threadIdx.x;
-  if (i >= L.sel.n) return;
+  if (i >= L.sel.src.n) return;
   const uint64_t s = L.slot[i];
   if (s == LAT_NONE) return;
   // (a group whose only change is 0 matches the cleared word)
-  if (L.sel.cols.change[i] == *lat_word(L, s, 1) && ld_agent(lat_word(L, s, 2)) < i + 1)  // (as lat_insert's maximum)
+  if (L.sel.src.cols.change[i] == *lat_word(L, s, 1) && ld_agent(lat_word(L, s, 2)) < i + 1)  // (as lat_insert's maximum)
     __hip_atomic_fetch_max(lat_word(L, s, 2), i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // sel_count_kernel with the predicate "the row its group picked"
 __global__ __launch_bounds__(SEL_BLK) void lat_keep_kernel(const LatestParams L) {
-  __shared__ uint32_t wcnt[SEL_WAVES];
-  const SelectParams &P = L.sel;
   const uint64_t i = (uint64_t)blockIdx.x * SEL_BLK + threadIdx.x;
   bool keep = false;
-  if (i < P.n) {
+  if (i < L.sel.src.n) {
     const uint64_t s = L.slot[i];
     keep = s != LAT_NONE && *lat_word(L, s, 2) == i + 1;
   }
-  const uint64_t b = __ballot(keep);
-  const uint32_t wv = threadIdx.x >> 6;
-  if (lane_id() == 0) {
-    P.mask[i >> 6] = b;  // (as sel_count_kernel: the scratch covers whole workgroups)
-    wcnt[wv] = (uint32_t)__popcll(b);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t s = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < SEL_WAVES; k++) s += wcnt[k];
-    P.block_cnt[blockIdx.x] = s;
-  }
+  sel_publish(L.sel, keep);
 }
 
 }  // namespace drp
@@ -155,13 +137,11 @@ extern "C" uint64_t drp_latest_scratch_bytes(uint64_t n) {
   return lat_al(drp_select_scratch_bytes(n)) + lat_al(n * 8) + lat_nslots(n) * 24;
 }
 
-extern "C" void drp_dbg_mark(const char *name, hipStream_t st);  // (drp_api.hip: DRP_WATCHDOG)
-
 extern "C" hipError_t drp_launch_latest(const SelectParams *Pp, const SelectBytes *fb, uint64_t hash_mask,
                                         void *scratch, hipStream_t st) {
   LatestParams L;
   L.sel = *Pp;
-  const uint64_t n = L.sel.n;
+  const uint64_t n = L.sel.src.n;
   if (n == 0) return hipMemsetAsync(L.sel.n_selected, 0, 8, st);
   if (const hipError_t e = drp_select_place(&L.sel, fb, scratch, st)) return e;
   uint8_t *sc = static_cast<uint8_t *>(scratch) + lat_al(drp_select_scratch_bytes(n));

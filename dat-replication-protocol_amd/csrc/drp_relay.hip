@@ -1,0 +1,356 @@
+// drp_relay.hip — the relay entry points of libdrp (include/drp.h): drp_select_device and
+// drp_latest_device over the caller's decoded columns, drp_relay_staged and drp_latest_staged over
+// the batch last staged (select or latest per key, then the encoder with the staged wire as its
+// heap), and drp_fanout_device / drp_fanout_staged (many filters over one pass). The kernels are in
+// drp_select.hip, drp_latest.hip and drp_fanout.hip; the context is drp_api.hip's (drp_ctx.h).
+#include <algorithm>
+#include <cstring>
+
+#include "drp_ctx.h"
+#include "drp_kernels.h"
+
+using namespace drp;
+
+// the decoded columns and the caller's row arrays are all there (n > 0)
+static bool rows_ok(const drp_frames *frames, const drp_changes *cols, const drp_change_src *out_rows, uint64_t n) {
+  return !n || (frames->payload_off && frames->type && cols->key_off && cols->key_len && cols->subset_off &&
+                cols->subset_len && cols->value_off && cols->value_len && cols->change && cols->from && cols->to &&
+                cols->flags && out_rows->key_off && out_rows->key_len && out_rows->subset_off &&
+                out_rows->subset_len && out_rows->value_off && out_rows->value_len && out_rows->change &&
+                out_rows->from && out_rows->to && out_rows->flags);
+}
+
+// drp_filter -> the kernels' filter record and its byte strings (fb: FAN_FBYTES bytes, zeroed by the
+// caller). DRP_E_INVAL: unknown bits, EQ together with NONE, a string longer than
+// DRP_SEL_MAX_BYTES or missing
+static int select_filter(const drp_filter *f, RowFilter &F, uint8_t *fb) {
+  F = RowFilter{0, 0, 0, 0, 0, ~0ull};
+  if (!f) return DRP_OK;
+  if (f->flags & ~drp_select_known_flags()) return DRP_E_INVAL;
+  if ((f->flags & DRP_SEL_SUBSET_EQ) && (f->flags & DRP_SEL_SUBSET_NONE)) return DRP_E_INVAL;
+  F.flags = f->flags;
+  if (f->flags & DRP_SEL_CHANGE_RANGE) {
+    F.change_min = f->change_min;
+    F.change_max = f->change_max;
+  }
+  if (f->flags & DRP_SEL_SUBSET_EQ) {
+    if (f->subset_len > DRP_SEL_MAX_BYTES || (f->subset_len && !f->subset)) return DRP_E_INVAL;
+    F.subset_len = f->subset_len;
+    if (f->subset_len) memcpy(fb, f->subset, f->subset_len);
+  }
+  if (f->flags & DRP_SEL_KEY_PREFIX) {
+    if (f->key_prefix_len > DRP_SEL_MAX_BYTES || (f->key_prefix_len && !f->key_prefix)) return DRP_E_INVAL;
+    F.prefix_len = f->key_prefix_len;
+    if (f->key_prefix_len) memcpy(fb + DRP_SEL_MAX_BYTES, f->key_prefix, f->key_prefix_len);
+  }
+  return DRP_OK;
+}
+
+// the caller's decoded columns as the kernels' row source
+static RowSrc caller_src(const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames, const drp_changes *cols,
+                         uint64_t n) {
+  RowSrc R = {};
+  R.bytes = bytes;
+  R.nbytes = nbytes;
+  R.payload_off = frames->payload_off;
+  R.type = frames->type;
+  R.cols = *cols;
+  R.n = n;
+  return R;
+}
+
+// the staged batch's delivered GPU rows as the kernels' row source. A piece's payload offsets are
+// relative to the batch offset it was staged at, and the staged bytes start at batch offset S.base
+// (a leading blob continuation never reaches the device): the table of several pieces goes to
+// piece_dev (2 * pieces words of device memory) through c->host_tmp
+static int staged_src(drp_ctx *c, RowSrc &R, uint64_t *piece_dev) {
+  const auto &S = c->staged;
+  const uint64_t np = S.pieces.size();
+  R = caller_src(S.wire, S.wire_bytes, &S.fr, &S.co, S.good);
+  if (np > 1) {
+    std::vector<uint64_t> &h = c->host_tmp;
+    h.resize(2 * np);
+    for (uint64_t k = 0; k < np; k++) {
+      h[k] = S.pieces[k].first;
+      h[np + k] = S.pieces[k].second - S.base;
+    }
+    CHK(hipMemcpyAsync(piece_dev, h.data(), 2 * np * 8, hipMemcpyHostToDevice, c->st));
+    R.piece_row = piece_dev;
+    R.piece_shift = piece_dev + np;
+    R.npieces = np;
+  } else {
+    R.shift0 = np ? S.pieces[0].second - S.base : 0;
+  }
+  return DRP_OK;
+}
+
+// ten row columns of `stride` bytes each out of buf, from byte o on
+static drp_change_src carve_rows(const DevBuf &buf, size_t o, size_t stride) {
+  auto take = [&]() { void *p = buf.at<char>(o); o += stride; return p; };
+  drp_change_src r;
+  r.key_off = (const uint64_t *)take();
+  r.key_len = (const uint32_t *)take();
+  r.subset_off = (const uint64_t *)take();
+  r.subset_len = (const uint32_t *)take();
+  r.value_off = (const uint64_t *)take();
+  r.value_len = (const uint32_t *)take();
+  r.change = (const uint64_t *)take();
+  r.from = (const uint64_t *)take();
+  r.to = (const uint64_t *)take();
+  r.flags = (const uint8_t *)take();
+  return r;
+}
+
+// (the row arrays are writable device memory behind drp_change_src's const pointers)
+static RowOut row_out(const drp_change_src *o, uint64_t *sel_idx) {
+  RowOut r;
+  r.o_key_off = const_cast<uint64_t *>(o->key_off);
+  r.o_key_len = const_cast<uint32_t *>(o->key_len);
+  r.o_subset_off = const_cast<uint64_t *>(o->subset_off);
+  r.o_subset_len = const_cast<uint32_t *>(o->subset_len);
+  r.o_value_off = const_cast<uint64_t *>(o->value_off);
+  r.o_value_len = const_cast<uint32_t *>(o->value_len);
+  r.o_change = const_cast<uint64_t *>(o->change);
+  r.o_from = const_cast<uint64_t *>(o->from);
+  r.o_to = const_cast<uint64_t *>(o->to);
+  r.o_flags = const_cast<uint8_t *>(o->flags);
+  r.sel_idx = sel_idx;
+  return r;
+}
+
+static uint64_t select_scratch(uint64_t n, bool latest) {
+  return latest ? drp_latest_scratch_bytes(n) : drp_select_scratch_bytes(n);
+}
+
+static hipError_t launch_select(drp_ctx *c, const SelectParams &P, const SelectBytes &fb, bool latest) {
+  return latest ? drp_launch_latest(&P, &fb, c->latest_hash_mask, c->scratch.p, c->st)
+                : drp_launch_select(&P, &fb, c->scratch.p, c->st);
+}
+
+// drp_select_device, or with `latest` drp_latest_device: the same arguments and checks
+static int select_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                         const drp_changes *cols, uint64_t n, const drp_filter *filter, const drp_change_src *out_rows,
+                         uint64_t *sel_idx, uint64_t *n_selected, bool latest) {
+  if (!c || !frames || !cols || !out_rows || !n_selected || (!bytes && nbytes)) return DRP_E_INVAL;
+  if (!rows_ok(frames, cols, out_rows, n)) return DRP_E_INVAL;
+  SelectParams P = {};
+  SelectBytes fb = {};
+  if (const int rc = select_filter(filter, P.f, fb.b)) return rc;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  // (the decode scratch: free between decodes, and every user is ordered on the ctx's stream)
+  if (!c->scratch.ensure(select_scratch(n, latest))) return DRP_E_NOMEM;
+  P.src = caller_src(bytes, nbytes, frames, cols, n);
+  P.out = row_out(out_rows, sel_idx);
+  P.n_selected = n_selected;
+  CHK(launch_select(c, P, fb, latest));
+  return DRP_OK;
+}
+
+// drp_relay_staged, or with `latest` drp_latest_staged: the latest-per-key step in the select's place
+static int relay_staged(drp_ctx *c, const drp_filter *filter, uint8_t *out, uint64_t cap, uint64_t *written,
+                        uint64_t *n_selected, bool latest) {
+  if (!c || !written || !n_selected || (!out && cap)) return DRP_E_INVAL;
+  const auto &S = c->staged;
+  if (!S.valid) return DRP_E_INVAL;
+  SelectParams P = {};
+  SelectBytes fb = {};
+  if (const int rc = select_filter(filter, P.f, fb.b)) return rc;
+  *written = 0;
+  *n_selected = 0;
+  const uint64_t n = S.good;  // the delivered GPU rows (a carried blob's row 0 is built on the host)
+  if (!n) return DRP_OK;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  // scratch (the decode's, free until the next decode): the kernel's words, the count, the piece
+  // table, the selected rows' columns
+  const size_t o_cnt = al(select_scratch(n, latest)), o_piece = o_cnt + 256,
+               o_rows = o_piece + al(2 * S.pieces.size() * 8), col = al(n * 8);
+  if (!c->scratch.ensure(o_rows + 10 * col)) return DRP_E_NOMEM;
+  uint64_t *dcnt = c->scratch.at<uint64_t>(o_cnt);
+  const drp_change_src rows = carve_rows(c->scratch, o_rows, col);
+  if (const int rc = staged_src(c, P.src, c->scratch.at<uint64_t>(o_piece))) return rc;
+  P.out = row_out(&rows, nullptr);
+  P.n_selected = dcnt;
+  CHK(launch_select(c, P, fb, latest));
+  uint64_t nsel = 0;
+  CHK(hipMemcpyAsync(&nsel, dcnt, 8, hipMemcpyDeviceToHost, c->st));
+  CHK(hipStreamSynchronize(c->st));  // (the one readback that sizes the encode)
+  *n_selected = nsel;
+  return drp_encode_batch(c, &rows, S.wire, S.wire_bytes, nsel, out, cap, written);
+}
+
+// ---- fan-out ------------------------------------------------------------------------------------
+// The filters, checked as select_filter checks one, into c->host_tmp in the device table's layout:
+// nfilters records, then every filter's byte strings at FAN_FBYTES steps. (Checked there first: a bad
+// filter leaves the page-locked table alone.)
+static size_t fanout_table_bytes(uint32_t K) { return al((size_t)K * sizeof(RowFilter)) + (size_t)K * FAN_FBYTES; }
+
+static int fanout_filters(drp_ctx *c, const drp_filter *filters, uint32_t K, FanParams &P) {
+  if (!filters || K == 0 || K > DRP_FANOUT_MAX) return DRP_E_INVAL;
+  std::vector<uint64_t> &h = c->host_tmp;
+  h.assign((fanout_table_bytes(K) + 7) / 8, 0);
+  RowFilter *tab = reinterpret_cast<RowFilter *>(h.data());
+  uint8_t *fbytes = reinterpret_cast<uint8_t *>(h.data()) + al((size_t)K * sizeof(RowFilter));
+  P.nfilters = K;
+  P.any_flags = P.any_bytes = 0;
+  for (uint32_t f = 0; f < K; f++) {
+    if (const int rc = select_filter(&filters[f], tab[f], fbytes + (size_t)f * FAN_FBYTES)) return rc;
+    P.any_flags |= tab[f].flags;
+    P.any_bytes |= filter_bytes(tab[f]);
+  }
+  return DRP_OK;
+}
+
+// (after the scratch is placed) the checked table of fanout_filters to the device. It travels by one
+// asynchronous copy out of the ctx's page-locked table, so before that is rewritten the copy of the
+// previous call must have read it.
+static int fanout_send_filters(drp_ctx *c, const FanParams &P) {
+  const size_t total = fanout_table_bytes(P.nfilters);
+  if (!c->fan_ev && hipEventCreateWithFlags(&c->fan_ev, hipEventDisableTiming) != hipSuccess) return DRP_E_HIP;
+  CHK(hipEventSynchronize(c->fan_ev));  // (never recorded: returns at once)
+  if (!c->fan_tab.ensure(total)) return DRP_E_NOMEM;
+  memcpy(c->fan_tab.p, c->host_tmp.data(), total);
+  // (filt is the scratch's first byte and the byte strings follow at the same offset as in the table)
+  CHK(hipMemcpyAsync(const_cast<RowFilter *>(P.filt), c->fan_tab.p, total, hipMemcpyHostToDevice, c->st));
+  CHK(hipEventRecord(c->fan_ev, c->st));
+  return DRP_OK;
+}
+
+extern "C" {
+
+int drp_select_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                      const drp_changes *cols, uint64_t n, const drp_filter *filter, const drp_change_src *out_rows,
+                      uint64_t *sel_idx, uint64_t *n_selected) {
+  return select_device(c, bytes, nbytes, frames, cols, n, filter, out_rows, sel_idx, n_selected, false);
+}
+
+int drp_latest_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                      const drp_changes *cols, uint64_t n, const drp_filter *filter, const drp_change_src *out_rows,
+                      uint64_t *sel_idx, uint64_t *n_selected) {
+  return select_device(c, bytes, nbytes, frames, cols, n, filter, out_rows, sel_idx, n_selected, true);
+}
+
+int drp_relay_staged(drp_ctx *c, const drp_filter *filter, uint8_t *out, uint64_t cap, uint64_t *written,
+                     uint64_t *n_selected) {
+  return relay_staged(c, filter, out, cap, written, n_selected, false);
+}
+
+int drp_latest_staged(drp_ctx *c, const drp_filter *filter, uint8_t *out, uint64_t cap, uint64_t *written,
+                      uint64_t *n_selected) {
+  return relay_staged(c, filter, out, cap, written, n_selected, true);
+}
+
+int drp_fanout_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                      const drp_changes *cols, uint64_t n, const drp_filter *filters, uint32_t nfilters,
+                      const drp_change_src *out_rows, uint64_t rows_cap, uint64_t *sel_idx, uint64_t *row_base,
+                      const drp_splice *splice) {
+  if (!c || !frames || !cols || !out_rows || !row_base || (!bytes && nbytes)) return DRP_E_INVAL;
+  if (!rows_ok(frames, cols, out_rows, n)) return DRP_E_INVAL;
+  if (splice && (!splice->n_blobs || (splice->blob_cap && (!splice->blob_row || !splice->blob_rank)))) return DRP_E_INVAL;
+  FanParams P = {};
+  if (const int rc = fanout_filters(c, filters, nfilters, P)) return rc;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  // (the decode scratch: free between decodes, and every user is ordered on the ctx's stream)
+  if (!c->scratch.ensure(drp_fanout_scratch_bytes(n, nfilters))) return DRP_E_NOMEM;
+  P.src = caller_src(bytes, nbytes, frames, cols, n);
+  drp_fanout_place(&P, c->scratch.p);
+  P.out = row_out(out_rows, sel_idx);
+  P.rows_cap = rows_cap;
+  P.row_base = row_base;
+  if (const int rc = fanout_send_filters(c, P)) return rc;
+  CHK(drp_launch_fanout_count(&P, c->st));
+  CHK(drp_launch_fanout_scatter(&P, c->st));
+  if (splice) {
+    P.blob_row = splice->blob_row;
+    P.blob_rank = splice->blob_rank;
+    P.n_blobs = splice->n_blobs;
+    P.blob_cap = splice->blob_cap;
+    CHK(drp_launch_fanout_splice(&P, c->st));
+  }
+  return DRP_OK;
+}
+
+int drp_fanout_staged(drp_ctx *c, const drp_filter *filters, uint32_t nfilters, uint8_t *out, uint64_t cap,
+                      uint64_t *out_off, uint64_t *n_selected, uint64_t *blob_row, uint64_t *blob_pos,
+                      uint64_t blob_cap, uint64_t *n_blobs) {
+  if (!c || !out_off || !n_selected || (!out && cap)) return DRP_E_INVAL;
+  if (blob_row ? (!n_blobs || (!blob_pos && blob_cap)) : (n_blobs != nullptr)) return DRP_E_INVAL;
+  const auto &S = c->staged;
+  if (!S.valid) return DRP_E_INVAL;
+  FanParams P = {};
+  if (const int rc = fanout_filters(c, filters, nfilters, P)) return rc;
+  const uint32_t K = nfilters;
+  for (uint32_t f = 0; f <= K; f++) out_off[f] = 0;
+  for (uint32_t f = 0; f < K; f++) n_selected[f] = 0;
+  if (n_blobs) *n_blobs = 0;
+  const uint64_t n = S.good;  // the delivered GPU rows (a carried blob's row 0 is built on the host)
+  if (!n) return DRP_OK;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  hipStream_t st = c->st;
+  // scratch (the decode's, free until the next decode): the kernels' words, row_base with the grand
+  // total and the splice kernel's blob count behind it, the piece table
+  const size_t o_base = al(drp_fanout_scratch_bytes(n, K)), o_piece = o_base + al((K + 3) * 8);
+  if (!c->scratch.ensure(o_piece + al(2 * S.pieces.size() * 8))) return DRP_E_NOMEM;
+  P.src.n = n;
+  drp_fanout_place(&P, c->scratch.p);
+  uint64_t *drb = c->scratch.at<uint64_t>(o_base);
+  P.row_base = drb;
+  P.gtotal = drb + K + 1;  // (one readback brings the outputs' bounds and the blob count)
+  if (const int rc = fanout_send_filters(c, P)) return rc;
+  // (c->host_tmp's filter table has been copied out: the piece table may pass through it)
+  if (const int rc = staged_src(c, P.src, c->scratch.at<uint64_t>(o_piece))) return rc;
+  CHK(drp_launch_fanout_count(&P, st));
+  uint64_t rb[DRP_FANOUT_MAX + 2];
+  CHK(hipMemcpyAsync(rb, drb, (K + 2) * 8, hipMemcpyDeviceToHost, st));
+  CHK(hipStreamSynchronize(st));  // (the one readback that sizes the rows and the encode)
+  const uint64_t total = rb[K], nb_true = rb[K + 1] - rb[K];
+  for (uint32_t f = 0; f < K; f++) n_selected[f] = rb[f + 1] - rb[f];
+  if (n_blobs) *n_blobs = nb_true;
+  const uint64_t nb = (blob_row && nb_true <= blob_cap) ? nb_true : 0;  // the splice entries to produce
+  // the selected rows (sized from the true total) and the splice kernel's outputs
+  const size_t col = al(total * 8), o_brow = 10 * col, o_rank = o_brow + al(nb * 8);
+  if (!c->fan_rows.ensure(o_rank + al((size_t)K * nb * 8) + 256)) return DRP_E_NOMEM;
+  const drp_change_src rows = carve_rows(c->fan_rows, 0, col);
+  P.out = row_out(&rows, nullptr);
+  P.rows_cap = total;
+  CHK(drp_launch_fanout_scatter(&P, st));
+  uint64_t *drank = c->fan_rows.at<uint64_t>(o_rank);
+  if (nb) {
+    P.blob_row = c->fan_rows.at<uint64_t>(o_brow);
+    P.blob_rank = drank;
+    P.n_blobs = drb + K + 2;  // (a word of its own: the grand total is still read by the kernel)
+    P.blob_cap = nb;
+    P.row_bias = S.nf0;
+    CHK(drp_launch_fanout_splice(&P, st));
+  }
+  // one encode of all outputs; its bytes go to `out` or, for a host `out`, to the output staging,
+  // which need not be larger than the outputs can get (none is longer than the staged wire)
+  const bool odev = is_device_ptr(out);
+  uint64_t nonempty = 0;
+  for (uint32_t f = 0; f < K; f++) nonempty += n_selected[f] != 0;
+  const uint64_t dcap = odev ? cap : std::min<uint64_t>(cap, nonempty * S.wire_bytes);
+  const size_t o_gat = al((total + 1) * 8), gat_n = (size_t)K + 1 + (size_t)K * nb, o_out = o_gat + al(gat_n * 8);
+  if (!c->out_stage.ensure(o_out + (odev ? 0 : dcap + 64))) return DRP_E_NOMEM;
+  uint64_t *foff = c->out_stage.at<uint64_t>(0), *dgat = c->out_stage.at<uint64_t>(o_gat);
+  uint8_t *dout = odev ? out : c->out_stage.at<uint8_t>(o_out);
+  if (const int rc = drp_encode_device(c, &rows, S.wire, S.wire_bytes, total, foff, dout, dcap)) return rc;
+  // the outputs' bounds and the blobs' byte positions, gathered into one block for one readback
+  CHK(drp_launch_fanout_gather(foff, drb, K, drank, nb, dgat, dgat + K + 1, st));
+  std::vector<uint64_t> &h = c->host_tmp;
+  h.resize(gat_n + nb);
+  CHK(hipMemcpyAsync(h.data(), dgat, gat_n * 8, hipMemcpyDeviceToHost, st));
+  if (nb) CHK(hipMemcpyAsync(h.data() + gat_n, P.blob_row, nb * 8, hipMemcpyDeviceToHost, st));
+  CHK(hipStreamSynchronize(st));
+  if (h[K] == ~0ull) return DRP_E_INVAL;  // a row's key/subset/value range is outside the wire
+  for (uint32_t f = 0; f <= K; f++) out_off[f] = h[f];
+  if (h[K] > cap) return DRP_E_CAPACITY;
+  for (uint64_t j = 0; j < nb; j++) blob_row[j] = h[gat_n + j];
+  for (uint32_t f = 0; f < K && nb; f++)
+    memcpy(blob_pos + (uint64_t)f * blob_cap, h.data() + K + 1 + (uint64_t)f * nb, nb * 8);
+  if (!odev && h[K]) {
+    CHK(hipMemcpyAsync(out, dout, h[K], hipMemcpyDeviceToHost, st));
+    CHK(hipStreamSynchronize(st));
+  }
+  return DRP_OK;
+}
+
+}  // extern "C"

@@ -12,7 +12,7 @@
 // the order of the rows is kept. The columns are read one 1 / 4 / 8-byte element per lane,
 // consecutive lanes consecutive elements; step (1) reads only the columns the filter names and
 // step (3) only the rows kept (the byte compares read wire bytes only of rows whose lengths match).
-#include "drp_select.h"  // (the predicate: sel_pred, sel_shift, SEL_BLK)
+#include "drp_select.h"  // (sel_pred, sel_publish, row_load / row_store, SEL_BLK)
 
 namespace drp {
 
@@ -26,22 +26,8 @@ __global__ __launch_bounds__(2 * DRP_SEL_MAX_BYTES) void sel_filter_kernel(const
 
 // (1) the ballot word of every 64 rows and the rows kept per workgroup
 __global__ __launch_bounds__(SEL_BLK) void sel_count_kernel(const SelectParams P) {
-  __shared__ uint32_t wcnt[SEL_WAVES];
   const uint64_t i = (uint64_t)blockIdx.x * SEL_BLK + threadIdx.x;
-  const bool keep = i < P.n && sel_pred(P, i);
-  const uint64_t b = __ballot(keep);
-  const uint32_t wv = threadIdx.x >> 6;
-  if (lane_id() == 0) {
-    P.mask[i >> 6] = b;  // (i >> 6 < ceil(n / 64) rounded up to the workgroup: the scratch covers it)
-    wcnt[wv] = (uint32_t)__popcll(b);
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t s = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < SEL_WAVES; k++) s += wcnt[k];
-    P.block_cnt[blockIdx.x] = s;
-  }
+  sel_publish(P, i < P.src.n && sel_pred(P, i));
 }
 
 // (2) exclusive scan of the workgroup counts in place (any number of them: SEL_BLK per round with
@@ -82,19 +68,7 @@ __global__ __launch_bounds__(SEL_BLK) void sel_scatter_kernel(const SelectParams
   uint64_t slot = P.block_cnt[blockIdx.x];
   for (uint32_t k = 0; k < wv; k++) slot += wcnt[k];
   slot += (uint32_t)__popcll(b & ((1ull << lane) - 1ull));
-  const drp_changes &c = P.cols;
-  const uint64_t base = P.payload_off[i] + sel_shift(P, i);
-  P.o_key_off[slot] = base + c.key_off[i];
-  P.o_key_len[slot] = c.key_len[i];
-  P.o_subset_off[slot] = base + c.subset_off[i];
-  P.o_subset_len[slot] = c.subset_len[i];
-  P.o_value_off[slot] = base + c.value_off[i];
-  P.o_value_len[slot] = c.value_len[i];
-  P.o_change[slot] = c.change[i];
-  P.o_from[slot] = c.from[i];
-  P.o_to[slot] = c.to[i];
-  P.o_flags[slot] = (uint8_t)(c.flags[i] & (DRP_F_SUBSET | DRP_F_VALUE));
-  if (P.sel_idx) P.sel_idx[slot] = i;
+  row_store(P.out, slot, row_load(P.src, i), i);
 }
 
 }  // namespace drp
@@ -111,17 +85,15 @@ extern "C" uint64_t drp_select_scratch_bytes(uint64_t n) {
   return 2 * DRP_SEL_MAX_BYTES + sel_mask_bytes(n) + sel_nblk(n) * 8 + 256;
 }
 
-extern "C" void drp_dbg_mark(const char *name, hipStream_t st);  // (drp_api.hip: DRP_WATCHDOG)
-
 // P's scratch pointers into `scratch` and the filter's byte strings onto the device (n > 0)
 extern "C" hipError_t drp_select_place(SelectParams *P, const SelectBytes *fb, void *scratch, hipStream_t st) {
-  if (sel_nblk(P->n) >= (1ull << 31)) return hipErrorInvalidValue;
+  if (sel_nblk(P->src.n) >= (1ull << 31)) return hipErrorInvalidValue;
   uint8_t *sc = static_cast<uint8_t *>(scratch);
   P->subset = sc;
   P->prefix = sc + DRP_SEL_MAX_BYTES;
   P->mask = reinterpret_cast<uint64_t *>(sc + 2 * DRP_SEL_MAX_BYTES);
-  P->block_cnt = reinterpret_cast<uint64_t *>(sc + 2 * DRP_SEL_MAX_BYTES + sel_mask_bytes(P->n));
-  if (P->fflags & (DRP_SEL_SUBSET_EQ | DRP_SEL_KEY_PREFIX))
+  P->block_cnt = reinterpret_cast<uint64_t *>(sc + 2 * DRP_SEL_MAX_BYTES + sel_mask_bytes(P->src.n));
+  if (P->f.flags & (DRP_SEL_SUBSET_EQ | DRP_SEL_KEY_PREFIX))
     hipLaunchKernelGGL(sel_filter_kernel, dim3(1), dim3(2 * DRP_SEL_MAX_BYTES), 0, st, *fb, sc);
   return hipSuccess;
 }
@@ -129,7 +101,7 @@ extern "C" hipError_t drp_select_place(SelectParams *P, const SelectBytes *fb, v
 // steps (2) and (3) over the ballot words and workgroup counts a step (1) has left in P's scratch
 extern "C" hipError_t drp_launch_select_compact(const SelectParams *Pp, hipStream_t st) {
   const SelectParams &P = *Pp;
-  const uint64_t nblk = sel_nblk(P.n);
+  const uint64_t nblk = sel_nblk(P.src.n);
   hipLaunchKernelGGL(sel_scan_kernel, dim3(1), dim3(SEL_BLK), 0, st, P, nblk);
   hipLaunchKernelGGL(sel_scatter_kernel, dim3((uint32_t)nblk), dim3(SEL_BLK), 0, st, P);
   return hipGetLastError();
@@ -137,9 +109,9 @@ extern "C" hipError_t drp_launch_select_compact(const SelectParams *Pp, hipStrea
 
 extern "C" hipError_t drp_launch_select(const SelectParams *Pp, const SelectBytes *fb, void *scratch, hipStream_t st) {
   SelectParams P = *Pp;
-  if (P.n == 0) return hipMemsetAsync(P.n_selected, 0, 8, st);
+  if (P.src.n == 0) return hipMemsetAsync(P.n_selected, 0, 8, st);
   if (const hipError_t e = drp_select_place(&P, fb, scratch, st)) return e;
-  hipLaunchKernelGGL(sel_count_kernel, dim3((uint32_t)sel_nblk(P.n)), dim3(SEL_BLK), 0, st, P);
+  hipLaunchKernelGGL(sel_count_kernel, dim3((uint32_t)sel_nblk(P.src.n)), dim3(SEL_BLK), 0, st, P);
   const hipError_t e = drp_launch_select_compact(&P, st);  // (the last error of all the launches)
   drp_dbg_mark("select", st);
   return e;
