@@ -261,6 +261,12 @@ int drp_set_latest_hash_mask(drp_ctx *c, uint64_t mask) {
   return DRP_OK;
 }
 
+int drp_set_fanout_latest_pass(drp_ctx *c, uint32_t filters_per_pass) {
+  if (!c) return DRP_E_INVAL;
+  c->fanout_latest_pass = filters_per_pass;
+  return DRP_OK;
+}
+
 // scratch layout for a decode of `nbytes` over `ns` streams
 struct DecLayout {
   uint64_t ntiles_max;

@@ -457,6 +457,15 @@ __device__ __forceinline__ uint32_t wave_incl_scan32(uint32_t v) {
   }
   return v;
 }
+__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v) {
+  const uint32_t lane = lane_id();
+#pragma unroll
+  for (uint32_t d = 1; d < WAVE; d <<= 1) {
+    const uint64_t t = shfl_up64(v, d);
+    if (lane >= d) v += t;
+  }
+  return v;
+}
 __device__ __forceinline__ uint64_t wave_sum64(uint64_t v) {
 #pragma unroll
   for (uint32_t m = 1; m < WAVE; m <<= 1) {

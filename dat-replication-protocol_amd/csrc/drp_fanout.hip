@@ -25,8 +25,7 @@
 
 namespace drp {
 
-constexpr uint32_t FAN_BLK = 1024, FAN_WAVES = FAN_BLK / 64, FAN_RPL = 4;
-constexpr uint32_t FAN_ROWS = FAN_BLK * FAN_RPL, FAN_CHUNKS = FAN_ROWS / 64;  // 64 ballot words per workgroup
+// (FAN_BLK, FAN_WAVES, FAN_RPL, FAN_ROWS, FAN_CHUNKS: drp_select.h)
 constexpr uint32_t FAN_SCAN = 1024;                                            // counts per first-level scan block
 constexpr uint32_t FAN_PLANES = DRP_FANOUT_MAX + 1;                            // the filters and the blob rows
 static_assert(FAN_CHUNKS == 64, "fan_prefix scans one ballot word per lane");
@@ -90,16 +89,6 @@ __global__ __launch_bounds__(FAN_BLK) void fan_count_kernel(const FanParams P) {
     for (uint32_t k = 0; k < FAN_WAVES; k++) s += wcnt[threadIdx.x][k];
     P.block_cnt[(uint64_t)threadIdx.x * P.nwg + blockIdx.x] = s;
   }
-}
-
-__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v) {
-  const uint32_t lane = lane_id();
-#pragma unroll
-  for (uint32_t d = 1; d < WAVE; d <<= 1) {
-    const uint64_t t = shfl_up64(v, d);
-    if (lane >= d) v += t;
-  }
-  return v;
 }
 
 // the sum of a value over the workgroup (every thread gets it); ws: FAN_WAVES words of LDS
@@ -267,20 +256,32 @@ extern "C" void drp_fanout_place(FanParams *P, void *scratch) {
   P->nwords = P->nwg * FAN_CHUNKS;
 }
 
-extern "C" hipError_t drp_launch_fanout_count(const FanParams *Pp, hipStream_t st) {
+extern "C" hipError_t drp_launch_fanout_ballot(const FanParams *Pp, hipStream_t st) {
+  const FanParams &P = *Pp;
+  if (P.src.n == 0) return hipSuccess;
+  if (P.nwg >= (1ull << 31) / FAN_PLANES) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(fan_count_kernel, dim3((uint32_t)P.nwg), dim3(FAN_BLK), 0, st, P);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t drp_launch_fanout_scan(const FanParams *Pp, hipStream_t st) {
   const FanParams &P = *Pp;
   if (P.src.n == 0) {  // no rows: every output and the blob list are empty
     hipError_t e = hipMemsetAsync(P.row_base, 0, ((size_t)P.nfilters + 1) * 8, st);
     if (e == hipSuccess) e = hipMemsetAsync(P.gtotal, 0, 8, st);
     return e;
   }
-  if (P.nwg >= (1ull << 31) / FAN_PLANES) return hipErrorInvalidValue;
   const uint64_t m = ((uint64_t)P.nfilters + 1) * P.nwg, nb = (m + FAN_SCAN - 1) / FAN_SCAN;
-  hipLaunchKernelGGL(fan_count_kernel, dim3((uint32_t)P.nwg), dim3(FAN_BLK), 0, st, P);
   hipLaunchKernelGGL(fan_blocksum_kernel, dim3((uint32_t)nb), dim3(FAN_SCAN), 0, st, P.block_cnt, m, P.bsum);
   hipLaunchKernelGGL(fan_scanbase_kernel, dim3((uint32_t)nb), dim3(FAN_SCAN), 0, st, P, m);
-  drp_dbg_mark("fanout_count", st);
   return hipGetLastError();
+}
+
+extern "C" hipError_t drp_launch_fanout_count(const FanParams *Pp, hipStream_t st) {
+  if (const hipError_t e = drp_launch_fanout_ballot(Pp, st)) return e;
+  const hipError_t e = drp_launch_fanout_scan(Pp, st);
+  if (Pp->src.n) drp_dbg_mark("fanout_count", st);
+  return e;
 }
 
 extern "C" hipError_t drp_launch_fanout_scatter(const FanParams *Pp, hipStream_t st) {

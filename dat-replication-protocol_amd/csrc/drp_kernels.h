@@ -163,18 +163,22 @@ struct SelectBytes {
   uint8_t b[FAN_FBYTES];
 };
 
+// drp_latest.hip's grouping table: nslots (a power of two >= 2 n) slots, all zero before the insert
+// step. A slot's first word is rep: hash tag | (the row that claimed the slot + 1)
+struct LatTable {
+  uint64_t *tab;
+  uint64_t nslots;
+  uint64_t hash_mask;  // ANDed with the row hash before the tag and the start slot are taken (test hook)
+  uint64_t tag_mask;   // rep's hash bits: the high 32 when n < 2^32 - 1 (rows fit the low 32), else none
+};
 // drp_latest.hip: the select's candidates grouped by (subset presence, subset bytes, key bytes) in
 // an insert-only open-addressing table, the row with the greatest (change, row) of every group kept
 struct LatestParams {
   SelectParams sel;  // the select's parameters: predicate, scratch and outputs as there
-  // table: nslots (a power of two >= 2 n) slots of three words, all zero before the insert step:
-  //   [0] rep: hash tag | (the row that claimed the slot + 1); [1] the greatest change of the
-  //   group; [2] the greatest row + 1 among those that carry it
-  uint64_t *tab;
-  uint64_t nslots;
-  uint64_t *slot;      // [n] the slot of row i's group, LAT_NONE for a row that is no candidate
-  uint64_t hash_mask;  // ANDed with the row hash before the tag and the start slot are taken (test hook)
-  uint64_t tag_mask;   // rep's hash bits: the high 32 when n < 2^32 - 1 (rows fit the low 32), else none
+  // slots of three words: [0] rep; [1] the greatest change of the group; [2] the greatest row + 1
+  // among those that carry it
+  LatTable t;
+  uint64_t *slot;  // [n] the slot of row i's group, LAT_NONE for a row that is no candidate
 };
 constexpr uint64_t LAT_NONE = ~0ull;
 
@@ -197,6 +201,25 @@ struct FanParams {
   uint64_t *blob_row, *blob_rank, *n_blobs;
   uint64_t blob_cap, row_bias;  // row_bias: added to every blob_row entry (rows the host put first)
 };
+
+// drp_latest.hip: latest per key under every filter of a fan-out. The rows some ballot plane keeps
+// are grouped once (slots of one word, rep) and the groups numbered densely, in the order of the rows
+// that claimed their slots; the planes are then reduced to their winners in passes of up to `pass`
+// filters [f0, f0 + nf)
+struct FanLatestParams {
+  FanParams fan;  // after fan_count: mask and block_cnt are read and rewritten
+  LatTable t;
+  uint64_t *group;  // [n] the slot of row i's group, then (flat_number) the group's number; LAT_NONE
+                    // for a row that is no candidate of any filter
+  uint64_t *lead, *lead_base;  // per 64 rows: the ballot of the rows that claimed a slot, and the
+                               // number of such rows before these 64
+  uint64_t *state;  // [groups <= n][nf][2], zero before a pass: the greatest change that filter f0 + k
+                    // keeps in the group, and the greatest row + 1 among those that carry it
+  uint32_t f0, nf;
+};
+// filters per pass by default: the pass state of one group (16 bytes per filter) is one 128-byte line,
+// and the state of a batch at most 128 bytes per row (DESIGN.md "Fan-out of latest per key")
+constexpr uint32_t FLAT_PASS_DEFAULT = 8;
 
 }  // namespace drp
 
@@ -275,6 +298,17 @@ uint64_t drp_fanout_scratch_bytes(uint64_t n, uint32_t nfilters);
 void drp_fanout_place(drp::FanParams *P, void *scratch);
 // count + scan: P->row_base[0 .. nfilters] and *P->gtotal (rows + blob rows) are written
 hipError_t drp_launch_fanout_count(const drp::FanParams *P, hipStream_t st);
+// its two halves: the ballot planes with their workgroup counts, and the scan of whatever counts
+// P's scratch holds (drp_launch_fanout_latest rewrites planes and counts in between)
+hipError_t drp_launch_fanout_ballot(const drp::FanParams *P, hipStream_t st);
+hipError_t drp_launch_fanout_scan(const drp::FanParams *P, hipStream_t st);
+// drp_latest.hip, between those two: every filter's plane and counts cut down to the plane's latest
+// row per key, `pass` filters (1 .. nfilters) per reduction pass. Scratch: the fan-out's
+// (drp_fanout_scratch_bytes, placed in P already), then group[n], the table's rep words, the claim
+// ballots and their scan, the pass state.
+uint64_t drp_fanout_latest_scratch_bytes(uint64_t n, uint32_t nfilters, uint32_t pass);
+hipError_t drp_launch_fanout_latest(const drp::FanParams *P, uint64_t hash_mask, uint32_t pass, void *scratch,
+                                    hipStream_t st);
 hipError_t drp_launch_fanout_scatter(const drp::FanParams *P, hipStream_t st);
 hipError_t drp_launch_fanout_splice(const drp::FanParams *P, hipStream_t st);
 // out_off[f] = frame_off[row_base[f]] (f <= nfilters); blob_pos[f * nb + j] = frame_off[row_base[f] +

@@ -27,12 +27,30 @@
 //               form sel_count_kernel leaves them, for the select's scan and scatter.
 // Which row claimed a slot and where a group landed decide nothing: every group's two maxima are
 // over the same rows whatever the order, and the kept rows leave in row order.
+//
+// The same for every filter of a fan-out (drp_fanout_latest_*): fan_count (drp_fanout.hip) has left
+// one ballot plane per filter; the grouping is done once, the reduction per filter, under the rule
+// above (the rep words and the state words through agent-scope atomics, the rest across kernel
+// boundaries):
+//   flat_group  lat_insert's probe (lat_group, one function, two callers) for every row that some
+//               plane keeps, over a table of rep words only; the row's slot, and per 64 rows the
+//               ballot of the rows whose swap claimed a slot: one row per group.
+//   flat_scan / flat_number   the groups numbered densely: a group's number is the rank of the row
+//               that claimed its slot among the rows that claimed one (a scan of the ballots; rep
+//               names the row); group[row] instead of the slot. The numbers depend on which rows
+//               won their swaps; nothing in the result does.
+//   flat_max / flat_pick / flat_keep   per pass of up to `pass` filters, over state words
+//               [group][filter of the pass][2] cleared before the pass: lat_insert's maximum, lat_pick
+//               and lat_keep for every filter of the pass per row, each behind the row's bit in the
+//               filter's plane; flat_keep overwrites the pass's planes and workgroup counts in the
+//               form fan_count left them, for the fan-out's scan and scatter.
 #include "drp_select.h"
 
 namespace drp {
 
-// the three words of slot s
-__device__ __forceinline__ uint64_t *lat_word(const LatestParams &L, uint64_t s, uint32_t w) { return L.tab + 3 * s + w; }
+// word w of slot s (W words per slot)
+template <uint32_t W>
+__device__ __forceinline__ uint64_t *lat_word(const LatTable &T, uint64_t s, uint32_t w) { return T.tab + W * s + w; }
 
 // wire bytes [a, a + len) == [b, b + len) (both ranges inside the wire)
 __device__ __forceinline__ bool lat_bytes_eq(const RowSrc &P, uint64_t a, uint64_t b, uint32_t len) {
@@ -59,44 +77,53 @@ __device__ __forceinline__ bool lat_same(const RowSrc &P, uint64_t j, bool has, 
   return !has || lat_bytes_eq(P, base + c.subset_off[j], soff, slen);
 }
 
+// The slot of row i's group (i: a well-formed Change that some predicate keeps), claimed by this row
+// or by an earlier visitor of the same identity; LAT_NONE for a row whose key or subset range leaves
+// the wire: it is never read and is no candidate. W: the table's words per slot. claimed: this row's
+// swap took the slot (one row per group sees that).
+template <uint32_t W>
+__device__ __forceinline__ uint64_t lat_group(const RowSrc &P, const LatTable &T, uint64_t i, bool &claimed) {
+  claimed = false;
+  const drp_changes &c = P.cols;
+  const bool has = (c.flags[i] & DRP_F_SUBSET) != 0;
+  const uint64_t base = P.payload_off[i] + row_shift(P, i);
+  const uint64_t koff = base + c.key_off[i], soff = base + c.subset_off[i];
+  const uint32_t klen = c.key_len[i], slen = has ? c.subset_len[i] : 0;
+  if (!wire_has(P, koff, klen) || (has && !wire_has(P, soff, slen))) return LAT_NONE;
+  uint64_t h = xxh::xxh64(P.bytes + koff, klen);
+  if (has) h = xxh::merge(h, xxh::xxh64(P.bytes + soff, slen));  // (an empty subset still changes h)
+  h &= T.hash_mask;
+  const uint64_t smask = T.nslots - 1, word = (h & T.tag_mask) | (i + 1);
+  uint64_t s = h & smask;
+  for (uint64_t step = 0; step < T.nslots; step++, s = (s + 1) & smask) {
+    // rep is written once, so an atomic load that finds it set saves the swap (a stale 0 only
+    // costs the swap, which leaves the word it found in `seen`)
+    uint64_t seen = ld_agent(lat_word<W>(T, s, 0));
+    if (seen == 0 && __hip_atomic_compare_exchange_strong(lat_word<W>(T, s, 0), &seen, word, __ATOMIC_RELAXED,
+                                                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+      claimed = true;
+      return s;
+    }
+    if (((seen ^ word) & T.tag_mask) == 0 && lat_same(P, (seen & ~T.tag_mask) - 1, has, koff, klen, soff, slen))
+      return s;
+  }
+  return LAT_NONE;  // (not reached: the table is at most half full)
+}
+
+// an atomic max of v into *p. The word only grows: a load that already shows v or more saves the
+// atomic (a stale, smaller value only costs it), which is what keeps a hot key's rows off one address
+__device__ __forceinline__ void lat_max(uint64_t *p, uint64_t v) {
+  if (ld_agent(p) < v) __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 __global__ __launch_bounds__(SEL_BLK) void lat_insert_kernel(const LatestParams L) {
-  const RowSrc &P = L.sel.src;
   const uint64_t i = (uint64_t)blockIdx.x * SEL_BLK + threadIdx.x;
-  if (i >= P.n) return;
+  if (i >= L.sel.src.n) return;
   uint64_t mine = LAT_NONE;
   if (sel_pred(L.sel, i)) {
-    const drp_changes &c = P.cols;
-    const bool has = (c.flags[i] & DRP_F_SUBSET) != 0;
-    const uint64_t base = P.payload_off[i] + row_shift(P, i);
-    const uint64_t koff = base + c.key_off[i], soff = base + c.subset_off[i];
-    const uint32_t klen = c.key_len[i], slen = has ? c.subset_len[i] : 0;
-    // a row whose key or subset range leaves the wire is never read and is no candidate
-    if (wire_has(P, koff, klen) && (!has || wire_has(P, soff, slen))) {
-      uint64_t h = xxh::xxh64(P.bytes + koff, klen);
-      if (has) h = xxh::merge(h, xxh::xxh64(P.bytes + soff, slen));  // (an empty subset still changes h)
-      h &= L.hash_mask;
-      const uint64_t smask = L.nslots - 1, word = (h & L.tag_mask) | (i + 1);
-      uint64_t s = h & smask;
-      for (uint64_t step = 0; step < L.nslots; step++, s = (s + 1) & smask) {
-        // rep is written once, so an atomic load that finds it set saves the swap (a stale 0 only
-        // costs the swap, which leaves the word it found in `seen`)
-        uint64_t seen = ld_agent(lat_word(L, s, 0));
-        if (seen == 0 && __hip_atomic_compare_exchange_strong(lat_word(L, s, 0), &seen, word, __ATOMIC_RELAXED,
-                                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-          mine = s;
-          break;
-        }
-        if (((seen ^ word) & L.tag_mask) == 0 && lat_same(P, (seen & ~L.tag_mask) - 1, has, koff, klen, soff, slen)) {
-          mine = s;
-          break;
-        }
-      }
-      // the maximum only grows: a load that already shows the row's change or more saves the atomic
-      // (a stale, smaller value only costs it), which is what keeps a hot key's rows off one address
-      const uint64_t ch = c.change[i];
-      if (mine != LAT_NONE && ld_agent(lat_word(L, mine, 1)) < ch)
-        __hip_atomic_fetch_max(lat_word(L, mine, 1), ch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    bool claimed;
+    mine = lat_group<3>(L.sel.src, L.t, i, claimed);
+    if (mine != LAT_NONE) lat_max(lat_word<3>(L.t, mine, 1), L.sel.src.cols.change[i]);
   }
   L.slot[i] = mine;
 }
@@ -107,8 +134,7 @@ __global__ __launch_bounds__(SEL_BLK) void lat_pick_kernel(const LatestParams L)
   const uint64_t s = L.slot[i];
   if (s == LAT_NONE) return;
   // (a group whose only change is 0 matches the cleared word)
-  if (L.sel.src.cols.change[i] == *lat_word(L, s, 1) && ld_agent(lat_word(L, s, 2)) < i + 1)  // (as lat_insert's maximum)
-    __hip_atomic_fetch_max(lat_word(L, s, 2), i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (L.sel.src.cols.change[i] == *lat_word<3>(L.t, s, 1)) lat_max(lat_word<3>(L.t, s, 2), i + 1);
 }
 
 // sel_count_kernel with the predicate "the row its group picked"
@@ -117,9 +143,130 @@ __global__ __launch_bounds__(SEL_BLK) void lat_keep_kernel(const LatestParams L)
   bool keep = false;
   if (i < L.sel.src.n) {
     const uint64_t s = L.slot[i];
-    keep = s != LAT_NONE && *lat_word(L, s, 2) == i + 1;
+    keep = s != LAT_NONE && *lat_word<3>(L.t, s, 2) == i + 1;
   }
   sel_publish(L.sel, keep);
+}
+
+// ---- latest per key under every filter of a fan-out -------------------------------------------
+// fan_count has left one ballot plane per filter, mask[f][row >> 6]. A row's wave reads a plane's
+// word of its 64 rows wave-uniformly; row i is in plane f iff bit i & 63 of that word is set (a bit
+// is only ever set for a well-formed Change below n).
+__device__ __forceinline__ uint64_t flat_plane(const FanParams &F, uint32_t f, uint64_t w) {
+  return F.mask[(uint64_t)f * F.nwords + w];
+}
+// the two words of (group g, filter k of the pass)
+__device__ __forceinline__ uint64_t *flat_state(const FanLatestParams &L, uint64_t g, uint32_t k) {
+  return L.state + (g * L.nf + k) * 2;
+}
+
+// the grouping, once for all filters: lat_insert's probe for every row that some plane keeps; the
+// row's slot, and per 64 rows the ballot of the rows that claimed theirs (one per group)
+__global__ __launch_bounds__(SEL_BLK) void flat_group_kernel(const FanLatestParams L) {
+  const FanParams &F = L.fan;
+  const uint64_t w = (uint64_t)blockIdx.x * SEL_WAVES + uniform32(threadIdx.x >> 6);
+  const uint64_t i = w * 64 + lane_id();
+  if (i >= F.src.n) return;
+  uint64_t any = 0;
+  for (uint32_t f = 0; f < F.nfilters; f++) any |= flat_plane(F, f, w);
+  bool claimed = false;
+  L.group[i] = ((any >> lane_id()) & 1ull) ? lat_group<1>(F.src, L.t, i, claimed) : LAT_NONE;
+  const uint64_t b = __ballot(claimed);
+  if (lane_id() == 0) L.lead[w] = b;
+}
+
+// exclusive scan of the m claim ballots' popcounts, one workgroup: every thread sums a run of
+// consecutive words, the runs' sums are scanned across the workgroup, every thread writes its run
+__global__ __launch_bounds__(SEL_BLK) void flat_scan_kernel(const FanLatestParams L, uint64_t m) {
+  __shared__ uint64_t part[SEL_WAVES];
+  const uint64_t per = (m + SEL_BLK - 1) / SEL_BLK, a = umin64(m, threadIdx.x * per), b = umin64(m, a + per);
+  uint64_t s = 0;
+  for (uint64_t g = a; g < b; g++) s += (uint64_t)__popcll(L.lead[g]);
+  const uint64_t incl = wave_incl_scan64(s);
+  const uint32_t wv = threadIdx.x >> 6;
+  if (lane_id() == 63) part[wv] = incl;
+  __syncthreads();
+  uint64_t run = incl - s;
+  for (uint32_t k = 0; k < wv; k++) run += part[k];
+  for (uint64_t g = a; g < b; g++) {
+    L.lead_base[g] = run;
+    run += (uint64_t)__popcll(L.lead[g]);
+  }
+}
+
+// group[row]: from the slot to the group's number, the rank of the row that claimed the slot among
+// the rows that claimed one (rep names that row; complete: a kernel boundary lies in between)
+__global__ __launch_bounds__(SEL_BLK) void flat_number_kernel(const FanLatestParams L) {
+  const uint64_t i = (uint64_t)blockIdx.x * SEL_BLK + threadIdx.x;
+  if (i >= L.fan.src.n) return;
+  const uint64_t s = L.group[i];
+  if (s == LAT_NONE) return;
+  const uint64_t r = (*lat_word<1>(L.t, s, 0) & ~L.t.tag_mask) - 1;
+  L.group[i] = L.lead_base[r >> 6] + (uint64_t)__popcll(L.lead[r >> 6] & ((1ull << (r & 63)) - 1ull));
+}
+
+// per pass, every filter of the pass per row: the greatest change the filter keeps in the row's group
+__global__ __launch_bounds__(SEL_BLK) void flat_max_kernel(const FanLatestParams L) {
+  const FanParams &F = L.fan;
+  const uint64_t w = (uint64_t)blockIdx.x * SEL_WAVES + uniform32(threadIdx.x >> 6);
+  const uint64_t i = w * 64 + lane_id();
+  if (i >= F.src.n) return;
+  const uint64_t s = L.group[i];
+  if (s == LAT_NONE) return;
+  const uint64_t ch = F.src.cols.change[i];
+  for (uint32_t k = 0; k < L.nf; k++)
+    if ((flat_plane(F, L.f0 + k, w) >> lane_id()) & 1ull) lat_max(flat_state(L, s, k), ch);
+}
+
+// the greatest row among those that carry that maximum (complete: a kernel boundary lies in between).
+// The plane bit is tested again: the cleared word equals a rejected row's change of 0
+__global__ __launch_bounds__(SEL_BLK) void flat_pick_kernel(const FanLatestParams L) {
+  const FanParams &F = L.fan;
+  const uint64_t w = (uint64_t)blockIdx.x * SEL_WAVES + uniform32(threadIdx.x >> 6);
+  const uint64_t i = w * 64 + lane_id();
+  if (i >= F.src.n) return;
+  const uint64_t s = L.group[i];
+  if (s == LAT_NONE) return;
+  const uint64_t ch = F.src.cols.change[i];
+  for (uint32_t k = 0; k < L.nf; k++)
+    if (((flat_plane(F, L.f0 + k, w) >> lane_id()) & 1ull) && ch == *flat_state(L, s, k))
+      lat_max(flat_state(L, s, k) + 1, i + 1);
+}
+
+// fan_count's geometry and outputs with the predicate "in the plane, and the row its group picked
+// under this filter": the pass's planes and their workgroup counts are overwritten (each ballot word
+// is read and rewritten by the one wave that owns its 64 rows)
+__global__ __launch_bounds__(FAN_BLK) void flat_keep_kernel(const FanLatestParams L) {
+  __shared__ uint32_t wcnt[DRP_FANOUT_MAX][FAN_WAVES];
+  const FanParams &F = L.fan;
+  const uint32_t wv = uniform32(threadIdx.x >> 6), lane = lane_id();
+  const uint64_t word0 = (uint64_t)blockIdx.x * FAN_CHUNKS + wv * FAN_RPL;  // (< nwords: the grid is nwg)
+  uint64_t s[FAN_RPL];
+#pragma unroll
+  for (uint32_t r = 0; r < FAN_RPL; r++) {
+    const uint64_t i = (word0 + r) * 64 + lane;
+    s[r] = i < F.src.n ? L.group[i] : LAT_NONE;
+  }
+  for (uint32_t k = 0; k < L.nf; k++) {  // (wave-uniform: nf is a launch argument)
+    uint64_t *mrow = F.mask + (uint64_t)(L.f0 + k) * F.nwords + word0;
+    uint32_t cnt = 0;
+#pragma unroll
+    for (uint32_t r = 0; r < FAN_RPL; r++) {
+      const uint64_t i = (word0 + r) * 64 + lane;
+      const bool keep = ((mrow[r] >> lane) & 1ull) && s[r] != LAT_NONE && flat_state(L, s[r], k)[1] == i + 1;
+      const uint64_t b = __ballot(keep);
+      if (lane == 0) mrow[r] = b;
+      cnt += (uint32_t)__popcll(b);
+    }
+    if (lane == 0) wcnt[k][wv] = cnt;
+  }
+  __syncthreads();
+  if (threadIdx.x < L.nf) {
+    uint32_t t = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < FAN_WAVES; j++) t += wcnt[threadIdx.x][j];
+    F.block_cnt[(uint64_t)(L.f0 + threadIdx.x) * F.nwg + blockIdx.x] = t;
+  }
 }
 
 }  // namespace drp
@@ -133,6 +280,18 @@ static uint64_t lat_nslots(uint64_t n) {
   while (c < 2 * n) c <<= 1;
   return c;
 }
+// the table for n rows at `at` (to be zeroed)
+static LatTable lat_table(void *at, uint64_t n, uint64_t hash_mask) {
+  LatTable T;
+  T.tab = static_cast<uint64_t *>(at);
+  T.nslots = lat_nslots(n);
+  T.hash_mask = hash_mask;
+  // rows below 2^32 - 1 leave rep's high half to 32 bits of the hash (most foreign slots are passed
+  // without a look at their row); beyond, rep is the row alone and every visit compares the rows
+  T.tag_mask = n < 0xFFFFFFFFull ? 0xFFFFFFFF00000000ull : 0;
+  return T;
+}
+
 extern "C" uint64_t drp_latest_scratch_bytes(uint64_t n) {
   return lat_al(drp_select_scratch_bytes(n)) + lat_al(n * 8) + lat_nslots(n) * 24;
 }
@@ -146,13 +305,8 @@ extern "C" hipError_t drp_launch_latest(const SelectParams *Pp, const SelectByte
   if (const hipError_t e = drp_select_place(&L.sel, fb, scratch, st)) return e;
   uint8_t *sc = static_cast<uint8_t *>(scratch) + lat_al(drp_select_scratch_bytes(n));
   L.slot = reinterpret_cast<uint64_t *>(sc);
-  L.tab = reinterpret_cast<uint64_t *>(sc + lat_al(n * 8));
-  L.nslots = lat_nslots(n);
-  L.hash_mask = hash_mask;
-  // rows below 2^32 - 1 leave rep's high half to 32 bits of the hash (most foreign slots are passed
-  // without a look at their row); beyond, rep is the row alone and every visit compares the rows
-  L.tag_mask = n < 0xFFFFFFFFull ? 0xFFFFFFFF00000000ull : 0;
-  if (const hipError_t e = hipMemsetAsync(L.tab, 0, L.nslots * 24, st)) return e;
+  L.t = lat_table(sc + lat_al(n * 8), n, hash_mask);
+  if (const hipError_t e = hipMemsetAsync(L.t.tab, 0, L.t.nslots * 24, st)) return e;
   const dim3 grid((uint32_t)((n + SEL_BLK - 1) / SEL_BLK)), blk(SEL_BLK);
   hipLaunchKernelGGL(lat_insert_kernel, grid, blk, 0, st, L);
   hipLaunchKernelGGL(lat_pick_kernel, grid, blk, 0, st, L);
@@ -160,4 +314,45 @@ extern "C" hipError_t drp_launch_latest(const SelectParams *Pp, const SelectByte
   const hipError_t e = drp_launch_select_compact(&L.sel, st);
   drp_dbg_mark("latest", st);
   return e;
+}
+
+static uint32_t flat_pass(uint32_t nfilters, uint32_t pass) { return pass == 0 || pass > nfilters ? nfilters : pass; }
+
+extern "C" uint64_t drp_fanout_latest_scratch_bytes(uint64_t n, uint32_t nfilters, uint32_t pass) {
+  const uint64_t words = lat_al((n + 63) / 64 * 8);
+  return lat_al(drp_fanout_scratch_bytes(n, nfilters)) + lat_al(n * 8) + lat_nslots(n) * 8 + 2 * words +
+         n * 16 * (uint64_t)flat_pass(nfilters, pass);
+}
+
+extern "C" hipError_t drp_launch_fanout_latest(const FanParams *Pp, uint64_t hash_mask, uint32_t pass, void *scratch,
+                                               hipStream_t st) {
+  FanLatestParams L;
+  L.fan = *Pp;
+  const uint64_t n = L.fan.src.n;
+  if (n == 0) return hipSuccess;
+  const uint32_t K = L.fan.nfilters;
+  pass = flat_pass(K, pass);
+  const uint64_t m = (n + 63) / 64, words = lat_al(m * 8);
+  uint8_t *sc = static_cast<uint8_t *>(scratch) + lat_al(drp_fanout_scratch_bytes(n, K));
+  L.group = reinterpret_cast<uint64_t *>(sc);
+  L.t = lat_table(sc + lat_al(n * 8), n, hash_mask);
+  L.lead = L.t.tab + L.t.nslots;
+  L.lead_base = L.lead + words / 8;
+  L.state = L.lead_base + words / 8;
+  if (const hipError_t e = hipMemsetAsync(L.t.tab, 0, L.t.nslots * 8, st)) return e;
+  const dim3 grid((uint32_t)((n + SEL_BLK - 1) / SEL_BLK)), blk(SEL_BLK);
+  L.f0 = L.nf = 0;
+  hipLaunchKernelGGL(flat_group_kernel, grid, blk, 0, st, L);
+  hipLaunchKernelGGL(flat_scan_kernel, dim3(1), blk, 0, st, L, m);
+  hipLaunchKernelGGL(flat_number_kernel, grid, blk, 0, st, L);
+  for (L.f0 = 0; L.f0 < K; L.f0 += pass) {
+    L.nf = K - L.f0 < pass ? K - L.f0 : pass;
+    // (the groups are at most n; how many there are stays on the device)
+    if (const hipError_t e = hipMemsetAsync(L.state, 0, n * L.nf * 16, st)) return e;
+    hipLaunchKernelGGL(flat_max_kernel, grid, blk, 0, st, L);
+    hipLaunchKernelGGL(flat_pick_kernel, grid, blk, 0, st, L);
+    hipLaunchKernelGGL(flat_keep_kernel, dim3((uint32_t)L.fan.nwg), dim3(FAN_BLK), 0, st, L);
+  }
+  drp_dbg_mark("fanout_latest", st);
+  return hipGetLastError();
 }

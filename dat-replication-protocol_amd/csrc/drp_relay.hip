@@ -1,7 +1,8 @@
 // drp_relay.hip — the relay entry points of libdrp (include/drp.h): drp_select_device and
 // drp_latest_device over the caller's decoded columns, drp_relay_staged and drp_latest_staged over
 // the batch last staged (select or latest per key, then the encoder with the staged wire as its
-// heap), and drp_fanout_device / drp_fanout_staged (many filters over one pass). The kernels are in
+// heap), drp_fanout_device / drp_fanout_staged (many filters over one pass) and
+// drp_fanout_latest_device / drp_fanout_latest_staged (latest per key under each). The kernels are in
 // drp_select.hip, drp_latest.hip and drp_fanout.hip; the context is drp_api.hip's (drp_ctx.h).
 #include <algorithm>
 #include <cstring>
@@ -215,34 +216,27 @@ static int fanout_send_filters(drp_ctx *c, const FanParams &P) {
   return DRP_OK;
 }
 
-extern "C" {
+// the fan-out's scratch and count step; with `latest` the planes are cut down to their latest row
+// per key between the ballots and the scan (drp_latest.hip)
+static uint32_t latest_pass(const drp_ctx *c) { return c->fanout_latest_pass ? c->fanout_latest_pass : FLAT_PASS_DEFAULT; }
 
-int drp_select_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
-                      const drp_changes *cols, uint64_t n, const drp_filter *filter, const drp_change_src *out_rows,
-                      uint64_t *sel_idx, uint64_t *n_selected) {
-  return select_device(c, bytes, nbytes, frames, cols, n, filter, out_rows, sel_idx, n_selected, false);
+static uint64_t fanout_scratch(const drp_ctx *c, uint64_t n, uint32_t K, bool latest) {
+  return latest ? drp_fanout_latest_scratch_bytes(n, K, latest_pass(c)) : drp_fanout_scratch_bytes(n, K);
 }
 
-int drp_latest_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
-                      const drp_changes *cols, uint64_t n, const drp_filter *filter, const drp_change_src *out_rows,
-                      uint64_t *sel_idx, uint64_t *n_selected) {
-  return select_device(c, bytes, nbytes, frames, cols, n, filter, out_rows, sel_idx, n_selected, true);
+static hipError_t launch_fanout_count(drp_ctx *c, const FanParams &P, bool latest) {
+  if (!latest) return drp_launch_fanout_count(&P, c->st);
+  if (const hipError_t e = drp_launch_fanout_ballot(&P, c->st)) return e;
+  if (const hipError_t e = drp_launch_fanout_latest(&P, c->latest_hash_mask, latest_pass(c), c->scratch.p, c->st))
+    return e;
+  return drp_launch_fanout_scan(&P, c->st);
 }
 
-int drp_relay_staged(drp_ctx *c, const drp_filter *filter, uint8_t *out, uint64_t cap, uint64_t *written,
-                     uint64_t *n_selected) {
-  return relay_staged(c, filter, out, cap, written, n_selected, false);
-}
-
-int drp_latest_staged(drp_ctx *c, const drp_filter *filter, uint8_t *out, uint64_t cap, uint64_t *written,
-                      uint64_t *n_selected) {
-  return relay_staged(c, filter, out, cap, written, n_selected, true);
-}
-
-int drp_fanout_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
-                      const drp_changes *cols, uint64_t n, const drp_filter *filters, uint32_t nfilters,
-                      const drp_change_src *out_rows, uint64_t rows_cap, uint64_t *sel_idx, uint64_t *row_base,
-                      const drp_splice *splice) {
+// drp_fanout_device, or with `latest` drp_fanout_latest_device (splice NULL)
+static int fanout_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                         const drp_changes *cols, uint64_t n, const drp_filter *filters, uint32_t nfilters,
+                         const drp_change_src *out_rows, uint64_t rows_cap, uint64_t *sel_idx, uint64_t *row_base,
+                         const drp_splice *splice, bool latest) {
   if (!c || !frames || !cols || !out_rows || !row_base || (!bytes && nbytes)) return DRP_E_INVAL;
   if (!rows_ok(frames, cols, out_rows, n)) return DRP_E_INVAL;
   if (splice && (!splice->n_blobs || (splice->blob_cap && (!splice->blob_row || !splice->blob_rank)))) return DRP_E_INVAL;
@@ -250,14 +244,14 @@ int drp_fanout_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const d
   if (const int rc = fanout_filters(c, filters, nfilters, P)) return rc;
   if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
   // (the decode scratch: free between decodes, and every user is ordered on the ctx's stream)
-  if (!c->scratch.ensure(drp_fanout_scratch_bytes(n, nfilters))) return DRP_E_NOMEM;
+  if (!c->scratch.ensure(fanout_scratch(c, n, nfilters, latest))) return DRP_E_NOMEM;
   P.src = caller_src(bytes, nbytes, frames, cols, n);
   drp_fanout_place(&P, c->scratch.p);
   P.out = row_out(out_rows, sel_idx);
   P.rows_cap = rows_cap;
   P.row_base = row_base;
   if (const int rc = fanout_send_filters(c, P)) return rc;
-  CHK(drp_launch_fanout_count(&P, c->st));
+  CHK(launch_fanout_count(c, P, latest));
   CHK(drp_launch_fanout_scatter(&P, c->st));
   if (splice) {
     P.blob_row = splice->blob_row;
@@ -269,9 +263,10 @@ int drp_fanout_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const d
   return DRP_OK;
 }
 
-int drp_fanout_staged(drp_ctx *c, const drp_filter *filters, uint32_t nfilters, uint8_t *out, uint64_t cap,
-                      uint64_t *out_off, uint64_t *n_selected, uint64_t *blob_row, uint64_t *blob_pos,
-                      uint64_t blob_cap, uint64_t *n_blobs) {
+// drp_fanout_staged, or with `latest` drp_fanout_latest_staged (no splice table: blob_row NULL)
+static int fanout_staged(drp_ctx *c, const drp_filter *filters, uint32_t nfilters, uint8_t *out, uint64_t cap,
+                         uint64_t *out_off, uint64_t *n_selected, uint64_t *blob_row, uint64_t *blob_pos,
+                         uint64_t blob_cap, uint64_t *n_blobs, bool latest) {
   if (!c || !out_off || !n_selected || (!out && cap)) return DRP_E_INVAL;
   if (blob_row ? (!n_blobs || (!blob_pos && blob_cap)) : (n_blobs != nullptr)) return DRP_E_INVAL;
   const auto &S = c->staged;
@@ -288,7 +283,7 @@ int drp_fanout_staged(drp_ctx *c, const drp_filter *filters, uint32_t nfilters, 
   hipStream_t st = c->st;
   // scratch (the decode's, free until the next decode): the kernels' words, row_base with the grand
   // total and the splice kernel's blob count behind it, the piece table
-  const size_t o_base = al(drp_fanout_scratch_bytes(n, K)), o_piece = o_base + al((K + 3) * 8);
+  const size_t o_base = al(fanout_scratch(c, n, K, latest)), o_piece = o_base + al((K + 3) * 8);
   if (!c->scratch.ensure(o_piece + al(2 * S.pieces.size() * 8))) return DRP_E_NOMEM;
   P.src.n = n;
   drp_fanout_place(&P, c->scratch.p);
@@ -298,7 +293,7 @@ int drp_fanout_staged(drp_ctx *c, const drp_filter *filters, uint32_t nfilters, 
   if (const int rc = fanout_send_filters(c, P)) return rc;
   // (c->host_tmp's filter table has been copied out: the piece table may pass through it)
   if (const int rc = staged_src(c, P.src, c->scratch.at<uint64_t>(o_piece))) return rc;
-  CHK(drp_launch_fanout_count(&P, st));
+  CHK(launch_fanout_count(c, P, latest));
   uint64_t rb[DRP_FANOUT_MAX + 2];
   CHK(hipMemcpyAsync(rb, drb, (K + 2) * 8, hipMemcpyDeviceToHost, st));
   CHK(hipStreamSynchronize(st));  // (the one readback that sizes the rows and the encode)
@@ -351,6 +346,57 @@ int drp_fanout_staged(drp_ctx *c, const drp_filter *filters, uint32_t nfilters, 
     CHK(hipStreamSynchronize(st));
   }
   return DRP_OK;
+}
+
+extern "C" {
+
+int drp_select_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                      const drp_changes *cols, uint64_t n, const drp_filter *filter, const drp_change_src *out_rows,
+                      uint64_t *sel_idx, uint64_t *n_selected) {
+  return select_device(c, bytes, nbytes, frames, cols, n, filter, out_rows, sel_idx, n_selected, false);
+}
+
+int drp_latest_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                      const drp_changes *cols, uint64_t n, const drp_filter *filter, const drp_change_src *out_rows,
+                      uint64_t *sel_idx, uint64_t *n_selected) {
+  return select_device(c, bytes, nbytes, frames, cols, n, filter, out_rows, sel_idx, n_selected, true);
+}
+
+int drp_relay_staged(drp_ctx *c, const drp_filter *filter, uint8_t *out, uint64_t cap, uint64_t *written,
+                     uint64_t *n_selected) {
+  return relay_staged(c, filter, out, cap, written, n_selected, false);
+}
+
+int drp_latest_staged(drp_ctx *c, const drp_filter *filter, uint8_t *out, uint64_t cap, uint64_t *written,
+                      uint64_t *n_selected) {
+  return relay_staged(c, filter, out, cap, written, n_selected, true);
+}
+
+int drp_fanout_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                      const drp_changes *cols, uint64_t n, const drp_filter *filters, uint32_t nfilters,
+                      const drp_change_src *out_rows, uint64_t rows_cap, uint64_t *sel_idx, uint64_t *row_base,
+                      const drp_splice *splice) {
+  return fanout_device(c, bytes, nbytes, frames, cols, n, filters, nfilters, out_rows, rows_cap, sel_idx, row_base,
+                       splice, false);
+}
+
+int drp_fanout_staged(drp_ctx *c, const drp_filter *filters, uint32_t nfilters, uint8_t *out, uint64_t cap,
+                      uint64_t *out_off, uint64_t *n_selected, uint64_t *blob_row, uint64_t *blob_pos,
+                      uint64_t blob_cap, uint64_t *n_blobs) {
+  return fanout_staged(c, filters, nfilters, out, cap, out_off, n_selected, blob_row, blob_pos, blob_cap, n_blobs,
+                       false);
+}
+
+int drp_fanout_latest_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                             const drp_changes *cols, uint64_t n, const drp_filter *filters, uint32_t nfilters,
+                             const drp_change_src *out_rows, uint64_t rows_cap, uint64_t *sel_idx, uint64_t *row_base) {
+  return fanout_device(c, bytes, nbytes, frames, cols, n, filters, nfilters, out_rows, rows_cap, sel_idx, row_base,
+                       nullptr, true);
+}
+
+int drp_fanout_latest_staged(drp_ctx *c, const drp_filter *filters, uint32_t nfilters, uint8_t *out, uint64_t cap,
+                             uint64_t *out_off, uint64_t *n_selected) {
+  return fanout_staged(c, filters, nfilters, out, cap, out_off, n_selected, nullptr, nullptr, 0, nullptr, true);
 }
 
 }  // extern "C"

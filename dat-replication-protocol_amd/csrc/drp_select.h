@@ -10,6 +10,10 @@
 namespace drp {
 
 constexpr uint32_t SEL_BLK = 1024, SEL_WAVES = SEL_BLK / 64;
+// the fan-out's count geometry (drp_fanout.hip; drp_latest.hip rewrites its planes and counts): a
+// workgroup of 16 waves takes FAN_ROWS = 4096 rows, wave w the 64-row chunks 4w .. 4w + 3
+constexpr uint32_t FAN_BLK = 1024, FAN_WAVES = FAN_BLK / 64, FAN_RPL = 4;
+constexpr uint32_t FAN_ROWS = FAN_BLK * FAN_RPL, FAN_CHUNKS = FAN_ROWS / 64;  // 64 ballot words per workgroup
 
 // what row i's payload offsets lack to be offsets into S.bytes
 __device__ __forceinline__ uint64_t row_shift(const RowSrc &S, uint64_t i) {

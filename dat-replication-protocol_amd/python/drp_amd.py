@@ -31,6 +31,7 @@ EXPORTS = [
     "drp_encode_batch", "drp_select_device", "drp_relay_staged", "drp_index_scan", "drp_stream_stats_from_results", "drp_device",
     "drp_fanout_device", "drp_fanout_staged",
     "drp_latest_device", "drp_latest_staged", "drp_set_latest_hash_mask",
+    "drp_fanout_latest_device", "drp_fanout_latest_staged", "drp_set_fanout_latest_pass",
     "drp_comm_id", "drp_comm_init_rank", "drp_comm_init_all", "drp_comm_destroy",
     "drp_index_allgather", "drp_index_allgather_multi", "drp_index_allgather_host", "drp_device_count",
     "drp_host_alloc", "drp_host_free",
@@ -186,6 +187,9 @@ def lib():
         L.drp_latest_device.argtypes = L.drp_select_device.argtypes
         L.drp_latest_staged.argtypes = L.drp_relay_staged.argtypes
         L.drp_set_latest_hash_mask.argtypes = [P, U64]
+        L.drp_fanout_latest_device.argtypes = L.drp_fanout_device.argtypes[:-1]
+        L.drp_fanout_latest_staged.argtypes = L.drp_fanout_staged.argtypes[:7]
+        L.drp_set_fanout_latest_pass.argtypes = [P, U32]
         L.drp_index_scan.argtypes = [P, P, U64, P]
         L.drp_stream_stats_from_results.argtypes = [P, P, P, U64, P]
         L.drp_device.argtypes = [P]
@@ -205,7 +209,8 @@ def lib():
                   "drp_decode_stage", "drp_decode_stage_v", "drp_decode_fetch", "drp_encode_size",
                   "drp_encode_device", "drp_encode_batch", "drp_select_device", "drp_relay_staged", "drp_index_scan",
                   "drp_fanout_device", "drp_fanout_staged", "drp_latest_device", "drp_latest_staged",
-                  "drp_set_latest_hash_mask", "drp_stream_stats_from_results", "drp_device", "drp_comm_id", "drp_comm_init_rank",
+                  "drp_set_latest_hash_mask", "drp_fanout_latest_device", "drp_fanout_latest_staged",
+                  "drp_set_fanout_latest_pass", "drp_stream_stats_from_results", "drp_device", "drp_comm_id", "drp_comm_init_rank",
                   "drp_comm_init_all", "drp_index_allgather", "drp_index_allgather_multi",
                   "drp_index_allgather_host", "drp_device_count"]:
             getattr(L, f).restype = C.c_int
@@ -582,6 +587,48 @@ class Ctx:
                   "blob_pos": bpos[:K * blob_cap].reshape(K, blob_cap)[:, :nb].copy() if fits else None,
                   "raw": (brow, bpos)}
         return outs, [int(v) for v in nsel[:K]], sp
+
+    # ---- fan-out of latest per key: many snapshots over one grouping -----------------------
+    def fanout_latest_device(self, wire_t, cols, n, filters, out_rows, rows_cap, sel_idx_t, row_base_t):
+        """drp_fanout_latest_device: fanout_device's arguments without the splice; output f holds
+        what latest_device gives for filters[f]."""
+        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
+        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
+                     tp(cols["flags"]), None)
+        dst = ChangeSrc(*[tp(out_rows[k]) for k in ["key_off", "key_len", "subset_off", "subset_len",
+                                                      "value_off", "value_len", "change", "from", "to", "flags"]])
+        self.order_after_torch(wire_t)
+        rc = self.L.drp_fanout_latest_device(self.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n,
+                                             filter_array(filters), len(filters), C.byref(dst), rows_cap,
+                                             tp(sel_idx_t), tp(row_base_t))
+        _chk("drp_fanout_latest_device", rc)
+        self.order_torch_after(wire_t)
+
+    def fanout_latest_staged(self, filters, cap=None, out=None):
+        """drp_fanout_latest_staged over the batch last staged (decode_staged), filters a list of
+        make_filter results (None: every Change is a candidate): returns ([wire bytes per filter],
+        [winners per filter]), output f being latest_staged's for filters[f]. cap=None: len(filters)
+        times the staged batch's length, which is always enough. A given cap that is too small
+        raises DrpError(DRP_E_CAPACITY) with .written = the size needed and .n_selected.
+        out: a host uint8 array to write into (at least cap bytes)."""
+        K = len(filters)
+        if cap is None:
+            cap = K * getattr(self, "_staged_len", 0)
+        buf = out if out is not None else np.zeros(max(16, cap), np.uint8)
+        out_off, nsel = np.zeros(K + 1, np.uint64), np.zeros(max(K, 1), np.uint64)
+        rc = self.L.drp_fanout_latest_staged(self.h, filter_array(filters), K, _p(buf), cap, _p(out_off), _p(nsel))
+        if rc != DRP_OK:
+            e = DrpError("drp_fanout_latest_staged", rc)
+            e.written = int(out_off[K]) if K <= FANOUT_MAX else 0
+            e.n_selected = [int(v) for v in nsel[:K]]
+            raise e
+        return [buf[int(out_off[f]):int(out_off[f + 1])].tobytes() for f in range(K)], [int(v) for v in nsel[:K]]
+
+    def set_fanout_latest_pass(self, t):
+        """Test hook: the filters one reduction pass of fanout_latest_device / fanout_latest_staged
+        handles (0: the default); results are identical for every value."""
+        _chk("drp_set_fanout_latest_pass", self.L.drp_set_fanout_latest_pass(self.h, t))
 
 
 class Comm:

@@ -25,6 +25,9 @@
  *   drp_latest_device / drp_latest_staged
  *       -> no reference counterpart: of the Changes that select keeps, the one with the greatest
  *          `change` per (subset, key) (schema messages/schema.proto:1-8), a hub's fan-in.
+ *   drp_fanout_latest_device / drp_fanout_latest_staged
+ *       -> no reference counterpart: that latest per key under many filters at once, grouped once
+ *          (a hub catching up many peers, each at its own version).
  *   drp_stream_stats + drp_index_scan
  *       -> no reference counterpart (the reference is single-stream); they build the
  *          global frame index after the per-GPU stats tables are all-gathered.
@@ -461,6 +464,45 @@ int drp_latest_staged(drp_ctx *ctx, const drp_filter *filter, uint8_t *out, uint
  * table (default: all ones; 0: every row starts at the same slot). Results are identical for
  * every mask. Test hook. */
 int drp_set_latest_hash_mask(drp_ctx *ctx, uint64_t mask);
+
+/* ---- fan-out of latest per key: many snapshots over one grouping ----------- */
+/* A hub that catches up many peers at once wants, for peer f, the snapshot under that peer's filter
+ * (its version T_f as DRP_SEL_CHANGE_RANGE, its subset, its key prefix). Output f of the two calls
+ * below is exactly what drp_latest_device returns for filters[f] over the same rows: the same
+ * candidates, identity, winner, row order, wire-bounds rule and flag masking. The part that does not
+ * depend on the filter is done once: the predicates in one pass over the columns (as drp_fanout_device),
+ * and the grouping (the hash of every key, the table probes, the byte compares) over the rows that
+ * at least one filter keeps; only the reduction to the greatest (change, row) runs per filter.
+ * No reference counterpart (the reference has no relay); the fields read are subset, key and change
+ * of messages/schema.proto:1-8. */
+
+/* drp_fanout_device without the splice argument (a snapshot has no blobs to place) and with that
+ * reduction behind every predicate: output f is rows [row_base[f], row_base[f + 1]) of out_rows and of
+ * sel_idx (device, may be NULL), the winners under filters[f] in increasing row order; row_base
+ * (device, nfilters + 1 entries) is always written and carries the true counts. If
+ * row_base[nfilters] > rows_cap nothing is written to out_rows or sel_idx, otherwise entries at or
+ * beyond row_base[nfilters] are left untouched; one drp_encode_device over row_base[nfilters] rows
+ * encodes every output. The result is a function of the input alone. Device pointers only (filters
+ * is HOST memory, read before the call returns); asynchronous on drp_stream(ctx), no host
+ * synchronisation inside. The DRP_E_INVAL cases are drp_fanout_device's. Scratch, from the ctx's
+ * (DRP_E_NOMEM if it cannot be allocated): drp_fanout_device's, 8 bytes per row, 8 bytes for each of
+ * the 2 n slots, rounded up to a power of two, 2 bits per row, and per row 16 bytes per filter of one
+ * reduction pass (min(nfilters, 8) by default: 128 bytes per row at most). */
+int drp_fanout_latest_device(drp_ctx *ctx, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                             const drp_changes *cols, uint64_t n, const drp_filter *filters, uint32_t nfilters,
+                             const drp_change_src *out_rows, uint64_t rows_cap, uint64_t *sel_idx, uint64_t *row_base);
+/* drp_fanout_staged without the four blob arguments and with that reduction: over the same delivered
+ * rows of the batch last staged, with the same validity rules and DRP_E_INVAL cases and the same
+ * bytes in every drp_set_blob_skip mode; output f equals drp_latest_staged's bytes for filters[f].
+ * Synchronous. out: host or device pointer; out_off (HOST, nfilters + 1) and n_selected (HOST,
+ * nfilters) as there. DRP_E_CAPACITY: nothing is written to out, out_off[nfilters] = the size needed,
+ * n_selected is valid. The staged batch stays valid. */
+int drp_fanout_latest_staged(drp_ctx *ctx, const drp_filter *filters, uint32_t nfilters, uint8_t *out, uint64_t cap,
+                             uint64_t *out_off, uint64_t *n_selected);
+/* Filters one reduction pass of the two calls above handles (0: the default; above nfilters: all in
+ * one pass). Results are identical for every value; the scratch grows with it. Test hook, as
+ * drp_set_latest_hash_mask, which applies to the two calls as well. */
+int drp_set_fanout_latest_pass(drp_ctx *ctx, uint32_t filters_per_pass);
 
 /* ---- multi-GPU global index ---------------------------------------------- */
 /* stats[nranks*per_rank] (device): all-gathered per-stream tables in rank order.

@@ -30,6 +30,15 @@ probe, and the host relay through drp_relay_staged against the host round trip i
               checked to be the same. Written to --latest-out as its own JSON line. With
               --latest-only the relay and fan-out legs are left out (a run under a kernel trace).
 
+  fan-out of latest  (--fanout-latest-out, default profiles/relay/fanout_latest_bench.json) Device: the
+              latest leg's frames / 16 key pool, K = 1, 8, 64 filters change <= 1 + floor(100 f / K)
+              (every peer at its own version); one drp_fanout_latest_device against K back-to-back
+              drp_latest_device calls, alternating call by call, HIP events, the device leg's warm-up
+              and repeat counts; every output's winners checked against a numpy sort of (key, change,
+              row). Host: K = 16 over the --host-mib batch, drp_fanout_latest_staged against 16
+              drp_latest_staged calls over the same staged batch, alternating, wall clock, the bytes
+              checked to be the same. With --fanout-latest-only every other leg is left out.
+
 Prints one JSON line (and writes it to --out). Needs an MI355X: there is no CPU path.
 
   hipcc -O3 --offload-arch=gfx950 scripts/probe_bw.hip -o exp/probe_bw
@@ -545,6 +554,163 @@ def latest_host_leg(ctx, drp_amd, mib, runs):
             "same_bytes": same}
 
 
+# ---- fan-out of latest per key ------------------------------------------------------------------
+
+def snapshot_winners(key_ids, tmaxes):
+    """latest_winners under change <= T for every T of tmaxes: one sort of (key, change, row); the
+    rows a T keeps are a prefix of every key's run, so each T takes the last kept row per key."""
+    n = len(key_ids)
+    assert n < 1 << 25 and int(key_ids.max()) < 1 << 31
+    i = np.arange(n, dtype=np.int64)
+    packed = np.sort((key_ids << 32) | ((i % 100 + 1) << 25) | i)
+    out = []
+    for t in tmaxes:
+        sub = packed[((packed >> 25) & 127) <= t]
+        last = np.flatnonzero(np.append(sub[1:] >> 32 != sub[:-1] >> 32, True))
+        out.append(np.sort(sub[last] & ((1 << 25) - 1)))
+    return out
+
+
+def _version_filters(drp_amd, K):
+    ts = [1 + (100 * f) // K for f in range(K)]  # every peer at its own version
+    return ts, [drp_amd.make_filter(change_range=(0, t)) for t in ts]
+
+
+def fanout_latest_device_leg(ctx, drp_amd, torch, frames, iters):
+    """One drp_fanout_latest_device with K filters against K back-to-back drp_latest_device calls over
+    the latest leg's frames / 16 key pool, alternating call by call, HIP events."""
+    dev = torch.device("cuda", 0)
+    L = ctx.L
+    tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    key_ids = latest_pools(frames)["keys_n_over_16"]
+    wire_t, cols, n = device_setup(ctx, drp_amd, torch, None, frames, wire=keyed_c2_stream(key_ids))
+    fr = drp_amd.Frames(tp(cols["payload_off"]), tp(cols["payload_len"]), tp(cols["type"]))
+    co = drp_amd.Changes(*[tp(cols[k]) for k in drp_amd.COLS32], tp(cols["change"]), tp(cols["from"]),
+                         tp(cols["to"]), tp(cols["flags"]), None)
+    ext = ctx._ext(dev)
+    one = _row_tensors(torch, dev, n)  # a single call's rows (every call of the sequence reuses them)
+    one_src = drp_amd.ChangeSrc(*[tp(one[k]) for k in SRC_KEYS])
+    one_idx = torch.zeros(n, dtype=torch.int64, device=dev)
+    nsel_t = torch.zeros(1, dtype=torch.int64, device=dev)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record(ext)
+        fn()
+        e1.record(ext)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    res = {"frames": n, "iters": iters, "keys": int(len(np.unique(key_ids)))}
+    for K in (1, 8, 64):
+        ts_, flt = _version_filters(drp_amd, K)
+        arr = drp_amd.filter_array(flt)
+        want = snapshot_winners(key_ids, ts_)
+        total = sum(len(w) for w in want)
+        many = _row_tensors(torch, dev, total)
+        many_src = drp_amd.ChangeSrc(*[tp(many[k]) for k in SRC_KEYS])
+        many_idx = torch.zeros(total, dtype=torch.int64, device=dev)
+        rb_t = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+
+        def fan():
+            rc = L.drp_fanout_latest_device(ctx.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n, arr, K,
+                                            C.byref(many_src), total, tp(many_idx), tp(rb_t))
+            assert rc == 0, rc
+
+        def seq():
+            for f in flt:
+                rc = L.drp_latest_device(ctx.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n, C.byref(f),
+                                         C.byref(one_src), tp(one_idx), tp(nsel_t))
+                assert rc == 0, rc
+
+        tf, tq = [], []
+        for it in range(iters + 3):  # (three warm-ups; alternating call by call)
+            a, b = timed(fan), timed(seq)
+            if it >= 3:
+                tf.append(a)
+                tq.append(b)
+        rb = rb_t.cpu().numpy()
+        assert [int(rb[f + 1] - rb[f]) for f in range(K)] == [len(w) for w in want], "winners per output"
+        idx = many_idx.cpu().numpy()
+        ch = many["change"].cpu().numpy()
+        for f in range(K):
+            a0, a1 = int(rb[f]), int(rb[f + 1])
+            assert np.array_equal(idx[a0:a1], want[f]), (K, f)
+            assert np.array_equal(ch[a0:a1], want[f] % 100 + 1), (K, f)
+        # the sequence's last call against the same numpy side
+        assert int(nsel_t.cpu()[0]) == len(want[-1]) and np.array_equal(one_idx[:len(want[-1])].cpu().numpy(), want[-1])
+        nslots = 1 << int(2 * n - 1).bit_length()
+        res[f"K{K}"] = {"filters": K, "rows_out": total, "fanout_latest_ms": _stat(tf), "sequential_ms": _stat(tq),
+                        "sequential_over_fanout_latest": statistics.median(tq) / statistics.median(tf),
+                        "ranges_overlap": not (max(tf) < min(tq) or max(tq) < min(tf)),
+                        "pass_width": min(K, 8), "passes": -(-K // 8),
+                        "group_scratch_bytes": int(n * 8 + nslots * 8 + 2 * ((n + 63) // 64 * 8) + n * 16 * min(K, 8))}
+        print("fanout_latest", K, res[f"K{K}"]["fanout_latest_ms"], res[f"K{K}"]["sequential_ms"], file=sys.stderr,
+              flush=True)
+        many = many_src = many_idx = None
+        torch.cuda.empty_cache()
+    return res
+
+
+def fanout_latest_host_leg(ctx, drp_amd, mib, runs, K=16):
+    """drp_fanout_latest_staged with K filters against K drp_latest_staged calls over the same staged
+    batch (staged once per pair, outside the timed part: it is the same for both), alternating."""
+    L = ctx.L
+    nbytes = mib << 20
+    frames = nbytes // 86 + 1
+    wire = keyed_c2_stream(latest_pools(frames)["keys_n_over_16"])[:nbytes].copy()
+    _, flt = _version_filters(drp_amd, K)
+    arr = drp_amd.filter_array(flt)
+    U64, U32 = C.c_uint64, C.c_uint32
+    out_f, out_s = np.zeros(K * nbytes, np.uint8), np.zeros(K * nbytes, np.uint8)
+    off_f, nsel_f = np.zeros(K + 1, np.uint64), np.zeros(K, np.uint64)
+
+    def stage():
+        carry = drp_amd.Carry(0, 0, 0, 0, 0)
+        nf, ef, ec, ed = U64(), U64(), U32(), U32()
+        rc = L.drp_decode_stage(ctx.h, drp_amd._p(wire), nbytes, C.byref(carry), C.byref(nf), C.byref(ef),
+                                C.byref(ec), C.byref(ed))
+        assert rc == 0 and ec.value == 0, (rc, ec.value)
+
+    def fan():
+        rc = L.drp_fanout_latest_staged(ctx.h, arr, K, drp_amd._p(out_f), out_f.size, drp_amd._p(off_f),
+                                        drp_amd._p(nsel_f))
+        assert rc == 0, rc
+
+    def seq():
+        at, ns = 0, []
+        for f in flt:
+            written, nsel = U64(), U64()
+            rc = L.drp_latest_staged(ctx.h, C.byref(f), drp_amd._p(out_s[at:]), out_s.size - at, C.byref(written),
+                                     C.byref(nsel))
+            assert rc == 0, rc
+            at += int(written.value)
+            ns.append(int(nsel.value))
+        return at, ns
+
+    tf, tq = [], []
+    same = False
+    for it in range(runs + 2):  # (two warm-ups; alternating)
+        stage()
+        t0 = time.perf_counter()
+        fan()
+        t1 = time.perf_counter()
+        at, ns = seq()
+        t2 = time.perf_counter()
+        if it == 1:
+            same = (int(off_f[K]) == at and ns == [int(v) for v in nsel_f] and
+                    out_f[:at].tobytes() == out_s[:at].tobytes())
+            assert same, (int(off_f[K]), at)
+        if it >= 2:
+            tf.append((t1 - t0) * 1e3)
+            tq.append((t2 - t1) * 1e3)
+    return {"batch_bytes": nbytes, "filters": K, "out_bytes": int(off_f[K]), "rows_out": int(nsel_f.sum()),
+            "runs": runs, "fanout_latest_staged_ms": _stat(tf), "sequential_latest_staged_ms": _stat(tq),
+            "sequential_over_fanout_latest": statistics.median(tq) / statistics.median(tf),
+            "ranges_overlap": not (max(tf) < min(tq) or max(tq) < min(tf)), "same_bytes": same}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20_000_000)
@@ -556,9 +722,16 @@ def main():
     ap.add_argument("--fanout-out", default=None, help="run the fan-out legs too and write their JSON line here")
     ap.add_argument("--latest-out", default=None, help="run the latest-per-key legs too and write their JSON line here")
     ap.add_argument("--latest-only", action="store_true", help="with --latest-out: leave the other legs out")
+    ap.add_argument("--fanout-latest-out", nargs="?", default=None,
+                    const=os.path.join(ROOT, "profiles", "relay", "fanout_latest_bench.json"),
+                    help="run the fan-out-of-latest legs too and write their JSON line here")
+    ap.add_argument("--fanout-latest-only", action="store_true",
+                    help="with --fanout-latest-out: leave the other legs out")
     a = ap.parse_args()
     if a.latest_only and not a.latest_out:
         ap.error("--latest-only needs --latest-out")
+    if a.fanout_latest_only and not a.fanout_latest_out:
+        ap.error("--fanout-latest-only needs --fanout-latest-out")
     res = {"bench": "relay"}
     if a.probe:
         res["probe_bw"] = run_probe(a.probe)
@@ -568,6 +741,17 @@ def main():
     torch.cuda.init()
     import _streams as S
     import drp_amd
+    if a.fanout_latest_out:
+        with drp_amd.Ctx(0) as ctx:
+            ctx.set_blob_skip(drp_amd.BLOB_SKIP_OFF)
+            fl = {"bench": "relay_fanout_latest",
+                  "device": fanout_latest_device_leg(ctx, drp_amd, torch, a.frames, a.iters),
+                  "host": fanout_latest_host_leg(ctx, drp_amd, a.host_mib, a.runs)}
+        with open(a.fanout_latest_out, "w") as f:
+            f.write(json.dumps(fl) + "\n")
+        print(json.dumps(fl))
+        if a.fanout_latest_only:
+            return
     if a.latest_out:
         with drp_amd.Ctx(0) as ctx:
             ctx.set_blob_skip(drp_amd.BLOB_SKIP_OFF)
