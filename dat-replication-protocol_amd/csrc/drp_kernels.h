@@ -221,6 +221,45 @@ struct FanLatestParams {
 // and the state of a batch at most 128 bytes per row (DESIGN.md "Fan-out of latest per key")
 constexpr uint32_t FLAT_PASS_DEFAULT = 8;
 
+// drp_store.hip: the store (drp_store of include/drp.h) as the kernels take it. A word of its table
+// is hash tag (the high 32 bits) | store row + 1 (max_keys <= 2^31), 0 for a free slot; nslots is a
+// power of two >= 2 max_keys, so the table is at most half full
+struct StoreDev {
+  uint8_t *arena;
+  uint64_t arena_bytes;
+  uint64_t *payload_off;
+  uint32_t *payload_len;
+  uint8_t *type;
+  drp_changes cols;
+  uint64_t max_keys;
+  uint64_t *table;
+  uint64_t nslots, hash_mask;  // hash_mask: as LatTable's
+  drp_store_info *info;
+};
+constexpr uint64_t ST_TAG = 0xFFFFFFFF00000000ull;
+// one merge: the winners drp_launch_latest left (encoder rows, offsets absolute into the wire, and
+// their count on the device) and the merge's state, placed by the launcher
+struct StoreMerge {
+  StoreDev s;
+  const uint8_t *bytes;
+  uint64_t nbytes;
+  drp_change_src w;
+  const uint64_t *nw;  // the winners (<= n)
+  uint64_t n;          // the batch's rows: what the grids are sized from
+  // per winner: the store row (replaced; inserted: the first free slot of its probe, then, from
+  // st_claim on, its new row), the identity's hash, the bytes its workgroup's winners before it
+  // need, its allocation, and outcome | rank among its workgroup's inserted winners << 8
+  uint64_t *where, *hash, *boff;
+  uint32_t *alloc, *meta;
+  // per workgroup of ST_BLK winners: inserted winners and bytes needed (each scanned in place), and
+  // ST_MISC further sums (replaced, unchanged, stale, skipped, dead bytes)
+  uint64_t *blk_ins, *blk_bytes, *blk_misc;
+  uint64_t nblk;
+  uint64_t *ctl;  // [0] the inserted winners, [1] the bytes needed, [2] the dead bytes
+};
+constexpr uint32_t ST_BLK = 256, ST_WAVES = ST_BLK / 64, ST_MISC = 5;
+constexpr uint32_t ST_GRP = 16;  // lanes that copy one payload, 16 bytes each per step
+
 }  // namespace drp
 
 extern "C" {
@@ -308,6 +347,18 @@ hipError_t drp_launch_fanout_scan(const drp::FanParams *P, hipStream_t st);
 // ballots and their scan, the pass state.
 uint64_t drp_fanout_latest_scratch_bytes(uint64_t n, uint32_t nfilters, uint32_t pass);
 hipError_t drp_launch_fanout_latest(const drp::FanParams *P, uint64_t hash_mask, uint32_t pass, void *scratch,
+                                    hipStream_t st);
+// drp_select.hip's scan on its own: cnt[0, nblk) scanned in place (exclusive), *total = their sum
+hipError_t drp_launch_count_scan(uint64_t *cnt, uint64_t nblk, uint64_t *total, hipStream_t st);
+// drp_store.hip. The table's slots for max_keys (0: out of range); an empty store; steps 2 to 6 of a
+// merge over the winners in M (its state is placed in `scratch`, drp_store_merge_scratch_bytes(n)
+// bytes); a compact into arena2 (scratch: drp_store_compact_scratch_bytes(max_keys)).
+uint64_t drp_store_nslots(uint64_t max_keys);
+hipError_t drp_launch_store_init(const drp::StoreDev *S, hipStream_t st);
+uint64_t drp_store_merge_scratch_bytes(uint64_t n);
+hipError_t drp_launch_store_merge(const drp::StoreMerge *M, void *scratch, hipStream_t st);
+uint64_t drp_store_compact_scratch_bytes(uint64_t max_keys);
+hipError_t drp_launch_store_compact(const drp::StoreDev *S, uint8_t *arena2, uint64_t arena2_bytes, void *scratch,
                                     hipStream_t st);
 hipError_t drp_launch_fanout_scatter(const drp::FanParams *P, hipStream_t st);
 hipError_t drp_launch_fanout_splice(const drp::FanParams *P, hipStream_t st);

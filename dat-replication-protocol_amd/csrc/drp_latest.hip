@@ -54,16 +54,7 @@ __device__ __forceinline__ uint64_t *lat_word(const LatTable &T, uint64_t s, uin
 
 // wire bytes [a, a + len) == [b, b + len) (both ranges inside the wire)
 __device__ __forceinline__ bool lat_bytes_eq(const RowSrc &P, uint64_t a, uint64_t b, uint32_t len) {
-  const uint8_t *x = P.bytes + a, *y = P.bytes + b;
-  if (len < 8) {
-    for (uint32_t k = 0; k < len; k++)
-      if (x[k] != y[k]) return false;
-    return true;
-  }
-  // eight bytes per step (unaligned 8-byte loads), the last step over the last eight bytes
-  for (uint32_t k = 0; k + 8 < len; k += 8)
-    if (xxh::rd64(x + k) != xxh::rd64(y + k)) return false;
-  return xxh::rd64(x + len - 8) == xxh::rd64(y + len - 8);
+  return bytes_eq(P.bytes + a, P.bytes + b, len);  // (drp_select.h; drp_store.hip compares with it too)
 }
 
 // candidate row j (it claimed a slot: its ranges are inside the wire) has this identity

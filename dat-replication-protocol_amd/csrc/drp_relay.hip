@@ -2,8 +2,10 @@
 // drp_latest_device over the caller's decoded columns, drp_relay_staged and drp_latest_staged over
 // the batch last staged (select or latest per key, then the encoder with the staged wire as its
 // heap), drp_fanout_device / drp_fanout_staged (many filters over one pass) and
-// drp_fanout_latest_device / drp_fanout_latest_staged (latest per key under each). The kernels are in
-// drp_select.hip, drp_latest.hip and drp_fanout.hip; the context is drp_api.hip's (drp_ctx.h).
+// drp_fanout_latest_device / drp_fanout_latest_staged (latest per key under each), and the store
+// (drp_store_*: the latest-per-key step, then the merge into caller-owned device memory). The kernels
+// are in drp_select.hip, drp_latest.hip, drp_fanout.hip and drp_store.hip; the context is
+// drp_api.hip's (drp_ctx.h).
 #include <algorithm>
 #include <cstring>
 
@@ -348,7 +350,116 @@ static int fanout_staged(drp_ctx *c, const drp_filter *filters, uint32_t nfilter
   return DRP_OK;
 }
 
+// ---- store --------------------------------------------------------------------------------------
+// the caller's drp_store as the kernels take it; false: a NULL pointer, a misaligned arena,
+// max_keys out of range
+static bool store_dev(const drp_ctx *c, const drp_store *s, StoreDev &D) {
+  const drp_changes &co = s->cols;
+  D.nslots = drp_store_nslots(s->max_keys);
+  if (!D.nslots || !s->table || !s->info || (!s->arena && s->arena_bytes) || ((uintptr_t)s->arena & 15)) return false;
+  if (!s->frames.payload_off || !s->frames.payload_len || !s->frames.type || !co.key_off || !co.key_len ||
+      !co.subset_off || !co.subset_len || !co.value_off || !co.value_len || !co.change || !co.from || !co.to ||
+      !co.flags)
+    return false;
+  D.arena = s->arena;
+  D.arena_bytes = s->arena_bytes;
+  D.payload_off = s->frames.payload_off;
+  D.payload_len = s->frames.payload_len;
+  D.type = s->frames.type;
+  D.cols = co;
+  D.max_keys = s->max_keys;
+  D.table = s->table;
+  D.hash_mask = c->latest_hash_mask;
+  D.info = s->info;
+  return true;
+}
+
+// A merge of the rows `src` describes (the caller's, or the staged batch's when `staged`): the
+// latest-per-key step into winner rows in the ctx's scratch, then drp_store.hip's steps over them.
+// Scratch: drp_launch_latest's words, the winners' count, the staged piece table, the winner rows
+// (ten columns of n entries), the merge's state
+static int store_merge(drp_ctx *c, const StoreDev &D, const RowSrc *caller, const drp_filter *filter) {
+  SelectParams P = {};
+  SelectBytes fb = {};
+  if (const int rc = select_filter(filter, P.f, fb.b)) return rc;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  const auto &S = c->staged;
+  const uint64_t n = caller ? caller->n : S.good, np = caller ? 0 : S.pieces.size();
+  const size_t o_cnt = al(drp_latest_scratch_bytes(n)), o_piece = o_cnt + 256, o_rows = o_piece + al(2 * np * 8),
+               col = al(n * 8), o_state = o_rows + 10 * col;
+  if (!c->scratch.ensure(o_state + drp_store_merge_scratch_bytes(n))) return DRP_E_NOMEM;
+  if (caller) P.src = *caller;
+  else if (const int rc = staged_src(c, P.src, c->scratch.at<uint64_t>(o_piece))) return rc;
+  const drp_change_src rows = carve_rows(c->scratch, o_rows, col);
+  P.out = row_out(&rows, nullptr);
+  P.n_selected = c->scratch.at<uint64_t>(o_cnt);
+  CHK(drp_launch_latest(&P, &fb, c->latest_hash_mask, c->scratch.p, c->st));
+  StoreMerge M = {};
+  M.s = D;
+  M.bytes = P.src.bytes;
+  M.nbytes = P.src.nbytes;
+  M.w = rows;
+  M.nw = P.n_selected;
+  M.n = n;
+  CHK(drp_launch_store_merge(&M, c->scratch.at<char>(o_state), c->st));
+  return DRP_OK;
+}
+
+static int store_query(drp_ctx *c, const drp_store_info *dev, drp_store_info *host) {
+  CHK(hipMemcpyAsync(host, dev, sizeof(drp_store_info), hipMemcpyDeviceToHost, c->st));
+  CHK(hipStreamSynchronize(c->st));
+  return DRP_OK;
+}
+
 extern "C" {
+
+uint64_t drp_store_table_bytes(uint64_t max_keys) { return 8 * drp_store_nslots(max_keys); }
+
+int drp_store_init(drp_ctx *c, const drp_store *s) {
+  StoreDev D = {};
+  if (!c || !s || !store_dev(c, s, D)) return DRP_E_INVAL;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  CHK(drp_launch_store_init(&D, c->st));
+  return DRP_OK;
+}
+
+int drp_store_merge_device(drp_ctx *c, const drp_store *s, const uint8_t *bytes, uint64_t nbytes,
+                           const drp_frames *frames, const drp_changes *cols, uint64_t n, const drp_filter *filter) {
+  StoreDev D = {};
+  if (!c || !s || !frames || !cols || (!bytes && nbytes) || !store_dev(c, s, D)) return DRP_E_INVAL;
+  if (n && !(frames->payload_off && frames->type && cols->key_off && cols->key_len && cols->subset_off &&
+             cols->subset_len && cols->value_off && cols->value_len && cols->change && cols->from && cols->to &&
+             cols->flags))
+    return DRP_E_INVAL;
+  const RowSrc R = caller_src(bytes, nbytes, frames, cols, n);
+  return store_merge(c, D, &R, filter);
+}
+
+int drp_store_merge_staged(drp_ctx *c, const drp_store *s, const drp_filter *filter, drp_store_info *info_host) {
+  StoreDev D = {};
+  if (!c || !s || !store_dev(c, s, D)) return DRP_E_INVAL;
+  if (!c->staged.valid) return DRP_E_INVAL;
+  if (const int rc = store_merge(c, D, nullptr, filter)) return rc;
+  drp_store_info I;
+  if (const int rc = store_query(c, D.info, &I)) return rc;
+  if (info_host) *info_host = I;
+  return I.refused ? DRP_E_CAPACITY : DRP_OK;
+}
+
+int drp_store_compact(drp_ctx *c, const drp_store *s, uint8_t *arena2, uint64_t arena2_bytes) {
+  StoreDev D = {};
+  if (!c || !s || !store_dev(c, s, D) || (!arena2 && arena2_bytes) || ((uintptr_t)arena2 & 15)) return DRP_E_INVAL;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  if (!c->scratch.ensure(drp_store_compact_scratch_bytes(D.max_keys))) return DRP_E_NOMEM;
+  CHK(drp_launch_store_compact(&D, arena2, arena2_bytes, c->scratch.p, c->st));
+  return DRP_OK;
+}
+
+int drp_store_query(drp_ctx *c, const drp_store *s, drp_store_info *info_host) {
+  if (!c || !s || !s->info || !info_host) return DRP_E_INVAL;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  return store_query(c, s->info, info_host);
+}
 
 int drp_select_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
                       const drp_changes *cols, uint64_t n, const drp_filter *filter, const drp_change_src *out_rows,

@@ -41,6 +41,19 @@ __device__ __forceinline__ bool wire_eq(const RowSrc &S, uint64_t off, uint32_t 
   return true;
 }
 
+// x[0, len) == y[0, len) (any alignment; both ranges readable)
+__device__ __forceinline__ bool bytes_eq(const uint8_t *x, const uint8_t *y, uint32_t len) {
+  if (len < 8) {
+    for (uint32_t k = 0; k < len; k++)
+      if (x[k] != y[k]) return false;
+    return true;
+  }
+  // eight bytes per step (unaligned 8-byte loads), the last step over the last eight bytes
+  for (uint32_t k = 0; k + 8 < len; k += 8)
+    if (xxh::rd64(x + k) != xxh::rd64(y + k)) return false;
+  return xxh::rd64(x + len - 8) == xxh::rd64(y + len - 8);
+}
+
 // the columns of one row the predicate reads (loaded once, whatever the number of filters)
 struct PredRow {
   uint64_t change, sub_at, key_at;  // sub_at / key_at: the subset's / key's offset into S.bytes

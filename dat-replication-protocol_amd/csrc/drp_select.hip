@@ -107,6 +107,15 @@ extern "C" hipError_t drp_launch_select_compact(const SelectParams *Pp, hipStrea
   return hipGetLastError();
 }
 
+// step (2) alone, for drp_store.hip: cnt[0, nblk) scanned in place (exclusive), *total = their sum
+extern "C" hipError_t drp_launch_count_scan(uint64_t *cnt, uint64_t nblk, uint64_t *total, hipStream_t st) {
+  SelectParams P = {};
+  P.block_cnt = cnt;
+  P.n_selected = total;
+  hipLaunchKernelGGL(sel_scan_kernel, dim3(1), dim3(SEL_BLK), 0, st, P, nblk);
+  return hipGetLastError();
+}
+
 extern "C" hipError_t drp_launch_select(const SelectParams *Pp, const SelectBytes *fb, void *scratch, hipStream_t st) {
   SelectParams P = *Pp;
   if (P.src.n == 0) return hipMemsetAsync(P.n_selected, 0, 8, st);

@@ -1,0 +1,420 @@
+// drp_store.hip — gfx950 kernels of the store (include/drp.h "store"): the latest Change per
+// identity (subset presence, subset bytes, key bytes) over every batch merged so far, kept in
+// caller-owned device memory as the rows of a decoded batch over an arena of payloads, plus an
+// open-addressing table from identity to row. No reference counterpart: the reference has no relay;
+// the fields read are those of messages/schema.proto:1-8.
+//
+// A merge starts from the winners drp_launch_latest (drp_latest.hip) leaves: one row per identity,
+// so identities are distinct within a merge. That is what keeps the persistent table simple: it is
+// only looked up against bytes that earlier kernels wrote, and new identities claim free slots with
+// a bare compare-and-swap. The rule of drp_latest.hip holds: what one workgroup writes and another
+// reads within one kernel goes through an agent-scope atomic (only the table words of st_claim);
+// everything else crosses a kernel boundary.
+//   st_lookup   one winner per lane: the identity's hash (lat_group's: XXH64 of the key, the subset's
+//               merged in, the ctx's hash mask), a linear probe of the table with atomic loads (no
+//               kernel of a merge writes the table before st_claim), on a tag match the lengths and
+//               then the winner's wire bytes against the row's arena bytes (plain reads: written by
+//               earlier launches). The outcome (inserted / replaced / unchanged / stale / skipped),
+//               the store row or the first free slot of the probe, the bytes needed; within the
+//               workgroup the winner's rank among the inserted and the bytes needed before it; per
+//               workgroup the sums.
+//   scan        drp_select.hip's scan over the workgroups' inserted counts and over their bytes.
+//   st_verdict  one workgroup: the remaining sums, the totals against the capacities, the verdict
+//               and the last-merge group of the info record. Every later kernel reads the verdict
+//               and does nothing after a refusal.
+//   st_claim    the inserted winners: row = rows + rank, then from the saved slot on a
+//               compare-and-swap of 0 -> tag | row + 1 per slot until one takes place. A slot taken
+//               meanwhile belongs to another identity (they are distinct), so nothing is compared;
+//               no lane waits for another; the loop ends after nslots steps at the latest.
+//   st_write    the inserted and replaced winners, ST_GRP = 16 lanes each: key | subset | value into
+//               the arena at arena_used + the scanned prefix, 16 bytes per lane and step (256 bytes
+//               per step: a 4 KB value takes 16, a 40-byte payload one, and four winners share a
+//               wave), the allocation's tail zeroed; the group's first lane writes the columns.
+//   st_commit   rows, arena_used, arena_dead, merges.
+// The compact is the same shape: the live allocations' sizes and their prefix, the scan, the verdict
+// with the commit (nothing later reads the old totals), the copy.
+#include "drp_select.h"  // (wire_has, bytes_eq; drp_device.h: xxh, ld_agent, the wave scans)
+
+namespace drp {
+
+enum : uint32_t { ST_NONE = 0, ST_INSERT = 1, ST_REPLACE = 2, ST_UNCHANGED = 3, ST_STALE = 4, ST_SKIPPED = 5 };
+
+__device__ __forceinline__ uint32_t st_r16(uint32_t len) { return (len + 15u) & ~15u; }  // (len <= 2^32 - 16)
+
+// v summed over the lanes of the workgroup before this one, and over all of them (ST_BLK lanes)
+__device__ __forceinline__ uint64_t st_block_prefix(uint64_t v, uint64_t &total) {
+  __shared__ uint64_t part[ST_WAVES];
+  const uint64_t incl = wave_incl_scan64(v);
+  const uint32_t wv = threadIdx.x >> 6;
+  if (lane_id() == 63) part[wv] = incl;
+  __syncthreads();
+  uint64_t before = incl - v, all = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < ST_WAVES; k++) {
+    if (k < wv) before += part[k];
+    all += part[k];
+  }
+  total = all;
+  return before;
+}
+
+// store row r (named by a table word) has this identity; a row outside the store, or whose payload
+// leaves the arena (a table that no drp_store_init cleared), matches nothing and is never read
+__device__ __forceinline__ bool st_same(const StoreDev &S, uint64_t r, bool has, const uint8_t *key, uint32_t klen,
+                                        const uint8_t *sub, uint32_t slen) {
+  if (r >= S.max_keys) return false;
+  const drp_changes &c = S.cols;
+  if (((c.flags[r] & DRP_F_SUBSET) != 0) != has || c.key_len[r] != klen || c.subset_len[r] != slen) return false;
+  const uint64_t at = S.payload_off[r], len = S.payload_len[r];
+  if (len > S.arena_bytes || at > S.arena_bytes - len || (uint64_t)klen + slen > len) return false;
+  const uint8_t *a = S.arena + at;
+  return bytes_eq(a, key, klen) && bytes_eq(a + klen, sub, slen);
+}
+
+__global__ __launch_bounds__(ST_BLK) void st_lookup_kernel(const StoreMerge M) {
+  __shared__ uint32_t wcnt[ST_WAVES][ST_MISC];
+  __shared__ uint64_t wdead[ST_WAVES];
+  const StoreDev &S = M.s;
+  const uint64_t i = (uint64_t)blockIdx.x * ST_BLK + threadIdx.x;
+  uint32_t code = ST_NONE, alloc = 0;
+  uint64_t where = 0, h = 0, dead = 0;
+  if (i < *M.nw && i < M.n) {
+    const uint32_t fl = M.w.flags[i];
+    const bool has = (fl & DRP_F_SUBSET) != 0, hv = (fl & DRP_F_VALUE) != 0;
+    const uint64_t koff = M.w.key_off[i], soff = M.w.subset_off[i], voff = M.w.value_off[i];
+    const uint32_t klen = M.w.key_len[i], slen = has ? M.w.subset_len[i] : 0, vlen = hv ? M.w.value_len[i] : 0;
+    const uint64_t plen = (uint64_t)klen + slen + vlen;
+    RowSrc W = {};
+    W.nbytes = M.nbytes;
+    // (a winner's key and subset lie inside the wire: it was a candidate; its value need not)
+    if (!wire_has(W, koff, klen) || (has && !wire_has(W, soff, slen)) || (hv && !wire_has(W, voff, vlen)) ||
+        plen > 0xFFFFFFF0ull) {
+      code = ST_SKIPPED;
+    } else {
+      const uint8_t *key = M.bytes + koff, *sub = M.bytes + soff, *val = M.bytes + voff;
+      h = xxh::xxh64(key, klen);
+      if (has) h = xxh::merge(h, xxh::xxh64(sub, slen));
+      h &= S.hash_mask;
+      const uint64_t smask = S.nslots - 1;
+      uint64_t s = h & smask, r = ~0ull;
+      code = ST_SKIPPED;  // (a table without a free slot: not reached, it is at most half full)
+      uint64_t step = 0;
+      while (step < S.nslots) {
+        // to the next free slot or tag match, then (outside that loop) the byte compare
+        uint64_t seen = 0;
+        for (; step < S.nslots; step++, s = (s + 1) & smask) {
+          seen = ld_agent(S.table + s);
+          if (seen == 0 || ((seen ^ h) & ST_TAG) == 0) break;
+        }
+        if (step == S.nslots) break;
+        if (seen == 0) {
+          code = ST_INSERT;
+          where = s;
+          break;
+        }
+        if (st_same(S, (seen & ~ST_TAG) - 1, has, key, klen, sub, slen)) {
+          r = (seen & ~ST_TAG) - 1;
+          break;
+        }
+        step++;
+        s = (s + 1) & smask;
+      }
+      if (r != ~0ull) {
+        const drp_changes &c = S.cols;
+        const uint64_t sch = c.change[r], wch = M.w.change[i];
+        where = r;
+        if (sch > wch) {
+          code = ST_STALE;
+        } else if (sch == wch && c.from[r] == M.w.from[i] && c.to[r] == M.w.to[i] &&
+                   (c.flags[r] & (DRP_F_SUBSET | DRP_F_VALUE)) == fl && c.value_len[r] == vlen &&
+                   (uint64_t)S.payload_len[r] == plen &&
+                   bytes_eq(S.arena + S.payload_off[r] + klen + slen, val, vlen)) {
+          code = ST_UNCHANGED;
+        } else {
+          code = ST_REPLACE;
+          dead = st_r16(S.payload_len[r]);
+        }
+      }
+      if (code == ST_INSERT || code == ST_REPLACE) alloc = st_r16((uint32_t)plen);
+    }
+  }
+  // the workgroup's sums, and this winner's place among its inserted winners and in its bytes
+  const uint32_t wv = threadIdx.x >> 6, lane = lane_id();
+  const uint64_t bi = __ballot(code == ST_INSERT), br = __ballot(code == ST_REPLACE),
+                 bu = __ballot(code == ST_UNCHANGED), bs = __ballot(code == ST_STALE),
+                 bk = __ballot(code == ST_SKIPPED);
+  const uint64_t dsum = wave_sum64(dead);
+  if (lane == 0) {
+    wcnt[wv][0] = (uint32_t)__popcll(bi);
+    wcnt[wv][1] = (uint32_t)__popcll(br);
+    wcnt[wv][2] = (uint32_t)__popcll(bu);
+    wcnt[wv][3] = (uint32_t)__popcll(bs);
+    wcnt[wv][4] = (uint32_t)__popcll(bk);
+    wdead[wv] = dsum;
+  }
+  uint64_t btotal;
+  const uint64_t before = st_block_prefix(alloc, btotal);  // (its barrier publishes wcnt and wdead too)
+  uint32_t irank = (uint32_t)__popcll(bi & ((1ull << lane) - 1ull));
+  for (uint32_t k = 0; k < wv; k++) irank += wcnt[k][0];
+  M.where[i] = where;  // (i < nblk * ST_BLK: the state covers whole workgroups)
+  M.hash[i] = h;
+  M.boff[i] = before;
+  M.alloc[i] = alloc;
+  M.meta[i] = code | (irank << 8);
+  if (threadIdx.x < ST_MISC + 1) {
+    uint64_t t = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < ST_WAVES; k++) t += threadIdx.x < ST_MISC ? (uint64_t)wcnt[k][threadIdx.x] : wdead[k];
+    if (threadIdx.x == 0) {
+      M.blk_ins[blockIdx.x] = t;
+      M.blk_bytes[blockIdx.x] = btotal;
+    } else {
+      M.blk_misc[(uint64_t)blockIdx.x * ST_MISC + threadIdx.x - 1] = t;  // [4]: the dead bytes
+    }
+  }
+}
+
+// one workgroup: the sums the scans did not take, the verdict, the record's last-merge group
+__global__ __launch_bounds__(ST_BLK) void st_verdict_kernel(const StoreMerge M) {
+  __shared__ uint64_t part[ST_WAVES][ST_MISC];
+  uint64_t s[ST_MISC] = {};
+  for (uint64_t b = threadIdx.x; b < M.nblk; b += ST_BLK)
+#pragma unroll
+    for (uint32_t k = 0; k < ST_MISC; k++) s[k] += M.blk_misc[b * ST_MISC + k];
+#pragma unroll
+  for (uint32_t k = 0; k < ST_MISC; k++) {
+    s[k] = wave_sum64(s[k]);
+    if (lane_id() == 0) part[threadIdx.x >> 6][k] = s[k];
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+#pragma unroll
+  for (uint32_t k = 0; k < ST_MISC; k++) {
+    s[k] = 0;
+    for (uint32_t w = 0; w < ST_WAVES; w++) s[k] += part[w][k];
+  }
+  drp_store_info *I = M.s.info;
+  const uint64_t ins = M.ctl[0], bytes = M.ctl[1], nw = umin64(*M.nw, M.n);
+  const uint64_t rows = umin64(I->rows, M.s.max_keys), used = umin64(I->arena_used, M.s.arena_bytes);
+  I->winners = nw;
+  I->inserted = ins;
+  I->replaced = s[0];
+  I->unchanged = s[1];
+  I->stale = s[2];
+  I->skipped = s[3];
+  I->refused = (ins > M.s.max_keys - rows || bytes > M.s.arena_bytes - used) ? 1 : 0;
+  I->need_rows = ins;
+  I->need_bytes = bytes;
+  M.ctl[2] = s[4];
+}
+
+__global__ __launch_bounds__(ST_BLK) void st_claim_kernel(const StoreMerge M) {
+  const StoreDev &S = M.s;
+  const uint64_t i = (uint64_t)blockIdx.x * ST_BLK + threadIdx.x;
+  if (i >= *M.nw || i >= M.n || S.info->refused) return;
+  const uint32_t meta = M.meta[i];
+  if ((meta & 0xFF) != ST_INSERT) return;
+  const uint64_t row = S.info->rows + M.blk_ins[blockIdx.x] + (meta >> 8);  // (< max_keys: the verdict)
+  const uint64_t word = (M.hash[i] & ST_TAG) | (row + 1), smask = S.nslots - 1;
+  uint64_t s = M.where[i];
+  for (uint64_t step = 0; step < S.nslots; step++, s = (s + 1) & smask) {
+    uint64_t seen = 0;
+    if (__hip_atomic_compare_exchange_strong(S.table + s, &seen, word, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_AGENT))
+      break;
+  }
+  M.where[i] = row;  // (read by this winner's lanes of st_write only)
+}
+
+// bytes [p0, p0 + 16) of key | subset | value, zeros past its end
+__device__ __forceinline__ uint4 st_chunk(const uint8_t *key, uint32_t klen, const uint8_t *sub, uint32_t slen,
+                                          const uint8_t *val, uint32_t vlen, uint32_t p0) {
+  const uint32_t ks = klen + slen, plen = ks + vlen;
+  uint64_t lo = 0, hi = 0;
+  if (p0 >= ks && p0 + 16 <= plen) {
+    lo = xxh::rd64(val + (p0 - ks));
+    hi = xxh::rd64(val + (p0 - ks) + 8);
+  } else {
+#pragma unroll
+    for (uint32_t b = 0; b < 16; b++) {
+      const uint32_t p = p0 + b;
+      uint64_t x = 0;
+      if (p < klen) x = key[p];
+      else if (p < ks) x = sub[p - klen];
+      else if (p < plen) x = val[p - ks];
+      if (b < 8) lo |= x << (8 * b);
+      else hi |= x << (8 * (b - 8));
+    }
+  }
+  return make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
+}
+
+__global__ __launch_bounds__(ST_BLK) void st_write_kernel(const StoreMerge M) {
+  const StoreDev &S = M.s;
+  const uint64_t t = (uint64_t)blockIdx.x * ST_BLK + threadIdx.x, i = t / ST_GRP;
+  const uint32_t g = (uint32_t)(t % ST_GRP);
+  if (i >= *M.nw || i >= M.n || S.info->refused) return;
+  const uint32_t code = M.meta[i] & 0xFF;
+  if (code != ST_INSERT && code != ST_REPLACE) return;
+  const uint64_t row = M.where[i], at = S.info->arena_used + M.blk_bytes[i / ST_BLK] + M.boff[i];
+  const uint32_t alloc = M.alloc[i];
+  // (the verdict keeps both inside the store; a record a caller has overwritten must not lead outside)
+  if (row >= S.max_keys || at > S.arena_bytes || alloc > S.arena_bytes - at) return;
+  const uint32_t fl = M.w.flags[i];
+  const uint32_t klen = M.w.key_len[i], slen = (fl & DRP_F_SUBSET) ? M.w.subset_len[i] : 0,
+                 vlen = (fl & DRP_F_VALUE) ? M.w.value_len[i] : 0;
+  const uint8_t *key = M.bytes + M.w.key_off[i], *sub = M.bytes + M.w.subset_off[i], *val = M.bytes + M.w.value_off[i];
+  uint4 *dst = reinterpret_cast<uint4 *>(S.arena + at);  // (16-byte aligned: the arena is, and every allocation)
+  for (uint32_t p0 = g * 16; p0 < alloc; p0 += ST_GRP * 16) dst[p0 >> 4] = st_chunk(key, klen, sub, slen, val, vlen, p0);
+  if (g != 0) return;
+  const drp_changes &c = S.cols;
+  S.payload_off[row] = at;
+  S.payload_len[row] = klen + slen + vlen;
+  S.type[row] = DRP_TYPE_CHANGE;
+  c.key_off[row] = 0;
+  c.key_len[row] = klen;
+  c.subset_off[row] = klen;
+  c.subset_len[row] = slen;
+  c.value_off[row] = klen + slen;
+  c.value_len[row] = vlen;
+  c.change[row] = M.w.change[i];
+  c.from[row] = M.w.from[i];
+  c.to[row] = M.w.to[i];
+  c.flags[row] = (uint8_t)(fl & (DRP_F_SUBSET | DRP_F_VALUE));
+}
+
+__global__ void st_commit_kernel(const StoreMerge M) {
+  drp_store_info *I = M.s.info;
+  if (I->refused) return;
+  I->rows += I->inserted;
+  I->arena_used += I->need_bytes;
+  I->arena_dead += M.ctl[2];
+  I->merges += 1;
+}
+
+// ---- compact ----------------------------------------------------------------------------------
+struct StoreCompact {
+  StoreDev s;
+  uint8_t *arena2;
+  uint64_t arena2_bytes;
+  uint64_t *boff;       // per row: the live bytes of its workgroup's rows before it
+  uint64_t *blk_bytes;  // per workgroup of ST_BLK rows: its live bytes (scanned in place)
+  uint64_t *ctl;        // [0] the live total
+};
+
+__global__ __launch_bounds__(ST_BLK) void stc_size_kernel(const StoreCompact Q) {
+  const uint64_t r = (uint64_t)blockIdx.x * ST_BLK + threadIdx.x;
+  const uint64_t rows = umin64(Q.s.info->rows, Q.s.max_keys);
+  uint64_t total;
+  const uint64_t before = st_block_prefix(r < rows ? st_r16(Q.s.payload_len[r]) : 0, total);
+  if (r < rows) Q.boff[r] = before;
+  if (threadIdx.x == 0) Q.blk_bytes[blockIdx.x] = total;
+}
+
+__global__ void stc_verdict_kernel(const StoreCompact Q) {
+  drp_store_info *I = Q.s.info;
+  const uint64_t live = Q.ctl[0];
+  I->winners = I->inserted = I->replaced = I->unchanged = I->stale = I->skipped = 0;
+  I->need_rows = 0;
+  I->need_bytes = live;
+  I->refused = live > Q.arena2_bytes ? 1 : 0;
+  if (I->refused) return;
+  I->arena_used = live;
+  I->arena_dead = 0;
+}
+
+// ST_GRP lanes per row, 16 bytes per lane and step (both ends are 16-byte aligned); every lane reads
+// the row's old offset before the group's first lane, in the same wave, stores the new one
+__global__ __launch_bounds__(ST_BLK) void stc_copy_kernel(const StoreCompact Q) {
+  const StoreDev &S = Q.s;
+  const uint64_t t = (uint64_t)blockIdx.x * ST_BLK + threadIdx.x, r = t / ST_GRP;
+  const uint32_t g = (uint32_t)(t % ST_GRP);
+  if (r >= umin64(S.info->rows, S.max_keys) || S.info->refused) return;
+  const uint64_t from = S.payload_off[r], to = Q.blk_bytes[r / ST_BLK] + Q.boff[r];
+  const uint64_t alloc = st_r16(S.payload_len[r]);
+  if ((from & 15) || from > S.arena_bytes || alloc > S.arena_bytes - from) return;  // (not a row of ours)
+  if (to > Q.arena2_bytes || alloc > Q.arena2_bytes - to) return;                   // (not reached: the verdict)
+  const uint4 *src = reinterpret_cast<const uint4 *>(S.arena + from);
+  uint4 *dst = reinterpret_cast<uint4 *>(Q.arena2 + to);
+  for (uint64_t k = g; k < alloc / 16; k += ST_GRP) dst[k] = src[k];
+  if (g == 0) S.payload_off[r] = to;
+}
+
+}  // namespace drp
+
+using namespace drp;
+
+static uint64_t st_al(uint64_t x) { return (x + 255) & ~255ull; }
+static uint64_t st_nblk(uint64_t n) { return n ? (n + ST_BLK - 1) / ST_BLK : 1; }
+
+extern "C" uint64_t drp_store_nslots(uint64_t max_keys) {
+  if (max_keys == 0 || max_keys > (1ull << 31)) return 0;
+  uint64_t c = 2;
+  while (c < 2 * max_keys) c <<= 1;
+  return c;
+}
+
+extern "C" hipError_t drp_launch_store_init(const StoreDev *S, hipStream_t st) {
+  if (const hipError_t e = hipMemsetAsync(S->table, 0, S->nslots * 8, st)) return e;
+  if (const hipError_t e = hipMemsetAsync(S->info, 0, sizeof(drp_store_info), st)) return e;
+  return hipMemsetAsync(S->type, 0, S->max_keys, st);
+}
+
+// the merge's state: three 8-byte and two 4-byte words per winner (32 bytes per row of the batch,
+// for whole workgroups), 2 + ST_MISC words per workgroup, the control words
+extern "C" uint64_t drp_store_merge_scratch_bytes(uint64_t n) {
+  const uint64_t nblk = st_nblk(n), m = nblk * ST_BLK;
+  return 3 * st_al(m * 8) + 2 * st_al(m * 4) + 2 * st_al(nblk * 8) + st_al(nblk * ST_MISC * 8) + 256;
+}
+
+extern "C" hipError_t drp_launch_store_merge(const StoreMerge *Mp, void *scratch, hipStream_t st) {
+  StoreMerge M = *Mp;
+  const uint64_t nblk = st_nblk(M.n), m = nblk * ST_BLK;
+  if (nblk >= (1ull << 31) / ST_GRP) return hipErrorInvalidValue;
+  uint8_t *sc = static_cast<uint8_t *>(scratch);
+  auto take = [&](uint64_t bytes) { void *p = sc; sc += st_al(bytes); return p; };
+  M.where = static_cast<uint64_t *>(take(m * 8));
+  M.hash = static_cast<uint64_t *>(take(m * 8));
+  M.boff = static_cast<uint64_t *>(take(m * 8));
+  M.alloc = static_cast<uint32_t *>(take(m * 4));
+  M.meta = static_cast<uint32_t *>(take(m * 4));
+  M.blk_ins = static_cast<uint64_t *>(take(nblk * 8));
+  M.blk_bytes = static_cast<uint64_t *>(take(nblk * 8));
+  M.blk_misc = static_cast<uint64_t *>(take(nblk * ST_MISC * 8));
+  M.ctl = static_cast<uint64_t *>(take(256));
+  M.nblk = nblk;
+  const dim3 grid((uint32_t)nblk), blk(ST_BLK);
+  hipLaunchKernelGGL(st_lookup_kernel, grid, blk, 0, st, M);
+  if (const hipError_t e = drp_launch_count_scan(M.blk_ins, nblk, M.ctl + 0, st)) return e;
+  if (const hipError_t e = drp_launch_count_scan(M.blk_bytes, nblk, M.ctl + 1, st)) return e;
+  hipLaunchKernelGGL(st_verdict_kernel, dim3(1), blk, 0, st, M);
+  hipLaunchKernelGGL(st_claim_kernel, grid, blk, 0, st, M);
+  hipLaunchKernelGGL(st_write_kernel, dim3((uint32_t)(nblk * ST_GRP)), blk, 0, st, M);
+  hipLaunchKernelGGL(st_commit_kernel, dim3(1), dim3(1), 0, st, M);
+  drp_dbg_mark("store_merge", st);
+  return hipGetLastError();
+}
+
+extern "C" uint64_t drp_store_compact_scratch_bytes(uint64_t max_keys) {
+  return st_al(max_keys * 8) + st_al(st_nblk(max_keys) * 8) + 256;
+}
+
+extern "C" hipError_t drp_launch_store_compact(const StoreDev *S, uint8_t *arena2, uint64_t arena2_bytes,
+                                               void *scratch, hipStream_t st) {
+  StoreCompact Q;
+  Q.s = *S;
+  Q.arena2 = arena2;
+  Q.arena2_bytes = arena2_bytes;
+  const uint64_t nblk = st_nblk(S->max_keys);
+  uint8_t *sc = static_cast<uint8_t *>(scratch);
+  Q.boff = reinterpret_cast<uint64_t *>(sc);
+  Q.blk_bytes = reinterpret_cast<uint64_t *>(sc + st_al(S->max_keys * 8));
+  Q.ctl = Q.blk_bytes + st_al(nblk * 8) / 8;
+  const dim3 blk(ST_BLK);
+  hipLaunchKernelGGL(stc_size_kernel, dim3((uint32_t)nblk), blk, 0, st, Q);
+  if (const hipError_t e = drp_launch_count_scan(Q.blk_bytes, nblk, Q.ctl, st)) return e;
+  hipLaunchKernelGGL(stc_verdict_kernel, dim3(1), dim3(1), 0, st, Q);
+  hipLaunchKernelGGL(stc_copy_kernel, dim3((uint32_t)(nblk * ST_GRP)), blk, 0, st, Q);
+  drp_dbg_mark("store_compact", st);
+  return hipGetLastError();
+}

@@ -32,6 +32,8 @@ EXPORTS = [
     "drp_fanout_device", "drp_fanout_staged",
     "drp_latest_device", "drp_latest_staged", "drp_set_latest_hash_mask",
     "drp_fanout_latest_device", "drp_fanout_latest_staged", "drp_set_fanout_latest_pass",
+    "drp_store_table_bytes", "drp_store_init", "drp_store_merge_device", "drp_store_merge_staged",
+    "drp_store_compact", "drp_store_query",
     "drp_comm_id", "drp_comm_init_rank", "drp_comm_init_all", "drp_comm_destroy",
     "drp_index_allgather", "drp_index_allgather_multi", "drp_index_allgather_host", "drp_device_count",
     "drp_host_alloc", "drp_host_free",
@@ -129,6 +131,22 @@ def filter_array(filters):
     return arr
 
 
+class StoreInfo(C.Structure):
+    """drp_store_info: the store's record (device memory; store_query copies it out)."""
+    _fields_ = [(k, U64) for k in ["rows", "arena_used", "arena_dead", "merges", "winners", "inserted", "replaced",
+                                   "unchanged", "stale", "skipped", "refused", "need_rows", "need_bytes",
+                                   "reserved"]]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_ if k != "reserved"}
+
+
+class StoreDesc(C.Structure):
+    """drp_store: a host struct of device pointers; the Store helper below builds one."""
+    _fields_ = [("arena", P), ("arena_bytes", U64), ("frames", Frames), ("cols", Changes), ("max_keys", U64),
+                ("table", P), ("info", P), ("reserved", U64)]
+
+
 class Timing(C.Structure):
     _fields_ = [("decode_ms", C.c_float), ("finalize_ms", C.c_float), ("total_ms", C.c_float),
                 ("strict_reruns", U32), ("spec_repairs", U32), ("exact_retries", U32), ("verify_relisted", U32),
@@ -190,6 +208,14 @@ def lib():
         L.drp_fanout_latest_device.argtypes = L.drp_fanout_device.argtypes[:-1]
         L.drp_fanout_latest_staged.argtypes = L.drp_fanout_staged.argtypes[:7]
         L.drp_set_fanout_latest_pass.argtypes = [P, U32]
+        L.drp_store_table_bytes.argtypes = [U64]
+        L.drp_store_table_bytes.restype = U64
+        L.drp_store_init.argtypes = [P, C.POINTER(StoreDesc)]
+        L.drp_store_merge_device.argtypes = [P, C.POINTER(StoreDesc), P, U64, C.POINTER(Frames), C.POINTER(Changes),
+                                             U64, C.POINTER(Filter)]
+        L.drp_store_merge_staged.argtypes = [P, C.POINTER(StoreDesc), C.POINTER(Filter), C.POINTER(StoreInfo)]
+        L.drp_store_compact.argtypes = [P, C.POINTER(StoreDesc), P, U64]
+        L.drp_store_query.argtypes = [P, C.POINTER(StoreDesc), C.POINTER(StoreInfo)]
         L.drp_index_scan.argtypes = [P, P, U64, P]
         L.drp_stream_stats_from_results.argtypes = [P, P, P, U64, P]
         L.drp_device.argtypes = [P]
@@ -210,7 +236,8 @@ def lib():
                   "drp_encode_device", "drp_encode_batch", "drp_select_device", "drp_relay_staged", "drp_index_scan",
                   "drp_fanout_device", "drp_fanout_staged", "drp_latest_device", "drp_latest_staged",
                   "drp_set_latest_hash_mask", "drp_fanout_latest_device", "drp_fanout_latest_staged",
-                  "drp_set_fanout_latest_pass", "drp_stream_stats_from_results", "drp_device", "drp_comm_id", "drp_comm_init_rank",
+                  "drp_set_fanout_latest_pass", "drp_store_init", "drp_store_merge_device", "drp_store_merge_staged",
+                  "drp_store_compact", "drp_store_query", "drp_stream_stats_from_results", "drp_device", "drp_comm_id", "drp_comm_init_rank",
                   "drp_comm_init_all", "drp_index_allgather", "drp_index_allgather_multi",
                   "drp_index_allgather_host", "drp_device_count"]:
             getattr(L, f).restype = C.c_int
@@ -629,6 +656,151 @@ class Ctx:
         """Test hook: the filters one reduction pass of fanout_latest_device / fanout_latest_staged
         handles (0: the default); results are identical for every value."""
         _chk("drp_set_fanout_latest_pass", self.L.drp_set_fanout_latest_pass(self.h, t))
+
+    # ---- store: the latest Change per key, resident on the device ---------------------------
+    def store_init(self, store):
+        """drp_store_init: an empty store (asynchronous)."""
+        self.order_after_torch(store.arena)
+        _chk("drp_store_init", self.L.drp_store_init(self.h, C.byref(store.desc())))
+        self.order_torch_after(store.arena)
+
+    def store_merge_device(self, store, wire_t, cols, n, filter=None):
+        """drp_store_merge_device: merge the decoded rows [0, n) of a batch (wire_t and cols as
+        latest_device takes them) into the store. Asynchronous; a merge that does not fit is refused on
+        the device (store_query(...).refused)."""
+        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
+        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
+                     tp(cols["flags"]), None)
+        self.order_after_torch(wire_t)
+        rc = self.L.drp_store_merge_device(self.h, C.byref(store.desc()), tp(wire_t), wire_t.numel(), C.byref(fr),
+                                           C.byref(co), n, C.byref(filter) if filter is not None else None)
+        _chk("drp_store_merge_device", rc)
+        self.order_torch_after(wire_t)
+
+    def store_merge_staged(self, store, filter=None):
+        """drp_store_merge_staged over the batch last staged (decode_staged): returns the StoreInfo
+        record; a refused merge raises DrpError(DRP_E_CAPACITY) with .info = the record."""
+        info = StoreInfo()
+        self.order_after_torch(store.arena)
+        rc = self.L.drp_store_merge_staged(self.h, C.byref(store.desc()), C.byref(filter) if filter is not None else None,
+                                           C.byref(info))
+        if rc != DRP_OK:
+            e = DrpError("drp_store_merge_staged", rc)
+            e.info = info
+            raise e
+        return info
+
+    def store_compact(self, store, arena2_t):
+        """drp_store_compact into arena2_t (a uint8 CUDA tensor). Asynchronous; the caller checks
+        store_query(...).refused and, if 0, sets store.arena = arena2_t."""
+        self.order_after_torch(arena2_t)
+        _chk("drp_store_compact", self.L.drp_store_compact(self.h, C.byref(store.desc()), C.c_void_p(arena2_t.data_ptr()),
+                                                           arena2_t.numel()))
+        self.order_torch_after(arena2_t)
+
+    def store_query(self, store):
+        """drp_store_query: waits for the ctx's stream and returns the StoreInfo record."""
+        info = StoreInfo()
+        _chk("drp_store_query", self.L.drp_store_query(self.h, C.byref(store.desc()), C.byref(info)))
+        return info
+
+
+SRC_COLS = ["key_off", "key_len", "subset_off", "subset_len", "value_off", "value_len", "change", "from", "to", "flags"]
+
+
+class Store:
+    """A drp_store in torch tensors on `device`: the arena, the frame and Change columns (max_keys
+    entries each), the identity table and the info record. The columns (self.cols) and the arena are
+    a decoded batch: any *_device relay call of the ctx runs over (store.arena, store.cols,
+    n = max_keys) as it does over a decoded wire."""
+
+    def __init__(self, ctx, max_keys, arena_bytes, device="cuda:0"):
+        import torch
+        self.ctx, self.max_keys = ctx, int(max_keys)
+        dev = torch.device(device)
+        z = lambda n, dt: torch.zeros(max(int(n), 1), dtype=dt, device=dev)
+        self.arena = z(arena_bytes, torch.uint8)
+        self.arena_bytes = int(arena_bytes)
+        self.cols = {"payload_off": z(max_keys, torch.int64), "payload_len": z(max_keys, torch.int32),
+                     "type": z(max_keys, torch.uint8), "flags": z(max_keys, torch.uint8)}
+        for k in COLS32:
+            self.cols[k] = z(max_keys, torch.int32)
+        for k in COLS64:
+            self.cols[k] = z(max_keys, torch.int64)
+        self.table = z(lib().drp_store_table_bytes(self.max_keys) // 8, torch.int64)
+        self.info = z(C.sizeof(StoreInfo) // 8, torch.int64)
+        ctx.store_init(self)
+
+    def desc(self):
+        tp = lambda t: C.c_void_p(t.data_ptr())
+        fr, co = _structs(self.cols, tp)
+        return StoreDesc(tp(self.arena), self.arena_bytes, fr, co, self.max_keys, tp(self.table), tp(self.info))
+
+    def merge_device(self, wire_t, cols, n, filter=None):
+        self.ctx.store_merge_device(self, wire_t, cols, n, filter)
+
+    def merge_staged(self, filter=None):
+        return self.ctx.store_merge_staged(self, filter)
+
+    def query(self):
+        return self.ctx.store_query(self)
+
+    def compact(self, arena2_bytes=None):
+        """Compact into a fresh arena of arena2_bytes (default: the live bytes); returns the record.
+        The store takes the new arena unless the compact was refused."""
+        import torch
+        if arena2_bytes is None:
+            i = self.query()
+            arena2_bytes = i.arena_used - i.arena_dead
+        a2 = torch.zeros(max(int(arena2_bytes), 1), dtype=torch.uint8, device=self.arena.device)
+        # (arena2's true size is passed: the 1-byte stand-in for an empty arena holds nothing)
+        self.ctx.order_after_torch(a2)
+        _chk("drp_store_compact", self.ctx.L.drp_store_compact(self.ctx.h, C.byref(self.desc()),
+                                                               C.c_void_p(a2.data_ptr()), int(arena2_bytes)))
+        self.ctx.order_torch_after(a2)
+        i = self.query()
+        if not i.refused:
+            self.arena, self.arena_bytes = a2, int(arena2_bytes)
+        return i
+
+    def fanout_rows(self, filters, n=None, rows_cap=None):
+        """The existing fanout_device over the store's view, rows [0, n) (default max_keys: the rows
+        past info.rows are no Changes). Returns (out_rows, row_base_t): drp_change_src columns of
+        rows_cap entries (default len(filters) * n) and the int64 tensor of len(filters) + 1 bounds.
+        Asynchronous."""
+        import torch
+        n = self.max_keys if n is None else int(n)
+        K = len(filters)
+        cap = K * n if rows_cap is None else int(rows_cap)
+        dev = self.arena.device
+        rows = {k: torch.zeros(max(cap, 1), dtype=(torch.int32 if k.endswith("_len") else
+                                                   torch.uint8 if k == "flags" else torch.int64), device=dev)
+                for k in SRC_COLS}
+        base = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+        self.ctx.fanout_device(self.arena[:self.arena_bytes] if self.arena_bytes else self.arena[:0], self.cols, n,
+                               filters, rows, cap, None, base)
+        return rows, base
+
+    def fanout(self, filters, n=None):
+        """The catch-up call: one fanout_device over the store and one encode_device with the arena
+        as the heap. filters: make_filter results (peer f at version T: change_range=(T + 1,
+        2**64 - 1), with its subset / key prefix). Returns [wire bytes per filter], in store order."""
+        import torch
+        rows, base = self.fanout_rows(filters, n)
+        rb = [int(v) for v in base.cpu()]  # (torch's stream was ordered after the ctx's)
+        total = rb[-1]
+        if total == 0:
+            return [b""] * len(filters)
+        src = ChangeSrc(*[C.c_void_p(rows[k].data_ptr()) for k in SRC_COLS])
+        need = U64()
+        _chk("drp_encode_size", self.ctx.L.drp_encode_size(self.ctx.h, C.byref(src), total, C.byref(need)))
+        dev = self.arena.device
+        foff = torch.zeros(total + 1, dtype=torch.int64, device=dev)
+        out = torch.zeros(max(int(need.value), 1), dtype=torch.uint8, device=dev)
+        self.ctx.encode_device(rows, self.arena[:self.arena_bytes], total, foff, out, int(need.value))
+        fo, o = foff.cpu().numpy(), out.cpu().numpy()
+        return [o[int(fo[rb[f]]):int(fo[rb[f + 1]])].tobytes() for f in range(len(filters))]
 
 
 class Comm:

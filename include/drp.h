@@ -28,6 +28,11 @@
  *   drp_fanout_latest_device / drp_fanout_latest_staged
  *       -> no reference counterpart: that latest per key under many filters at once, grouped once
  *          (a hub catching up many peers, each at its own version).
+ *   drp_store_init / drp_store_merge_device / drp_store_merge_staged / drp_store_compact /
+ *   drp_store_query / drp_store_table_bytes
+ *       -> no reference counterpart: the latest Change per (subset, key) over every batch merged so
+ *          far, resident in caller-owned device memory in the layout of a decoded batch, so the
+ *          relay calls above run over it unchanged (a hub answering "what changed since T?").
  *   drp_stream_stats + drp_index_scan
  *       -> no reference counterpart (the reference is single-stream); they build the
  *          global frame index after the per-GPU stats tables are all-gathered.
@@ -503,6 +508,97 @@ int drp_fanout_latest_staged(drp_ctx *ctx, const drp_filter *filters, uint32_t n
  * one pass). Results are identical for every value; the scratch grows with it. Test hook, as
  * drp_set_latest_hash_mask, which applies to the two calls as well. */
 int drp_set_fanout_latest_pass(drp_ctx *ctx, uint32_t filters_per_pass);
+
+/* ---- store: the latest Change per key, resident on the device -------------- */
+/* The calls above reduce one decoded batch. A hub receives batches for as long as it runs, and a
+ * peer asks it "what has changed since my version T?". The store is the current state the batches
+ * merge into: one row per identity (subset presence, subset bytes, key bytes), holding the winner of
+ * drp_latest_device over everything merged so far. No reference counterpart (the reference has no
+ * relay); the fields read are those of messages/schema.proto:1-8.
+ *   The store lives in caller-owned device memory; libdrp allocates nothing for it and there is no
+ * open or close. Its rows have the layout of a decoded batch, with the arena in the wire's place:
+ * (s->arena, s->arena_bytes, &s->frames, &s->cols) is a valid input of drp_select_device,
+ * drp_fanout_device, drp_latest_device, drp_fanout_latest_device and (through their rows)
+ * drp_encode_device. frames.type is 0 at and beyond info.rows, so a caller may pass n = max_keys
+ * to any of them without reading the count back: the unused rows are no Changes and select nothing.
+ * A catch-up of K peers at versions T_f is one drp_fanout_device with DRP_SEL_CHANGE_RANGE =
+ * [T_f + 1, 2^64 - 1] over that view and one drp_encode_device.
+ *   Stored form of row r: the payload key | subset | value at arena[payload_off[r]] (a multiple of
+ * 16), payload_len = key_len + subset_len + value_len, type = DRP_TYPE_CHANGE, key_off = 0,
+ * subset_off = key_len, value_off = key_len + subset_len (an absent field has length 0), change /
+ * from / to copied, flags = the source's & (DRP_F_SUBSET | DRP_F_VALUE). An allocation is
+ * payload_len rounded up to 16 bytes; bytes past the payload are zero. Rows stand in the order in
+ * which their identities first entered and keep their index for good. */
+typedef struct drp_store_info { /* one record in device memory, written by the calls below */
+  uint64_t rows;       /* identities held = rows of frames / cols in use */
+  uint64_t arena_used; /* bytes of the arena handed out so far */
+  uint64_t arena_dead; /* of those, bytes of payloads since replaced */
+  uint64_t merges;     /* merges applied (a refused one is not counted) */
+  /* the last merge / compact: */
+  uint64_t winners, inserted, replaced, unchanged, stale, skipped;
+  uint64_t refused; /* 1: it did not fit; nothing but the fields of this group changed */
+  uint64_t need_rows, need_bytes; /* rows it would have added, arena bytes it would have taken */
+  uint64_t reserved; /* 0 (the record is 112 bytes) */
+} drp_store_info;
+
+typedef struct drp_store { /* HOST struct of DEVICE pointers, read before a call returns */
+  uint8_t *arena; /* 16-byte aligned */
+  uint64_t arena_bytes;
+  drp_frames frames; /* max_keys entries each */
+  drp_changes cols;  /* max_keys entries each; cols.key_hash is ignored */
+  uint64_t max_keys; /* 1 .. 2^31 */
+  uint64_t *table;   /* drp_store_table_bytes(max_keys) bytes */
+  drp_store_info *info;
+  uint64_t reserved; /* not read (the struct is 160 bytes) */
+} drp_store;
+
+/* 8 bytes for each slot of the identity table: a power of two >= 2 * max_keys, at least 2.
+ * 0 if max_keys is 0 or above 2^31. */
+uint64_t drp_store_table_bytes(uint64_t max_keys);
+/* An empty store: the table, the info record and frames.type[0, max_keys) zeroed. Asynchronous on
+ * drp_stream(ctx). DRP_E_INVAL: a NULL pointer in *s, an arena that is not 16-byte aligned,
+ * max_keys out of range. */
+int drp_store_init(drp_ctx *ctx, const drp_store *s);
+/* Merge the decoded rows [0, n) of a batch (bytes, frames, cols: drp_latest_device's arguments and
+ * DRP_E_INVAL cases) into the store.
+ *   Winners: exactly the rows drp_latest_device returns for (bytes, nbytes, frames, cols, n, filter).
+ * A winner with DRP_F_VALUE whose value range leaves [0, nbytes) is never read: it counts as
+ * `skipped` and the store keeps what it had (so does one whose three lengths sum past 2^32 - 16).
+ *   Every other winner is looked up by identity. Absent: `inserted` as row info.rows + its rank among
+ * the inserted winners in batch-row order. Present with a greater stored change: `stale`. Present
+ * with equal change, from, to, flags & (SUBSET | VALUE) and value bytes: `unchanged`, nothing is
+ * written (a batch delivered twice costs no arena). Otherwise `replaced` (a greater change, or an
+ * equal one with different content: the later arrival wins, as the later row wins in
+ * drp_latest_device): the row keeps its index, its columns are rewritten, a fresh payload is
+ * appended to the arena and the old allocation is added to arena_dead.
+ *   All or nothing: if rows + inserted > max_keys or arena_used + need_bytes > arena_bytes the merge
+ * is refused: refused = 1, need_rows and need_bytes are set with the other fields of the record's
+ * last-merge group, and nothing else changes (the table neither). The verdict is taken on the
+ * device: the call has no host synchronisation and returns DRP_OK either way; read the record with
+ * drp_store_query. After merges B1 .. Bk under one filter, none refused or skipped, the rows hold
+ * exactly the winners of drp_latest_device over B1 | ... | Bk under that filter.
+ *   Device pointers only; asynchronous on drp_stream(ctx). Scratch from the ctx's (DRP_E_NOMEM if it
+ * cannot be had): drp_latest_device's, and per row of the batch 80 bytes of winner rows and 32
+ * bytes of merge state. */
+int drp_store_merge_device(drp_ctx *ctx, const drp_store *s, const uint8_t *bytes, uint64_t nbytes,
+                           const drp_frames *frames, const drp_changes *cols, uint64_t n, const drp_filter *filter);
+/* That merge over the delivered rows of the batch last staged (the rows, validity rules and
+ * DRP_E_INVAL cases of drp_latest_staged; the same store in every drp_set_blob_skip mode).
+ * Synchronous: *info_host (HOST, may be NULL) receives the record; DRP_E_CAPACITY if the merge was
+ * refused (*info_host is still filled). The staged batch stays valid. */
+int drp_store_merge_staged(drp_ctx *ctx, const drp_store *s, const drp_filter *filter, drp_store_info *info_host);
+/* Copy the live payloads into arena2 (device, 16-byte aligned, arena2_bytes long, not overlapping
+ * the arena) in row order, rewrite payload_off, and set arena_used to the live total and arena_dead
+ * to 0. The table maps identities to rows and is not touched. If the live total exceeds
+ * arena2_bytes the compact is refused on the device (refused = 1, need_bytes = the live total,
+ * nothing else changed); otherwise refused = 0 and the caller puts arena2 and arena2_bytes into its
+ * drp_store. The other fields of the last-merge group are zeroed; merges is not counted.
+ * Asynchronous on drp_stream(ctx), returns DRP_OK either way. */
+int drp_store_compact(drp_ctx *ctx, const drp_store *s, uint8_t *arena2, uint64_t arena2_bytes);
+/* Wait for the ctx's stream and copy the record to *info_host (HOST). */
+int drp_store_query(drp_ctx *ctx, const drp_store *s, drp_store_info *info_host);
+/* drp_set_latest_hash_mask applies to the store's table as well (test hook): a store must see one
+ * mask from drp_store_init on, for its whole life. */
 
 /* ---- multi-GPU global index ---------------------------------------------- */
 /* stats[nranks*per_rank] (device): all-gathered per-stream tables in rank order.

@@ -39,6 +39,20 @@ probe, and the host relay through drp_relay_staged against the host round trip i
               drp_latest_staged calls over the same staged batch, alternating, wall clock, the bytes
               checked to be the same. With --fanout-latest-only every other leg is left out.
 
+  store       (--store-out, default profiles/relay/store_bench.json) The latest leg's frames / 16 keyed
+              stream, decoded once, as 8 equal batches of rows merged one after the other into an empty
+              store (drp_store_merge_device), HIP events around every merge, one warm-up sequence and
+              --store-seqs timed ones; per batch also drp_latest_device alone over the same rows (the
+              merge's first step) and over the rows of all batches so far (what a hub without a store
+              would run), alternating with the merges; then the catch-up (drp_fanout_device over the
+              store's view, n = max_keys, and drp_encode_device with the arena as the heap: what
+              Store.fanout composes) for K = 1, 8, 64 peers at change > floor(100 f / K), and
+              drp_store_compact. The final store is checked against latest_winners. With --store-only
+              every other leg is left out. --store-baseline-out: only the drp_latest_device timings
+              over the same batches, through nothing the store added, so that they can be taken with
+              another commit's library and binding (DRP_LIB, DRP_PY); --store-baseline reads such a
+              file into the result.
+
 Prints one JSON line (and writes it to --out). Needs an MI355X: there is no CPU path.
 
   hipcc -O3 --offload-arch=gfx950 scripts/probe_bw.hip -o exp/probe_bw
@@ -58,7 +72,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-sys.path.insert(0, os.path.join(ROOT, "dat-replication-protocol_amd", "python"))
+# (DRP_PY: another commit's binding directory, with DRP_LIB naming that commit's library: an A/B)
+sys.path.insert(0, os.environ.get("DRP_PY") or os.path.join(ROOT, "dat-replication-protocol_amd", "python"))
 
 READ_B, WRITE_B = 58, 61  # model bytes per row read / per selected row written (no sel_idx)
 SRC_KEYS = ["key_off", "key_len", "subset_off", "subset_len", "value_off", "value_len", "change", "from", "to",
@@ -711,6 +726,156 @@ def fanout_latest_host_leg(ctx, drp_amd, mib, runs, K=16):
             "ranges_overlap": not (max(tf) < min(tq) or max(tq) < min(tf)), "same_bytes": same}
 
 
+# ---- store ----------------------------------------------------------------------------------------
+
+STORE_BATCHES = 8
+
+
+def _store_input(ctx, drp_amd, torch, frames):
+    """The keyed stream decoded once; batch b is rows [b m, (b + 1) m) of its columns over the one wire."""
+    frames -= frames % STORE_BATCHES
+    key_ids = latest_pools(frames)["keys_n_over_16"]
+    wire_t, cols, n = device_setup(ctx, drp_amd, torch, None, frames, wire=keyed_c2_stream(key_ids))
+    return key_ids, wire_t, cols, n, n // STORE_BATCHES
+
+
+def _latest_times(ctx, drp_amd, torch, wire_t, cols, n, m, seqs):
+    """drp_latest_device alone per batch, and over the rows of all batches so far: [seq][batch] ms."""
+    dev = torch.device("cuda", 0)
+    L = ctx.L
+    tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    rows = _row_tensors(torch, dev, n)
+    src = drp_amd.ChangeSrc(*[tp(rows[k]) for k in SRC_KEYS])
+    nsel_t = torch.zeros(1, dtype=torch.int64, device=dev)
+    ext = ctx._ext(dev)
+
+    def latest(a, b):
+        fr = drp_amd.Frames(tp(cols["payload_off"][a:]), tp(cols["payload_len"][a:]), tp(cols["type"][a:]))
+        co = drp_amd.Changes(*[tp(cols[k][a:]) for k in drp_amd.COLS32], tp(cols["change"][a:]), tp(cols["from"][a:]),
+                             tp(cols["to"][a:]), tp(cols["flags"][a:]), None)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record(ext)
+        rc = L.drp_latest_device(ctx.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), b - a, None, C.byref(src),
+                                 None, tp(nsel_t))
+        e1.record(ext)
+        e1.synchronize()
+        assert rc == 0, rc
+        return e0.elapsed_time(e1)
+
+    alone, concat = [], []
+    for it in range(seqs + 1):  # (one warm-up sequence)
+        ta = [latest(b * m, (b + 1) * m) for b in range(STORE_BATCHES)]
+        tc = [latest(0, (b + 1) * m) for b in range(STORE_BATCHES)]
+        if it:
+            alone.append(ta)
+            concat.append(tc)
+    return alone, concat, latest
+
+
+def _per_batch(seq_times):
+    return [_stat([t[b] for t in seq_times]) for b in range(STORE_BATCHES)]
+
+
+def store_baseline(ctx, drp_amd, torch, frames, seqs):
+    key_ids, wire_t, cols, n, m = _store_input(ctx, drp_amd, torch, frames)
+    alone, concat, _ = _latest_times(ctx, drp_amd, torch, wire_t, cols, n, m, seqs)
+    return {"bench": "relay_store_baseline", "frames": n, "batch_rows": m, "seqs": seqs,
+            "latest_alone_ms": _per_batch(alone), "latest_concat_ms": _per_batch(concat)}
+
+
+def store_leg(ctx, drp_amd, torch, frames, seqs, iters):
+    dev = torch.device("cuda", 0)
+    key_ids, wire_t, cols, n, m = _store_input(ctx, drp_amd, torch, frames)
+    keys = int(len(np.unique(key_ids)))
+    want = latest_winners(key_ids)
+    ext = ctx._ext(dev)
+    arena_bytes = 80 * (keys + STORE_BATCHES * m) // 2  # (74-byte payloads; about 0.86 m winners a batch)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record(ext)
+        fn()
+        e1.record(ext)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    merges, infos, compacts, store = [], [], [], None
+    for it in range(seqs + 1):  # (one warm-up sequence; every sequence starts from an empty store)
+        store = None
+        torch.cuda.empty_cache()
+        store = drp_amd.Store(ctx, keys, arena_bytes)
+        tm = []
+        for b in range(STORE_BATCHES):
+            view = {k: v[b * m:] for k, v in cols.items()}
+            tm.append(timed(lambda: ctx.store_merge_device(store, wire_t, view, m)))
+            if it == 1:
+                infos.append(store.query().as_dict())
+        a2 = torch.zeros(store.query().arena_used, dtype=torch.uint8, device=dev)
+        before = store.query()
+        tc = timed(lambda: ctx.store_compact(store, a2))
+        after = store.query()
+        assert after.refused == 0 and after.arena_used == before.arena_used - before.arena_dead and after.arena_dead == 0
+        store.arena, store.arena_bytes = a2, a2.numel()
+        if it:
+            merges.append(tm)
+            compacts.append(tc)
+    # the final store against the numpy side: every key's winner, its change and from
+    info = store.query()
+    assert info.rows == keys == len(want) and info.refused == 0, (info.rows, keys)
+    got = np.sort(store.cols["change"][:keys].cpu().numpy() * 128 + store.cols["from"][:keys].cpu().numpy())
+    assert np.array_equal(got, np.sort((want % 100 + 1) * 128 + want % 128)), "store rows"
+    alone, concat, _ = _latest_times(ctx, drp_amd, torch, wire_t, cols, n, m, seqs)
+    res = {"frames": n, "batches": STORE_BATCHES, "batch_rows": m, "keys": keys, "seqs": seqs,
+           "merge_ms": _per_batch(merges), "latest_alone_ms": _per_batch(alone), "latest_concat_ms": _per_batch(concat),
+           "merge_info": infos, "compact_ms": _stat(compacts), "compact_live_bytes": int(info.arena_used),
+           "arena_bytes": arena_bytes, "table_bytes": int(store.table.numel() * 8)}
+    res["merge_over_latest_alone"] = [a["median"] / b["median"] for a, b in zip(res["merge_ms"], res["latest_alone_ms"])]
+    res["latest_concat_over_merge"] = [a["median"] / b["median"] for a, b in zip(res["latest_concat_ms"], res["merge_ms"])]
+    res["sum_merge_ms"] = sum(a["median"] for a in res["merge_ms"])
+    res["sum_latest_alone_ms"] = sum(a["median"] for a in res["latest_alone_ms"])
+    res["sum_latest_concat_ms"] = sum(a["median"] for a in res["latest_concat_ms"])
+    del wire_t, cols
+    torch.cuda.empty_cache()
+    # catch-up: what Store.fanout composes, over preallocated outputs
+    tp = lambda t: C.c_void_p(t.data_ptr())
+    ch = store.cols["change"][:keys].cpu().numpy()
+    res["catch_up"] = {}
+    for K in (1, 8, 64):
+        ts_ = [(100 * f) // K for f in range(K)]
+        flt = [drp_amd.make_filter(change_range=(t + 1, 2**64 - 1)) for t in ts_]
+        counts = [int((ch > t).sum()) for t in ts_]
+        total = sum(counts)
+        rows = _row_tensors(torch, dev, total)
+        rb_t = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+        foff = torch.zeros(total + 1, dtype=torch.int64, device=dev)
+        out = torch.zeros(total * 86, dtype=torch.uint8, device=dev)
+
+        def fan():
+            ctx.fanout_device(store.arena, store.cols, store.max_keys, flt, rows, total, None, rb_t)
+
+        def enc():
+            ctx.encode_device(rows, store.arena, total, foff, out, out.numel())
+
+        tf, te = [], []
+        for it in range(iters + 3):
+            a, b = timed(fan), timed(enc)
+            if it >= 3:
+                tf.append(a)
+                te.append(b)
+        rb = rb_t.cpu().numpy()
+        assert [int(rb[f + 1] - rb[f]) for f in range(K)] == counts, "catch-up counts"
+        assert int(foff[total].cpu()) == total * 86, "catch-up bytes"  # (every frame is 86 bytes again)
+        res["catch_up"][f"K{K}"] = {"filters": K, "rows_out": total, "out_bytes": total * 86, "fanout_ms": _stat(tf),
+                                    "encode_ms": _stat(te),
+                                    "total_ms_median": statistics.median(tf) + statistics.median(te)}
+        print("store catch-up", K, res["catch_up"][f"K{K}"], file=sys.stderr, flush=True)
+        rows = foff = out = None
+        torch.cuda.empty_cache()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20_000_000)
@@ -727,7 +892,17 @@ def main():
                     help="run the fan-out-of-latest legs too and write their JSON line here")
     ap.add_argument("--fanout-latest-only", action="store_true",
                     help="with --fanout-latest-out: leave the other legs out")
+    ap.add_argument("--store-out", nargs="?", default=None,
+                    const=os.path.join(ROOT, "profiles", "relay", "store_bench.json"),
+                    help="run the store leg too and write its JSON line here")
+    ap.add_argument("--store-only", action="store_true", help="with --store-out: leave the other legs out")
+    ap.add_argument("--store-seqs", type=int, default=5, help="timed sequences of 8 merges")
+    ap.add_argument("--store-baseline-out", default=None,
+                    help="only drp_latest_device over the store leg's batches (any commit's library), written here")
+    ap.add_argument("--store-baseline", default=None, help="such a file of the parent commit, read into the store leg's result")
     a = ap.parse_args()
+    if a.store_only and not a.store_out:
+        ap.error("--store-only needs --store-out")
     if a.latest_only and not a.latest_out:
         ap.error("--latest-only needs --latest-out")
     if a.fanout_latest_only and not a.fanout_latest_out:
@@ -741,6 +916,33 @@ def main():
     torch.cuda.init()
     import _streams as S
     import drp_amd
+    if a.store_baseline_out:
+        with drp_amd.Ctx(0) as ctx:
+            base = store_baseline(ctx, drp_amd, torch, a.frames, a.store_seqs)
+        with open(a.store_baseline_out, "w") as f:
+            f.write(json.dumps(base) + "\n")
+        print(json.dumps(base))
+        return
+    if a.store_out:
+        with drp_amd.Ctx(0) as ctx:
+            st = {"bench": "relay_store", "device": store_leg(ctx, drp_amd, torch, a.frames, a.store_seqs, a.iters)}
+        if a.store_baseline:
+            parent = json.loads(open(a.store_baseline).read())
+            d = st["device"]
+            assert parent["frames"] == d["frames"] and parent["batch_rows"] == d["batch_rows"]
+            d["parent_latest_alone_ms"] = parent["latest_alone_ms"]
+            d["parent_latest_concat_ms"] = parent["latest_concat_ms"]
+            d["merge_over_parent_latest_alone"] = [x["median"] / y["median"] for x, y in
+                                                   zip(d["merge_ms"], parent["latest_alone_ms"])]
+            d["parent_latest_concat_over_merge"] = [x["median"] / y["median"] for x, y in
+                                                    zip(parent["latest_concat_ms"], d["merge_ms"])]
+            d["sum_parent_latest_alone_ms"] = sum(x["median"] for x in parent["latest_alone_ms"])
+            d["sum_parent_latest_concat_ms"] = sum(x["median"] for x in parent["latest_concat_ms"])
+        with open(a.store_out, "w") as f:
+            f.write(json.dumps(st) + "\n")
+        print(json.dumps(st))
+        if a.store_only:
+            return
     if a.fanout_latest_out:
         with drp_amd.Ctx(0) as ctx:
             ctx.set_blob_skip(drp_amd.BLOB_SKIP_OFF)
