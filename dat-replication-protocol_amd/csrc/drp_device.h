@@ -509,29 +509,26 @@ __device__ __forceinline__ uint32_t rd32(const uint8_t *p) {
   return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
 }
 
-// XXH64, seed 0 (the published algorithm; tests check it against python-xxhash)
-__device__ inline uint64_t xxh64(const uint8_t *p, uint32_t len) {
-  const uint8_t *end = p + len;
-  uint64_t h;
-  if (len >= 32) {
-    uint64_t v1 = P1 + P2, v2 = P2, v3 = 0, v4 = 0 - P1;
-    const uint8_t *lim = end - 32;
-    do {
-      v1 = round1(v1, rd64(p));
-      v2 = round1(v2, rd64(p + 8));
-      v3 = round1(v3, rd64(p + 16));
-      v4 = round1(v4, rd64(p + 24));
-      p += 32;
-    } while (p <= lim);
-    h = rotl(v1, 1) + rotl(v2, 7) + rotl(v3, 12) + rotl(v4, 18);
-    h = merge(h, v1);
-    h = merge(h, v2);
-    h = merge(h, v3);
-    h = merge(h, v4);
-  } else {
-    h = P5;
-  }
-  h += len;
+__device__ __forceinline__ uint64_t avalanche(uint64_t h) {
+  h ^= h >> 33;
+  h *= P2;
+  h ^= h >> 29;
+  h *= P3;
+  h ^= h >> 32;
+  return h;
+}
+// the four stripe accumulators' start values, and what they come to after the last stripe
+__device__ __forceinline__ uint64_t acc0(uint32_t j) { return j == 0 ? P1 + P2 : j == 1 ? P2 : j == 2 ? 0 : 0 - P1; }
+__device__ __forceinline__ uint64_t converge(uint64_t v1, uint64_t v2, uint64_t v3, uint64_t v4) {
+  uint64_t h = rotl(v1, 1) + rotl(v2, 7) + rotl(v3, 12) + rotl(v4, 18);
+  h = merge(h, v1);
+  h = merge(h, v2);
+  h = merge(h, v3);
+  return merge(h, v4);
+}
+// XXH64's end: h (the converged accumulators, or P5 for fewer than 32 bytes, plus the length) over
+// the bytes [p, end) behind the last stripe (fewer than 32)
+__device__ __forceinline__ uint64_t finish(uint64_t h, const uint8_t *p, const uint8_t *end) {
   while (p + 8 <= end) {
     h ^= round1(0, rd64(p));
     h = rotl(h, 27) * P1 + P4;
@@ -547,12 +544,26 @@ __device__ inline uint64_t xxh64(const uint8_t *p, uint32_t len) {
     h = rotl(h, 11) * P1;
     p++;
   }
-  h ^= h >> 33;
-  h *= P2;
-  h ^= h >> 29;
-  h *= P3;
-  h ^= h >> 32;
-  return h;
+  return avalanche(h);
+}
+
+// XXH64, seed 0 (the published algorithm; tests check it against python-xxhash)
+__device__ inline uint64_t xxh64(const uint8_t *p, uint32_t len) {
+  const uint8_t *end = p + len;
+  uint64_t h = P5;
+  if (len >= 32) {
+    uint64_t v1 = acc0(0), v2 = acc0(1), v3 = acc0(2), v4 = acc0(3);
+    const uint8_t *lim = end - 32;
+    do {
+      v1 = round1(v1, rd64(p));
+      v2 = round1(v2, rd64(p + 8));
+      v3 = round1(v3, rd64(p + 16));
+      v4 = round1(v4, rd64(p + 24));
+      p += 32;
+    } while (p <= lim);
+    h = converge(v1, v2, v3, v4);
+  }
+  return finish(h + len, p, end);
 }
 
 }  // namespace xxh

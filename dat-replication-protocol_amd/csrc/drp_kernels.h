@@ -260,6 +260,25 @@ struct StoreMerge {
 constexpr uint32_t ST_BLK = 256, ST_WAVES = ST_BLK / 64, ST_MISC = 5;
 constexpr uint32_t ST_GRP = 16;  // lanes that copy one payload, 16 bytes each per step
 
+// drp_digest.hip: the bucket digest of the select's candidates whose ranges lie inside the wire
+// (dig_cells: cells, totals), and the count step of the select restricted to the buckets of a set
+// (dig_count: bucket_set; sel's scratch and outputs as drp_select.hip's)
+struct DigestParams {
+  SelectParams sel;
+  uint32_t bits;    // 0 .. DRP_DIGEST_MAX_BITS: 2^bits cells, bucket = the identity hash's high bits
+  uint32_t chunks;  // dig_cells: chunks of SEL_BLK consecutive rows per workgroup (set by the launcher)
+  drp_digest_cell *cells;  // zero before dig_cells
+  uint64_t *totals;        // zero before dig_cells; may be null
+  const uint64_t *bucket_set;
+};
+// up to this many bits a workgroup of dig_cells sums into a copy of the cells in LDS (16 KB) and adds
+// its non-empty cells to the global ones at its end; above, every row adds to the global cells
+constexpr uint32_t DIG_LDS_BITS = 10;
+// a dig_cells workgroup takes up to DIG_CHUNKS chunks of SEL_BLK consecutive rows, one row per lane (the
+// more rows, the more of them share a cell of its LDS copy), but no more than leave DIG_GRID_MIN
+// workgroups: a small batch of long values needs the compute units more than the sharing
+constexpr uint32_t DIG_CHUNKS = 4, DIG_GRID_MIN = 128;
+
 }  // namespace drp
 
 extern "C" {
@@ -360,6 +379,15 @@ hipError_t drp_launch_store_merge(const drp::StoreMerge *M, void *scratch, hipSt
 uint64_t drp_store_compact_scratch_bytes(uint64_t max_keys);
 hipError_t drp_launch_store_compact(const drp::StoreDev *S, uint8_t *arena2, uint64_t arena2_bytes, void *scratch,
                                     hipStream_t st);
+// drp_digest.hip. The cells and totals of D (both cleared first); bucket_set and *n_diff from two cell
+// arrays of 2^bits; the select over D's candidates in the buckets of D->bucket_set (scratch:
+// drp_select_scratch_bytes(n), as drp_launch_select; drp_launch_digest takes its first
+// 2 * DRP_SEL_MAX_BYTES bytes for the filter's byte strings)
+hipError_t drp_launch_digest(const drp::DigestParams *D, const drp::SelectBytes *fb, void *scratch, hipStream_t st);
+hipError_t drp_launch_digest_diff(const drp_digest_cell *a, const drp_digest_cell *b, uint32_t bits,
+                                  uint64_t *bucket_set, uint64_t *n_diff, hipStream_t st);
+hipError_t drp_launch_select_buckets(const drp::DigestParams *D, const drp::SelectBytes *fb, void *scratch,
+                                     hipStream_t st);
 hipError_t drp_launch_fanout_scatter(const drp::FanParams *P, hipStream_t st);
 hipError_t drp_launch_fanout_splice(const drp::FanParams *P, hipStream_t st);
 // out_off[f] = frame_off[row_base[f]] (f <= nfilters); blob_pos[f * nb + j] = frame_off[row_base[f] +

@@ -3,9 +3,10 @@
 // the batch last staged (select or latest per key, then the encoder with the staged wire as its
 // heap), drp_fanout_device / drp_fanout_staged (many filters over one pass) and
 // drp_fanout_latest_device / drp_fanout_latest_staged (latest per key under each), and the store
-// (drp_store_*: the latest-per-key step, then the merge into caller-owned device memory). The kernels
-// are in drp_select.hip, drp_latest.hip, drp_fanout.hip and drp_store.hip; the context is
-// drp_api.hip's (drp_ctx.h).
+// (drp_store_*: the latest-per-key step, then the merge into caller-owned device memory), and the
+// digest calls (drp_digest_device, drp_digest_diff_device, drp_select_buckets_device). The kernels
+// are in drp_select.hip, drp_latest.hip, drp_fanout.hip, drp_store.hip and drp_digest.hip; the
+// context is drp_api.hip's (drp_ctx.h).
 #include <algorithm>
 #include <cstring>
 
@@ -15,10 +16,13 @@
 using namespace drp;
 
 // the decoded columns and the caller's row arrays are all there (n > 0)
-static bool rows_ok(const drp_frames *frames, const drp_changes *cols, const drp_change_src *out_rows, uint64_t n) {
+static bool cols_ok(const drp_frames *frames, const drp_changes *cols, uint64_t n) {
   return !n || (frames->payload_off && frames->type && cols->key_off && cols->key_len && cols->subset_off &&
                 cols->subset_len && cols->value_off && cols->value_len && cols->change && cols->from && cols->to &&
-                cols->flags && out_rows->key_off && out_rows->key_len && out_rows->subset_off &&
+                cols->flags);
+}
+static bool rows_ok(const drp_frames *frames, const drp_changes *cols, const drp_change_src *out_rows, uint64_t n) {
+  return !n || (cols_ok(frames, cols, n) && out_rows->key_off && out_rows->key_len && out_rows->subset_off &&
                 out_rows->subset_len && out_rows->value_off && out_rows->value_len && out_rows->change &&
                 out_rows->from && out_rows->to && out_rows->flags);
 }
@@ -411,7 +415,61 @@ static int store_query(drp_ctx *c, const drp_store_info *dev, drp_store_info *ho
   return DRP_OK;
 }
 
+// ---- digest / reconcile ---------------------------------------------------------------------------
+// the arguments drp_digest_device and drp_select_buckets_device share, into D (out_rows NULL: the
+// digest, which writes no rows)
+static int digest_params(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                         const drp_changes *cols, uint64_t n, const drp_filter *filter, uint32_t bits,
+                         const drp_change_src *out_rows, DigestParams &D, SelectBytes &fb) {
+  if (!c || !frames || !cols || (!bytes && nbytes) || bits > DRP_DIGEST_MAX_BITS) return DRP_E_INVAL;
+  if (out_rows ? !rows_ok(frames, cols, out_rows, n) : !cols_ok(frames, cols, n)) return DRP_E_INVAL;
+  if (const int rc = select_filter(filter, D.sel.f, fb.b)) return rc;
+  D.sel.src = caller_src(bytes, nbytes, frames, cols, n);
+  D.bits = bits;
+  return DRP_OK;
+}
+
 extern "C" {
+
+int drp_digest_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                      const drp_changes *cols, uint64_t n, const drp_filter *filter, uint32_t bits,
+                      drp_digest_cell *cells, uint64_t *totals) {
+  DigestParams D = {};
+  SelectBytes fb = {};
+  if (!cells) return DRP_E_INVAL;
+  if (const int rc = digest_params(c, bytes, nbytes, frames, cols, n, filter, bits, nullptr, D, fb)) return rc;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  if (!c->scratch.ensure(2 * DRP_SEL_MAX_BYTES)) return DRP_E_NOMEM;
+  D.cells = cells;
+  D.totals = totals;
+  CHK(drp_launch_digest(&D, &fb, c->scratch.p, c->st));
+  return DRP_OK;
+}
+
+int drp_digest_diff_device(drp_ctx *c, const drp_digest_cell *a, const drp_digest_cell *b, uint32_t bits,
+                           uint64_t *bucket_set, uint64_t *n_diff) {
+  if (!c || !a || !b || !bucket_set || !n_diff || bits > DRP_DIGEST_MAX_BITS) return DRP_E_INVAL;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  CHK(drp_launch_digest_diff(a, b, bits, bucket_set, n_diff, c->st));
+  return DRP_OK;
+}
+
+int drp_select_buckets_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                              const drp_changes *cols, uint64_t n, const drp_filter *filter, uint32_t bits,
+                              const uint64_t *bucket_set, const drp_change_src *out_rows, uint64_t *sel_idx,
+                              uint64_t *n_selected) {
+  DigestParams D = {};
+  SelectBytes fb = {};
+  if (!bucket_set || !out_rows || !n_selected) return DRP_E_INVAL;
+  if (const int rc = digest_params(c, bytes, nbytes, frames, cols, n, filter, bits, out_rows, D, fb)) return rc;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  if (!c->scratch.ensure(drp_select_scratch_bytes(n))) return DRP_E_NOMEM;
+  D.bucket_set = bucket_set;
+  D.sel.out = row_out(out_rows, sel_idx);
+  D.sel.n_selected = n_selected;
+  CHK(drp_launch_select_buckets(&D, &fb, c->scratch.p, c->st));
+  return DRP_OK;
+}
 
 uint64_t drp_store_table_bytes(uint64_t max_keys) { return 8 * drp_store_nslots(max_keys); }
 
@@ -427,10 +485,7 @@ int drp_store_merge_device(drp_ctx *c, const drp_store *s, const uint8_t *bytes,
                            const drp_frames *frames, const drp_changes *cols, uint64_t n, const drp_filter *filter) {
   StoreDev D = {};
   if (!c || !s || !frames || !cols || (!bytes && nbytes) || !store_dev(c, s, D)) return DRP_E_INVAL;
-  if (n && !(frames->payload_off && frames->type && cols->key_off && cols->key_len && cols->subset_off &&
-             cols->subset_len && cols->value_off && cols->value_len && cols->change && cols->from && cols->to &&
-             cols->flags))
-    return DRP_E_INVAL;
+  if (!cols_ok(frames, cols, n)) return DRP_E_INVAL;
   const RowSrc R = caller_src(bytes, nbytes, frames, cols, n);
   return store_merge(c, D, &R, filter);
 }

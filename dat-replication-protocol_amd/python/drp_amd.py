@@ -34,6 +34,7 @@ EXPORTS = [
     "drp_fanout_latest_device", "drp_fanout_latest_staged", "drp_set_fanout_latest_pass",
     "drp_store_table_bytes", "drp_store_init", "drp_store_merge_device", "drp_store_merge_staged",
     "drp_store_compact", "drp_store_query",
+    "drp_digest_device", "drp_digest_diff_device", "drp_select_buckets_device",
     "drp_comm_id", "drp_comm_init_rank", "drp_comm_init_all", "drp_comm_destroy",
     "drp_index_allgather", "drp_index_allgather_multi", "drp_index_allgather_host", "drp_device_count",
     "drp_host_alloc", "drp_host_free",
@@ -44,6 +45,8 @@ DRP_E_COMM = -7
 SEL_CHANGE_RANGE, SEL_SUBSET_EQ, SEL_SUBSET_NONE, SEL_KEY_PREFIX = 1, 2, 4, 8
 SEL_MAX_BYTES = 256
 FANOUT_MAX = 64
+DIGEST_MAX_BITS = 16
+DIGEST_LDS_BITS = 10  # csrc/drp_kernels.h DIG_LDS_BITS: up to here dig_cells sums in LDS, above in global memory
 COMM_ID_BYTES = 128
 
 P = C.c_void_p
@@ -147,6 +150,11 @@ class StoreDesc(C.Structure):
                 ("table", P), ("info", P), ("reserved", U64)]
 
 
+class DigestCell(C.Structure):
+    """drp_digest_cell: the rows of one bucket and the sum of their fingerprints (mod 2^64)."""
+    _fields_ = [("count", U64), ("sum", U64)]
+
+
 class Timing(C.Structure):
     _fields_ = [("decode_ms", C.c_float), ("finalize_ms", C.c_float), ("total_ms", C.c_float),
                 ("strict_reruns", U32), ("spec_repairs", U32), ("exact_retries", U32), ("verify_relisted", U32),
@@ -216,6 +224,11 @@ def lib():
         L.drp_store_merge_staged.argtypes = [P, C.POINTER(StoreDesc), C.POINTER(Filter), C.POINTER(StoreInfo)]
         L.drp_store_compact.argtypes = [P, C.POINTER(StoreDesc), P, U64]
         L.drp_store_query.argtypes = [P, C.POINTER(StoreDesc), C.POINTER(StoreInfo)]
+        L.drp_digest_device.argtypes = [P, P, U64, C.POINTER(Frames), C.POINTER(Changes), U64, C.POINTER(Filter), U32,
+                                        P, P]
+        L.drp_digest_diff_device.argtypes = [P, P, P, U32, P, P]
+        L.drp_select_buckets_device.argtypes = [P, P, U64, C.POINTER(Frames), C.POINTER(Changes), U64,
+                                                C.POINTER(Filter), U32, P, C.POINTER(ChangeSrc), P, P]
         L.drp_index_scan.argtypes = [P, P, U64, P]
         L.drp_stream_stats_from_results.argtypes = [P, P, P, U64, P]
         L.drp_device.argtypes = [P]
@@ -237,7 +250,8 @@ def lib():
                   "drp_fanout_device", "drp_fanout_staged", "drp_latest_device", "drp_latest_staged",
                   "drp_set_latest_hash_mask", "drp_fanout_latest_device", "drp_fanout_latest_staged",
                   "drp_set_fanout_latest_pass", "drp_store_init", "drp_store_merge_device", "drp_store_merge_staged",
-                  "drp_store_compact", "drp_store_query", "drp_stream_stats_from_results", "drp_device", "drp_comm_id", "drp_comm_init_rank",
+                  "drp_store_compact", "drp_store_query", "drp_digest_device", "drp_digest_diff_device",
+                  "drp_select_buckets_device", "drp_stream_stats_from_results", "drp_device", "drp_comm_id", "drp_comm_init_rank",
                   "drp_comm_init_all", "drp_index_allgather", "drp_index_allgather_multi",
                   "drp_index_allgather_host", "drp_device_count"]:
             getattr(L, f).restype = C.c_int
@@ -705,6 +719,48 @@ class Ctx:
         _chk("drp_store_query", self.L.drp_store_query(self.h, C.byref(store.desc()), C.byref(info)))
         return info
 
+    # ---- digest / reconcile: what differs between two stores ------------------------------------
+    def digest_device(self, wire_t, cols, n, filter, bits, cells_t, totals_t=None):
+        """drp_digest_device over torch CUDA tensors (asynchronous, on this ctx's stream): wire_t and
+        cols as select_device takes them; cells_t an int64 tensor of 2**bits * 2 elements (count, sum
+        per bucket), zeroed and filled; totals_t (int64, two elements, may be None): the rows
+        digested, and the selected rows left out for a range outside the wire."""
+        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
+        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
+                     tp(cols["flags"]), None)
+        self.order_after_torch(wire_t)
+        rc = self.L.drp_digest_device(self.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n,
+                                      C.byref(filter) if filter is not None else None, bits, tp(cells_t), tp(totals_t))
+        _chk("drp_digest_device", rc)
+        self.order_torch_after(wire_t)
+
+    def digest_diff_device(self, a_t, b_t, bits, bucket_set_t, n_diff_t):
+        """drp_digest_diff_device: a_t, b_t two digests of 2**bits cells; bucket_set_t (int64,
+        max(1, 2**bits // 64) words) gets bit b set iff cell b differs, n_diff_t (int64, one element)
+        the number of such buckets. Asynchronous."""
+        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self.order_after_torch(a_t)
+        _chk("drp_digest_diff_device", self.L.drp_digest_diff_device(self.h, tp(a_t), tp(b_t), bits, tp(bucket_set_t),
+                                                                     tp(n_diff_t)))
+        self.order_torch_after(a_t)
+
+    def select_buckets_device(self, wire_t, cols, n, filter, bits, bucket_set_t, out_rows, sel_idx_t, n_selected_t):
+        """drp_select_buckets_device: select_device's arguments and outputs, for the rows
+        digest_device counted (same filter, same bits) in the buckets whose bit is set in
+        bucket_set_t."""
+        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
+        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
+                     tp(cols["flags"]), None)
+        dst = ChangeSrc(*[tp(out_rows[k]) for k in SRC_COLS])
+        self.order_after_torch(wire_t)
+        rc = self.L.drp_select_buckets_device(self.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n,
+                                              C.byref(filter) if filter is not None else None, bits, tp(bucket_set_t),
+                                              C.byref(dst), tp(sel_idx_t), tp(n_selected_t))
+        _chk("drp_select_buckets_device", rc)
+        self.order_torch_after(wire_t)
+
 
 SRC_COLS = ["key_off", "key_len", "subset_off", "subset_len", "value_off", "value_len", "change", "from", "to", "flags"]
 
@@ -801,6 +857,56 @@ class Store:
         self.ctx.encode_device(rows, self.arena[:self.arena_bytes], total, foff, out, int(need.value))
         fo, o = foff.cpu().numpy(), out.cpu().numpy()
         return [o[int(fo[rb[f]]):int(fo[rb[f + 1]])].tobytes() for f in range(len(filters))]
+
+    def _view(self):
+        return self.arena[:self.arena_bytes] if self.arena_bytes else self.arena[:0]
+
+    def digest(self, bits, filter=None, n=None):
+        """The store's bucket digest (digest_device over its view, rows [0, n), default max_keys): an
+        int64 tensor of shape (2**bits, 2) on the store's device, [b] = (count, sum) of bucket b, the
+        16 bytes per bucket two hubs exchange. torch's stream is ordered after the ctx's."""
+        import torch
+        n = self.max_keys if n is None else int(n)
+        cells = torch.zeros((1 << bits, 2), dtype=torch.int64, device=self.arena.device)
+        self.ctx.digest_device(self._view(), self.cols, n, filter, bits, cells)
+        return cells
+
+    def reconcile(self, peer_cells, bits, filter=None):
+        """What this store holds in the buckets where its digest differs from a peer's: digest, diff
+        and bucket select over the view with n = max_keys, and one encode_device with the arena as the
+        heap (as fanout). peer_cells: the peer's digest(bits, filter), a tensor or a numpy array of
+        2**bits * 2 64-bit words. Returns (wire bytes, differing buckets): the rows in store order as
+        change frames, for the peer to decode and merge, and the increasing bucket numbers (numpy
+        int64) in which the two digests differ."""
+        import torch
+        dev = self.arena.device
+        if not isinstance(peer_cells, torch.Tensor):
+            peer_cells = torch.from_numpy(np.ascontiguousarray(peer_cells).view(np.int64).copy())
+        peer = peer_cells.to(device=dev, dtype=torch.int64).contiguous()
+        if peer.numel() != 2 << bits:
+            raise ValueError(f"peer_cells holds {peer.numel()} words, 2**{bits} cells are {2 << bits}")
+        mine = self.digest(bits, filter)
+        words = max(1, (1 << bits) // 64)
+        bset = torch.zeros(words, dtype=torch.int64, device=dev)
+        cnt = torch.zeros(2, dtype=torch.int64, device=dev)  # [0] differing buckets, [1] rows selected
+        self.ctx.digest_diff_device(mine, peer, bits, bset, cnt[0:1])
+        n = self.max_keys
+        rows = {k: torch.zeros(n, dtype=(torch.int32 if k.endswith("_len") else
+                                         torch.uint8 if k == "flags" else torch.int64), device=dev)
+                for k in SRC_COLS}
+        self.ctx.select_buckets_device(self._view(), self.cols, n, filter, bits, bset, rows, None, cnt[1:2])
+        total = int(cnt.cpu()[1])  # (torch's stream was ordered after the ctx's)
+        w = bset.cpu().numpy().view(np.uint64)
+        buckets = np.flatnonzero(np.unpackbits(w.view(np.uint8), bitorder="little")).astype(np.int64)
+        if total == 0:
+            return b"", buckets
+        src = ChangeSrc(*[C.c_void_p(rows[k].data_ptr()) for k in SRC_COLS])
+        need = U64()
+        _chk("drp_encode_size", self.ctx.L.drp_encode_size(self.ctx.h, C.byref(src), total, C.byref(need)))
+        foff = torch.zeros(total + 1, dtype=torch.int64, device=dev)
+        out = torch.zeros(max(int(need.value), 1), dtype=torch.uint8, device=dev)
+        self.ctx.encode_device(rows, self._view(), total, foff, out, int(need.value))
+        return out.cpu().numpy()[:int(need.value)].tobytes(), buckets
 
 
 class Comm:

@@ -33,6 +33,10 @@
  *       -> no reference counterpart: the latest Change per (subset, key) over every batch merged so
  *          far, resident in caller-owned device memory in the layout of a decoded batch, so the
  *          relay calls above run over it unchanged (a hub answering "what changed since T?").
+ *   drp_digest_device / drp_digest_diff_device / drp_select_buckets_device
+ *       -> no reference counterpart: a digest of the rows per bucket of identities, the buckets in
+ *          which two digests differ, and the select of those buckets' rows (two hubs without a shared
+ *          `change` counter reconciling their stores).
  *   drp_stream_stats + drp_index_scan
  *       -> no reference counterpart (the reference is single-stream); they build the
  *          global frame index after the per-GPU stats tables are all-gathered.
@@ -599,6 +603,70 @@ int drp_store_compact(drp_ctx *ctx, const drp_store *s, uint8_t *arena2, uint64_
 int drp_store_query(drp_ctx *ctx, const drp_store *s, drp_store_info *info_host);
 /* drp_set_latest_hash_mask applies to the store's table as well (test hook): a store must see one
  * mask from drp_store_init on, for its whole life. */
+
+/* ---- digest / reconcile: what differs between two stores, without a shared version ---------- */
+/* "What changed since T?" needs two parties that share one `change` counter. Two hubs that each hold
+ * a store, or a hub that merges several peers' feeds, have none; they compare content instead: a
+ * digest of the rows per bucket of identities (16 bytes a bucket), a diff of two digests, and a select
+ * that keeps the rows of the differing buckets, which one drp_encode_device then sends and the peer's
+ * drp_store_merge_device takes in. No reference counterpart (the reference has no relay); the fields
+ * read are those of messages/schema.proto:1-8.
+ *   The digest crosses the network, so it is defined bit for bit. All arithmetic is modulo 2^64;
+ * XXH64 is the published function with seed 0, P1 .. P4 its primes, rotl a left rotation:
+ *     merge(a, v)  = (a ^ (rotl(v * P2, 31) * P1)) * P1 + P4
+ *     avalanche(h) : h ^= h >> 33; h *= P2; h ^= h >> 29; h *= P3; h ^= h >> 32
+ *     ident(row)   = XXH64(key); with DRP_F_SUBSET: ident = merge(ident, XXH64(subset))
+ *                    (an empty subset still merges: the identity of drp_latest_device and the store)
+ *     fp(row)      = ident; for v in (change, from, to, flags & (DRP_F_SUBSET | DRP_F_VALUE)):
+ *                    fp = merge(fp, v); with DRP_F_VALUE: fp = merge(fp, XXH64(value)) (an empty value
+ *                    still merges); fp = avalanche(fp)
+ *     bucket(row)  = bits ? ident >> (64 - bits) : 0
+ *     cell[b]      = { count: the rows of bucket b, sum: the sum of their fp }
+ * fp covers what the store's `unchanged` rule compares. drp_set_latest_hash_mask does not reach any
+ * of this: it is a hook of the grouping tables only.
+ *   Candidates: the rows drp_select_device selects under the filter (NULL or flags == 0: every
+ * well-formed Change) whose key range, with DRP_F_SUBSET subset range and with DRP_F_VALUE value
+ * range lie inside [0, nbytes). A selected row with a range that leaves the wire is never read and is
+ * in no cell; it is counted in totals[1].
+ *   The digest is over the rows as they stand: over a store's view or drp_latest_device's output,
+ * where identities are distinct, the cells are a function of the set of (identity, content); over a
+ * raw batch a row that occurs twice counts twice. The order of the rows never matters.
+ *   Limit: two stores converge under mutual reconcile-and-merge only if no identity carries two
+ * different contents at the same `change` (a log never does). With such a pair each side would take
+ * the other's row, by the store's "equal change, later arrival wins" rule, and they would swap. */
+#define DRP_DIGEST_MAX_BITS 16
+typedef struct drp_digest_cell {
+  uint64_t count, sum;
+} drp_digest_cell;
+
+/* The digest of the candidates among decoded rows [0, n): cells (device, 2^bits entries) is zeroed
+ * and filled; totals (device, two entries, may be NULL): [0] the rows digested, [1] the selected rows
+ * left out for a range outside the wire. bytes, frames, cols, n and filter follow drp_latest_device's
+ * argument rules (out_rows aside) and DRP_E_INVAL cases; a store's view (s->arena, s->arena_bytes,
+ * &s->frames, &s->cols, n = max_keys) is a valid input. DRP_E_INVAL also for bits >
+ * DRP_DIGEST_MAX_BITS and NULL cells. Device pointers only; asynchronous on drp_stream(ctx), no host
+ * synchronisation inside. The result is a function of the input alone. Scratch from the ctx's: 512
+ * bytes (the filter's byte strings). */
+int drp_digest_device(drp_ctx *ctx, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                      const drp_changes *cols, uint64_t n, const drp_filter *filter, uint32_t bits,
+                      drp_digest_cell *cells, uint64_t *totals);
+/* Two digests of 2^bits cells each (a, b: device) compared: bucket_set (device, max(1, 2^bits / 64)
+ * words) gets bit b & 63 of word b >> 6 set iff a[b] and b[b] differ in count or sum; the unused high
+ * bits of the one word of bits < 6 are 0. *n_diff (device) = the bits set. Asynchronous on
+ * drp_stream(ctx); no scratch. DRP_E_INVAL: a NULL pointer, bits > DRP_DIGEST_MAX_BITS. */
+int drp_digest_diff_device(drp_ctx *ctx, const drp_digest_cell *a, const drp_digest_cell *b, uint32_t bits,
+                           uint64_t *bucket_set, uint64_t *n_diff);
+/* drp_select_device restricted to the digest's candidates whose bucket's bit is set in bucket_set
+ * (device, as drp_digest_diff_device writes it): the same stable compaction and the same out_rows,
+ * sel_idx and n_selected contract. Under one filter and one bits, the rows kept are exactly the rows
+ * drp_digest_device counted in the cells of the set buckets. The argument rules and DRP_E_INVAL cases
+ * are drp_select_device's, and bits > DRP_DIGEST_MAX_BITS or a NULL bucket_set. Asynchronous on
+ * drp_stream(ctx). Scratch from the ctx's: drp_select_device's (one bit per row, 8 bytes per 1024
+ * rows, 512 bytes). */
+int drp_select_buckets_device(drp_ctx *ctx, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                              const drp_changes *cols, uint64_t n, const drp_filter *filter, uint32_t bits,
+                              const uint64_t *bucket_set, const drp_change_src *out_rows, uint64_t *sel_idx,
+                              uint64_t *n_selected);
 
 /* ---- multi-GPU global index ---------------------------------------------- */
 /* stats[nranks*per_rank] (device): all-gathered per-stream tables in rank order.

@@ -53,6 +53,19 @@ probe, and the host relay through drp_relay_staged against the host round trip i
               another commit's library and binding (DRP_LIB, DRP_PY); --store-baseline reads such a
               file into the result.
 
+  digest      (--digest-out, default profiles/relay/digest_bench.json) Two compacted stores: the store
+              leg's final store (frames / 16 keys, 74-byte payloads) and one of 65,536 keys with 4 KB
+              values. Per store, HIP events, three warm-up rounds and --iters timed ones:
+              drp_digest_device over the view (n = max_keys) at bits 8, 12 and 16; against a peer whose
+              `change` is raised on 0.1 % and on 10 % of the keys, drp_digest_diff_device,
+              drp_select_buckets_device and drp_encode_device at bits 16 (what Store.reconcile composes),
+              the rows checked to hold every altered key; and the two yardsticks: drp_store_compact of
+              the same store and the full snapshot (drp_fanout_device with one all-pass filter and
+              drp_encode_device). --digest-baseline-out: only the yardsticks, through nothing the digest
+              added, so that they can be taken with the parent commit's library and binding (DRP_LIB,
+              DRP_PY); --digest-baseline reads such a file, and the ratios (digest / compact, reconcile /
+              snapshot) are then over the parent's figures. With --digest-only every other leg is left out.
+
 Prints one JSON line (and writes it to --out). Needs an MI355X: there is no CPU path.
 
   hipcc -O3 --offload-arch=gfx950 scripts/probe_bw.hip -o exp/probe_bw
@@ -876,6 +889,185 @@ def store_leg(ctx, drp_amd, torch, frames, seqs, iters):
     return res
 
 
+# ---- digest / reconcile -----------------------------------------------------------------------------
+
+DIGEST_BITS = (8, 12, 16)
+RECONCILE_BITS = 16
+BIG_KEYS, BIG_VALUE = 65536, 4096
+
+
+def big_value_stream(n, vlen=BIG_VALUE, seed=3):
+    """n Changes with the 10-digit keys 0 .. n - 1 and vlen random value bytes (two-byte varints:
+    128 <= vlen < 16000): change = i % 100 + 1, from = i % 128, to = (i + 1) % 128; 24 + vlen bytes a frame."""
+    plen = 21 + vlen
+    assert 128 <= vlen and plen + 1 < 16384
+    i = np.arange(n, dtype=np.int64)
+    a = np.zeros((n, plen + 3), np.uint8)
+    a[:, 0], a[:, 1], a[:, 2] = ((plen + 1) & 0x7F) | 0x80, (plen + 1) >> 7, 1
+    a[:, 3], a[:, 4] = 0x12, 10
+    for k in range(10):
+        a[:, 5 + k] = 48 + (i // 10 ** (9 - k)) % 10
+    a[:, 15], a[:, 16] = 0x18, (i % 100) + 1
+    a[:, 17], a[:, 18] = 0x20, i % 128
+    a[:, 19], a[:, 20] = 0x28, (i + 1) % 128
+    a[:, 21], a[:, 22], a[:, 23] = 0x32, (vlen & 0x7F) | 0x80, vlen >> 7
+    a[:, 24:] = np.random.default_rng(seed).integers(0, 256, size=(n, vlen), dtype=np.uint8)
+    return a.reshape(-1)
+
+
+def _digest_store(ctx, drp_amd, torch, shape, frames):
+    """One of the leg's two stores, compacted: (store, keys, frame bytes of a stored row re-encoded).
+    "keyed": the store leg's final store (frames keyed C2 rows in 8 merges); "big_values": BIG_KEYS keys
+    with BIG_VALUE-byte values in one merge. Only calls every commit with a store has."""
+    dev = torch.device("cuda", 0)
+    if shape == "keyed":
+        key_ids, wire_t, cols, n, m = _store_input(ctx, drp_amd, torch, frames)
+        keys, batches, fb = int(len(np.unique(key_ids))), STORE_BATCHES, 86
+        arena_bytes = 80 * (keys + STORE_BATCHES * m) // 2
+    else:
+        wire_t, cols, n = device_setup(ctx, drp_amd, torch, None, BIG_KEYS, wire=big_value_stream(BIG_KEYS))
+        keys, batches, m, fb = BIG_KEYS, 1, BIG_KEYS, 24 + BIG_VALUE
+        arena_bytes = keys * ((10 + BIG_VALUE + 15) & ~15)
+    store = drp_amd.Store(ctx, keys, arena_bytes)
+    for b in range(batches):
+        ctx.store_merge_device(store, wire_t, {k: v[b * m:] for k, v in cols.items()}, m)
+    info = store.query()
+    assert info.refused == 0 and info.rows == keys, (info.rows, keys, info.refused)
+    a2 = torch.zeros(info.arena_used - info.arena_dead, dtype=torch.uint8, device=dev)
+    ctx.store_compact(store, a2)
+    assert store.query().refused == 0
+    store.arena, store.arena_bytes = a2, a2.numel()
+    del wire_t, cols
+    torch.cuda.empty_cache()
+    return store, keys, fb
+
+
+def _digest_yardsticks(ctx, drp_amd, torch, store, keys, fb, iters):
+    """The two existing passes the digest is set against: drp_store_compact of the store (between two
+    arenas, to and fro) and the full snapshot a hub sends today (drp_fanout_device with one all-pass
+    filter over the store's view and drp_encode_device). HIP events; three warm-up rounds."""
+    dev = torch.device("cuda", 0)
+    ext = ctx._ext(dev)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record(ext)
+        fn()
+        e1.record(ext)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    live = store.arena_bytes
+    spare = torch.zeros(live, dtype=torch.uint8, device=dev)
+    rows = _row_tensors(torch, dev, keys)
+    rb_t = torch.zeros(2, dtype=torch.int64, device=dev)
+    foff = torch.zeros(keys + 1, dtype=torch.int64, device=dev)
+    out = torch.zeros(keys * fb, dtype=torch.uint8, device=dev)
+    flt = [None]
+    tc, tf, te = [], [], []
+    for it in range(iters + 3):
+        a2 = spare
+        c = timed(lambda: ctx.store_compact(store, a2))
+        assert store.query().refused == 0
+        spare, store.arena = store.arena, a2
+        f = timed(lambda: ctx.fanout_device(store.arena, store.cols, store.max_keys, flt, rows, keys, None, rb_t))
+        e = timed(lambda: ctx.encode_device(rows, store.arena, keys, foff, out, out.numel()))
+        if it >= 3:
+            tc.append(c)
+            tf.append(f)
+            te.append(e)
+    assert int(rb_t.cpu()[1]) == keys and int(foff[keys].cpu()) == keys * fb, "snapshot"
+    return {"keys": keys, "live_bytes": live, "compact_ms": _stat(tc),
+            "snapshot": {"rows_out": keys, "out_bytes": keys * fb, "fanout_ms": _stat(tf), "encode_ms": _stat(te),
+                         "total_ms_median": statistics.median(tf) + statistics.median(te)}}
+
+
+def digest_baseline(ctx, drp_amd, torch, frames, iters):
+    res = {"bench": "relay_digest_baseline", "frames": frames, "iters": iters}
+    for shape in ("keyed", "big_values"):
+        store, keys, fb = _digest_store(ctx, drp_amd, torch, shape, frames)
+        res[shape] = _digest_yardsticks(ctx, drp_amd, torch, store, keys, fb, iters)
+        print("digest baseline", shape, res[shape], file=sys.stderr, flush=True)
+        store = None
+        torch.cuda.empty_cache()
+    return res
+
+
+def digest_leg(ctx, drp_amd, torch, frames, iters, parent=None):
+    dev = torch.device("cuda", 0)
+    ext = ctx._ext(dev)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record(ext)
+        fn()
+        e1.record(ext)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    def runs(fn):
+        return _stat([timed(fn) for it in range(iters + 3)][3:])
+
+    res = {"frames": frames, "iters": iters}
+    for shape in ("keyed", "big_values"):
+        store, keys, fb = _digest_store(ctx, drp_amd, torch, shape, frames)
+        r = _digest_yardsticks(ctx, drp_amd, torch, store, keys, fb, iters)
+        view, n = store.arena, store.max_keys
+        tot = torch.zeros(2, dtype=torch.int64, device=dev)
+        r["digest_ms"], mine = {}, {}
+        for bits in DIGEST_BITS:
+            cells = torch.zeros((1 << bits, 2), dtype=torch.int64, device=dev)
+            r["digest_ms"][f"bits{bits}"] = runs(lambda: ctx.digest_device(view, store.cols, n, None, bits, cells, tot))
+            assert [int(v) for v in tot.cpu()] == [keys, 0] and int(cells[:, 0].sum().cpu()) == keys, "digest totals"
+            mine[bits] = cells
+        base = (parent or {}).get(shape, r)
+        r["yardsticks_from"] = "parent" if parent else "this commit"
+        r["parent"] = base if parent else None
+        r["digest_over_compact"] = {k: v["median"] / base["compact_ms"]["median"] for k, v in r["digest_ms"].items()}
+        # the peer: the same rows with `change` raised on a random share of the keys
+        bits = RECONCILE_BITS
+        words = (1 << bits) // 64
+        bset = torch.zeros(words, dtype=torch.int64, device=dev)
+        cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+        rows = _row_tensors(torch, dev, keys)
+        idx_t = torch.zeros(keys, dtype=torch.int64, device=dev)
+        foff = torch.zeros(keys + 1, dtype=torch.int64, device=dev)
+        out = torch.zeros(keys * fb, dtype=torch.uint8, device=dev)
+        r["reconcile"] = {}
+        for share in (0.001, 0.10):
+            gen = torch.Generator(device="cpu").manual_seed(int(share * 1000))
+            hit = torch.randperm(keys, generator=gen)[:max(1, int(keys * share))].to(dev)
+            peer_cols = dict(store.cols)
+            peer_cols["change"] = store.cols["change"].clone()
+            peer_cols["change"][hit] += 1
+            peer = torch.zeros((1 << bits, 2), dtype=torch.int64, device=dev)
+            ctx.digest_device(view, peer_cols, n, None, bits, peer, None)
+            t_diff = runs(lambda: ctx.digest_diff_device(mine[bits], peer, bits, bset, cnt[0:1]))
+            t_sel = runs(lambda: ctx.select_buckets_device(view, store.cols, n, None, bits, bset, rows, idx_t, cnt[1:2]))
+            nd, nsel = [int(v) for v in cnt.cpu()]
+            got = torch.zeros(keys, dtype=torch.bool, device=dev)
+            got[idx_t[:nsel]] = True
+            assert bool(got[hit].all()) and len(hit) >= nd > 0 and nsel >= len(hit), "reconcile rows"
+            # (cap = the bytes needed, as Store.reconcile passes it: the encoder's write grid is sized from cap)
+            t_enc = runs(lambda: ctx.encode_device(rows, view, nsel, foff, out, nsel * fb))
+            assert int(foff[nsel].cpu()) == nsel * fb, "reconcile bytes"
+            total = (r["digest_ms"][f"bits{bits}"]["median"] + t_diff["median"] + t_sel["median"] + t_enc["median"])
+            r["reconcile"][f"share{share}"] = {
+                "bits": bits, "keys_altered": int(len(hit)), "buckets_differing": nd, "rows_out": nsel,
+                "out_bytes": nsel * fb, "cells_bytes": 16 << bits, "diff_ms": t_diff, "select_buckets_ms": t_sel,
+                "encode_ms": t_enc, "total_ms_median": total,
+                "over_snapshot": total / base["snapshot"]["total_ms_median"],
+                "bytes_over_snapshot": (nsel * fb + (16 << bits)) / base["snapshot"]["out_bytes"]}
+            print("digest reconcile", shape, share, r["reconcile"][f"share{share}"], file=sys.stderr, flush=True)
+        res[shape] = r
+        print("digest", shape, r["digest_ms"], r["compact_ms"], r["digest_over_compact"], file=sys.stderr, flush=True)
+        store = view = rows = out = mine = None
+        torch.cuda.empty_cache()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20_000_000)
@@ -900,7 +1092,16 @@ def main():
     ap.add_argument("--store-baseline-out", default=None,
                     help="only drp_latest_device over the store leg's batches (any commit's library), written here")
     ap.add_argument("--store-baseline", default=None, help="such a file of the parent commit, read into the store leg's result")
+    ap.add_argument("--digest-out", nargs="?", default=None,
+                    const=os.path.join(ROOT, "profiles", "relay", "digest_bench.json"),
+                    help="run the digest leg too and write its JSON line here")
+    ap.add_argument("--digest-only", action="store_true", help="with --digest-out: leave the other legs out")
+    ap.add_argument("--digest-baseline-out", default=None,
+                    help="only the digest leg's yardsticks (compact, full snapshot; any commit's library), written here")
+    ap.add_argument("--digest-baseline", default=None, help="such a file of the parent commit, read into the digest leg's result")
     a = ap.parse_args()
+    if a.digest_only and not a.digest_out:
+        ap.error("--digest-only needs --digest-out")
     if a.store_only and not a.store_out:
         ap.error("--store-only needs --store-out")
     if a.latest_only and not a.latest_out:
@@ -916,6 +1117,23 @@ def main():
     torch.cuda.init()
     import _streams as S
     import drp_amd
+    if a.digest_baseline_out:
+        with drp_amd.Ctx(0) as ctx:
+            base = digest_baseline(ctx, drp_amd, torch, a.frames, a.iters)
+        with open(a.digest_baseline_out, "w") as f:
+            f.write(json.dumps(base) + "\n")
+        print(json.dumps(base))
+        return
+    if a.digest_out:
+        parent = json.loads(open(a.digest_baseline).read()) if a.digest_baseline else None
+        assert parent is None or parent["frames"] == a.frames
+        with drp_amd.Ctx(0) as ctx:
+            dg = {"bench": "relay_digest", "device": digest_leg(ctx, drp_amd, torch, a.frames, a.iters, parent)}
+        with open(a.digest_out, "w") as f:
+            f.write(json.dumps(dg) + "\n")
+        print(json.dumps(dg))
+        if a.digest_only:
+            return
     if a.store_baseline_out:
         with drp_amd.Ctx(0) as ctx:
             base = store_baseline(ctx, drp_amd, torch, a.frames, a.store_seqs)
