@@ -279,6 +279,24 @@ constexpr uint32_t DIG_LDS_BITS = 10;
 // workgroups: a small batch of long values needs the compute units more than the sharing
 constexpr uint32_t DIG_CHUNKS = 4, DIG_GRID_MIN = 128;
 
+// drp_digest.hip: the second level inside the buckets of d.bucket_set (include/drp.h "refined
+// digests"). dig_rank leaves rank[w] = the set bits of the set's words before word w, and the set
+// bits of all of them (n_set) in d.totals[2]; dig_refine sums d's candidates of the set buckets into
+// d.cells[slot(bucket) << sub_bits | sub] (d.totals: three entries, required), dig_count2 keeps those
+// whose cell's bit is set in cell_set
+struct RefineParams {
+  DigestParams d;
+  uint32_t sub_bits;     // 1 .. DRP_DIGEST_MAX_SUB_BITS
+  uint32_t set_words;    // the words of d.bucket_set: max(1, 2^bits / 64) <= DIG_RANK_BLK
+  uint32_t *rank;        // [set_words], scratch
+  uint64_t cells_cap;    // dig_refine writes d.cells only if n_set << sub_bits <= cells_cap
+  const uint64_t *cell_set;
+};
+constexpr uint32_t DIG_RANK_BLK = 1024;  // one workgroup, one word of the set per lane
+// up to this many second-level cells a dig_refine workgroup sums into a copy in LDS, as dig_cells does
+// up to DIG_LDS_BITS bits (DESIGN.md "Refined digests" has the measurement)
+constexpr uint32_t DIG_REFINE_LDS_CELLS = 1u << DIG_LDS_BITS;
+
 }  // namespace drp
 
 extern "C" {
@@ -387,6 +405,15 @@ hipError_t drp_launch_digest(const drp::DigestParams *D, const drp::SelectBytes 
 hipError_t drp_launch_digest_diff(const drp_digest_cell *a, const drp_digest_cell *b, uint32_t bits,
                                   uint64_t *bucket_set, uint64_t *n_diff, hipStream_t st);
 hipError_t drp_launch_select_buckets(const drp::DigestParams *D, const drp::SelectBytes *fb, void *scratch,
+                                     hipStream_t st);
+// The second level. drp_launch_digest_diff for any cell count (0: the one word and *n_diff are 0);
+// the refine (scratch: 2 * DRP_SEL_MAX_BYTES bytes, then R->rank, placed by the caller); the select of
+// the set cells' rows (scratch: drp_select_scratch_bytes(n), R->rank behind it)
+hipError_t drp_launch_digest_diff_cells(const drp_digest_cell *a, const drp_digest_cell *b, uint32_t ncell,
+                                        uint64_t *cell_set, uint64_t *n_diff, hipStream_t st);
+hipError_t drp_launch_digest_refine(const drp::RefineParams *R, const drp::SelectBytes *fb, void *scratch,
+                                    hipStream_t st);
+hipError_t drp_launch_select_refined(const drp::RefineParams *R, const drp::SelectBytes *fb, void *scratch,
                                      hipStream_t st);
 hipError_t drp_launch_fanout_scatter(const drp::FanParams *P, hipStream_t st);
 hipError_t drp_launch_fanout_splice(const drp::FanParams *P, hipStream_t st);

@@ -4,7 +4,8 @@
 // heap), drp_fanout_device / drp_fanout_staged (many filters over one pass) and
 // drp_fanout_latest_device / drp_fanout_latest_staged (latest per key under each), and the store
 // (drp_store_*: the latest-per-key step, then the merge into caller-owned device memory), and the
-// digest calls (drp_digest_device, drp_digest_diff_device, drp_select_buckets_device). The kernels
+// digest calls (drp_digest_device, drp_digest_diff_device, drp_select_buckets_device, and their second
+// level drp_digest_refine_device, drp_digest_diff_cells_device, drp_select_refined_device). The kernels
 // are in drp_select.hip, drp_latest.hip, drp_fanout.hip, drp_store.hip and drp_digest.hip; the
 // context is drp_api.hip's (drp_ctx.h).
 #include <algorithm>
@@ -468,6 +469,62 @@ int drp_select_buckets_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes,
   D.sel.out = row_out(out_rows, sel_idx);
   D.sel.n_selected = n_selected;
   CHK(drp_launch_select_buckets(&D, &fb, c->scratch.p, c->st));
+  return DRP_OK;
+}
+
+// the second level: the set, sub_bits and the rank table's place (`rank_at` bytes into the scratch)
+static void refine_params(drp_ctx *c, RefineParams &R, const uint64_t *bucket_set, uint32_t sub_bits, size_t rank_at) {
+  R.d.bucket_set = bucket_set;
+  R.sub_bits = sub_bits;
+  R.set_words = std::max(1u, (1u << R.d.bits) / 64);
+  R.rank = c->scratch.at<uint32_t>(rank_at);
+}
+static bool sub_bits_ok(uint32_t sub_bits) { return sub_bits >= 1 && sub_bits <= DRP_DIGEST_MAX_SUB_BITS; }
+
+int drp_digest_refine_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                             const drp_changes *cols, uint64_t n, const drp_filter *filter, uint32_t bits,
+                             const uint64_t *bucket_set, uint32_t sub_bits, drp_digest_cell *cells2,
+                             uint64_t cells_cap, uint64_t *totals) {
+  RefineParams R = {};
+  SelectBytes fb = {};
+  if (!bucket_set || !cells2 || !totals || !sub_bits_ok(sub_bits)) return DRP_E_INVAL;
+  if (const int rc = digest_params(c, bytes, nbytes, frames, cols, n, filter, bits, nullptr, R.d, fb)) return rc;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  const size_t rank_at = 2 * DRP_SEL_MAX_BYTES;
+  if (!c->scratch.ensure(rank_at + 4 * DIG_RANK_BLK)) return DRP_E_NOMEM;
+  refine_params(c, R, bucket_set, sub_bits, rank_at);
+  R.d.cells = cells2;
+  R.d.totals = totals;
+  R.cells_cap = cells_cap;
+  CHK(drp_launch_digest_refine(&R, &fb, c->scratch.p, c->st));
+  return DRP_OK;
+}
+
+int drp_digest_diff_cells_device(drp_ctx *c, const drp_digest_cell *a, const drp_digest_cell *b, uint64_t ncells,
+                                 uint64_t *cell_set, uint64_t *n_diff) {
+  const uint64_t most = (uint64_t)1 << (DRP_DIGEST_MAX_BITS + DRP_DIGEST_MAX_SUB_BITS);
+  if (!c || !a || !b || !cell_set || !n_diff || ncells > most) return DRP_E_INVAL;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  CHK(drp_launch_digest_diff_cells(a, b, (uint32_t)ncells, cell_set, n_diff, c->st));
+  return DRP_OK;
+}
+
+int drp_select_refined_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                              const drp_changes *cols, uint64_t n, const drp_filter *filter, uint32_t bits,
+                              const uint64_t *bucket_set, uint32_t sub_bits, const uint64_t *cell_set,
+                              const drp_change_src *out_rows, uint64_t *sel_idx, uint64_t *n_selected) {
+  RefineParams R = {};
+  SelectBytes fb = {};
+  if (!bucket_set || !cell_set || !out_rows || !n_selected || !sub_bits_ok(sub_bits)) return DRP_E_INVAL;
+  if (const int rc = digest_params(c, bytes, nbytes, frames, cols, n, filter, bits, out_rows, R.d, fb)) return rc;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  const size_t rank_at = (drp_select_scratch_bytes(n) + 7) & ~(size_t)7;
+  if (!c->scratch.ensure(rank_at + 4 * DIG_RANK_BLK)) return DRP_E_NOMEM;
+  refine_params(c, R, bucket_set, sub_bits, rank_at);
+  R.cell_set = cell_set;
+  R.d.sel.out = row_out(out_rows, sel_idx);
+  R.d.sel.n_selected = n_selected;
+  CHK(drp_launch_select_refined(&R, &fb, c->scratch.p, c->st));
   return DRP_OK;
 }
 

@@ -35,6 +35,7 @@ EXPORTS = [
     "drp_store_table_bytes", "drp_store_init", "drp_store_merge_device", "drp_store_merge_staged",
     "drp_store_compact", "drp_store_query",
     "drp_digest_device", "drp_digest_diff_device", "drp_select_buckets_device",
+    "drp_digest_refine_device", "drp_digest_diff_cells_device", "drp_select_refined_device",
     "drp_comm_id", "drp_comm_init_rank", "drp_comm_init_all", "drp_comm_destroy",
     "drp_index_allgather", "drp_index_allgather_multi", "drp_index_allgather_host", "drp_device_count",
     "drp_host_alloc", "drp_host_free",
@@ -46,6 +47,7 @@ SEL_CHANGE_RANGE, SEL_SUBSET_EQ, SEL_SUBSET_NONE, SEL_KEY_PREFIX = 1, 2, 4, 8
 SEL_MAX_BYTES = 256
 FANOUT_MAX = 64
 DIGEST_MAX_BITS = 16
+DIGEST_MAX_SUB_BITS = 8
 DIGEST_LDS_BITS = 10  # csrc/drp_kernels.h DIG_LDS_BITS: up to here dig_cells sums in LDS, above in global memory
 COMM_ID_BYTES = 128
 
@@ -229,6 +231,11 @@ def lib():
         L.drp_digest_diff_device.argtypes = [P, P, P, U32, P, P]
         L.drp_select_buckets_device.argtypes = [P, P, U64, C.POINTER(Frames), C.POINTER(Changes), U64,
                                                 C.POINTER(Filter), U32, P, C.POINTER(ChangeSrc), P, P]
+        L.drp_digest_refine_device.argtypes = [P, P, U64, C.POINTER(Frames), C.POINTER(Changes), U64,
+                                               C.POINTER(Filter), U32, P, U32, P, U64, P]
+        L.drp_digest_diff_cells_device.argtypes = [P, P, P, U64, P, P]
+        L.drp_select_refined_device.argtypes = [P, P, U64, C.POINTER(Frames), C.POINTER(Changes), U64,
+                                                C.POINTER(Filter), U32, P, U32, P, C.POINTER(ChangeSrc), P, P]
         L.drp_index_scan.argtypes = [P, P, U64, P]
         L.drp_stream_stats_from_results.argtypes = [P, P, P, U64, P]
         L.drp_device.argtypes = [P]
@@ -251,7 +258,8 @@ def lib():
                   "drp_set_latest_hash_mask", "drp_fanout_latest_device", "drp_fanout_latest_staged",
                   "drp_set_fanout_latest_pass", "drp_store_init", "drp_store_merge_device", "drp_store_merge_staged",
                   "drp_store_compact", "drp_store_query", "drp_digest_device", "drp_digest_diff_device",
-                  "drp_select_buckets_device", "drp_stream_stats_from_results", "drp_device", "drp_comm_id", "drp_comm_init_rank",
+                  "drp_select_buckets_device", "drp_digest_refine_device", "drp_digest_diff_cells_device",
+                  "drp_select_refined_device", "drp_stream_stats_from_results", "drp_device", "drp_comm_id", "drp_comm_init_rank",
                   "drp_comm_init_all", "drp_index_allgather", "drp_index_allgather_multi",
                   "drp_index_allgather_host", "drp_device_count"]:
             getattr(L, f).restype = C.c_int
@@ -761,6 +769,51 @@ class Ctx:
         _chk("drp_select_buckets_device", rc)
         self.order_torch_after(wire_t)
 
+    # ---- refined digests: a second level inside the differing buckets ----------------------------
+    def digest_refine_device(self, wire_t, cols, n, filter, bits, bucket_set_t, sub_bits, cells2_t, cells_cap, totals_t):
+        """drp_digest_refine_device: digest_device's candidates in the buckets whose bit is set in
+        bucket_set_t (int64, max(1, 2**bits // 64) words), summed into cells2_t (int64, cells_cap * 2
+        elements) at cell slot(bucket) << sub_bits | sub. totals_t (int64, three elements, required):
+        the rows digested, the selected rows left out for a range outside the wire, n_set. The cells
+        are written only if n_set << sub_bits <= cells_cap; totals_t is complete either way."""
+        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
+        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
+                     tp(cols["flags"]), None)
+        self.order_after_torch(wire_t)
+        rc = self.L.drp_digest_refine_device(self.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n,
+                                             C.byref(filter) if filter is not None else None, bits, tp(bucket_set_t),
+                                             sub_bits, tp(cells2_t), cells_cap, tp(totals_t))
+        _chk("drp_digest_refine_device", rc)
+        self.order_torch_after(wire_t)
+
+    def digest_diff_cells_device(self, a_t, b_t, ncells, cell_set_t, n_diff_t):
+        """drp_digest_diff_cells_device: digest_diff_device for any cell count; cell_set_t (int64,
+        max(1, ceil(ncells / 64)) words), n_diff_t (int64, one element). Asynchronous."""
+        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        self.order_after_torch(a_t)
+        _chk("drp_digest_diff_cells_device", self.L.drp_digest_diff_cells_device(self.h, tp(a_t), tp(b_t), ncells,
+                                                                                 tp(cell_set_t), tp(n_diff_t)))
+        self.order_torch_after(a_t)
+
+    def select_refined_device(self, wire_t, cols, n, filter, bits, bucket_set_t, sub_bits, cell_set_t, out_rows,
+                              sel_idx_t, n_selected_t):
+        """drp_select_refined_device: select_buckets_device's arguments and outputs, for the rows
+        digest_refine_device counted (same filter, bits, bucket set and sub_bits) in the cells whose
+        bit is set in cell_set_t."""
+        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
+        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
+                     tp(cols["flags"]), None)
+        dst = ChangeSrc(*[tp(out_rows[k]) for k in SRC_COLS]) if out_rows is not None else None
+        self.order_after_torch(wire_t)
+        rc = self.L.drp_select_refined_device(self.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n,
+                                              C.byref(filter) if filter is not None else None, bits, tp(bucket_set_t),
+                                              sub_bits, tp(cell_set_t), C.byref(dst) if dst is not None else None,
+                                              tp(sel_idx_t), tp(n_selected_t))
+        _chk("drp_select_refined_device", rc)
+        self.order_torch_after(wire_t)
+
 
 SRC_COLS = ["key_off", "key_len", "subset_off", "subset_len", "value_off", "value_len", "change", "from", "to", "flags"]
 
@@ -907,6 +960,80 @@ class Store:
         out = torch.zeros(max(int(need.value), 1), dtype=torch.uint8, device=dev)
         self.ctx.encode_device(rows, self._view(), total, foff, out, int(need.value))
         return out.cpu().numpy()[:int(need.value)].tobytes(), buckets
+
+    def _set_tensor(self, words):
+        """A bit set (a tensor or a numpy array of 64-bit words) as an int64 tensor on the store's device."""
+        import torch
+        if not isinstance(words, torch.Tensor):
+            words = torch.from_numpy(np.ascontiguousarray(words).view(np.int64).copy())
+        return words.to(device=self.arena.device, dtype=torch.int64).contiguous()
+
+    def digest_refined(self, bits, bucket_set, sub_bits, filter=None):
+        """The second level of the store's digest inside the buckets of bucket_set (a tensor or a numpy
+        array of max(1, 2**bits // 64) words, as digest_diff_device writes it): (cells2, n_set), cells2
+        an int64 tensor of shape (n_set << sub_bits, 2) on the store's device, [slot << sub_bits | sub]
+        = (count, sum) of the rows of the slot-th set bucket whose next sub_bits hash bits are sub.
+
+        The exchange: both hubs hold both first-level digests (each sent its digest(bits)), so both
+        derive the same bucket_set from one diff; each then sends its cells2, and each encodes its rows
+        of the differing cells (reconcile_refined). The sub-cells of a slot add up to the first-level
+        cell of that bucket. n_set is the popcount of the set, taken on the host to size the tensor."""
+        import torch
+        bset = self._set_tensor(bucket_set)
+        words = max(1, (1 << bits) // 64)
+        if bset.numel() != words:
+            raise ValueError(f"bucket_set holds {bset.numel()} words, 2**{bits} buckets are {words}")
+        w = bset.cpu().numpy().view(np.uint64)
+        if bits < 6:
+            w = w & np.uint64((1 << (1 << bits)) - 1)
+        ncells = int(np.unpackbits(w.view(np.uint8)).sum()) << sub_bits
+        dev = self.arena.device
+        cells2 = torch.zeros((max(ncells, 1), 2), dtype=torch.int64, device=dev)
+        tot = torch.zeros(3, dtype=torch.int64, device=dev)
+        self.ctx.digest_refine_device(self._view(), self.cols, self.max_keys, filter, bits, bset, sub_bits, cells2,
+                                      ncells, tot)
+        return cells2[:ncells], ncells >> sub_bits
+
+    def reconcile_refined(self, peer_cells2, bits, bucket_set, sub_bits, filter=None):
+        """What this store holds in the second-level cells where its digest_refined differs from a
+        peer's: refine, cell diff and refined select over the view with n = max_keys, and one
+        encode_device with the arena as the heap (shaped like reconcile). peer_cells2: the peer's
+        digest_refined(bits, bucket_set, sub_bits, filter)[0], a tensor or a numpy array of
+        (n_set << sub_bits) * 2 64-bit words; bucket_set: a tensor or a numpy array of words, the same
+        set on both hubs (see digest_refined for the exchange). Returns (wire bytes, differing cells):
+        the rows in store order as change frames, for the peer to decode and merge, and the increasing
+        cell numbers (numpy int64) in which the two second levels differ."""
+        import torch
+        dev = self.arena.device
+        bset = self._set_tensor(bucket_set)
+        mine, n_set = self.digest_refined(bits, bset, sub_bits, filter)
+        ncells = n_set << sub_bits
+        peer = self._set_tensor(peer_cells2)
+        if peer.numel() != 2 * ncells:
+            raise ValueError(f"peer_cells2 holds {peer.numel()} words, {ncells} cells are {2 * ncells}")
+        if ncells == 0:
+            return b"", np.zeros(0, np.int64)
+        cset = torch.zeros((ncells + 63) // 64, dtype=torch.int64, device=dev)
+        cnt = torch.zeros(2, dtype=torch.int64, device=dev)  # [0] differing cells, [1] rows selected
+        self.ctx.digest_diff_cells_device(mine, peer, ncells, cset, cnt[0:1])
+        n = self.max_keys
+        rows = {k: torch.zeros(n, dtype=(torch.int32 if k.endswith("_len") else
+                                         torch.uint8 if k == "flags" else torch.int64), device=dev)
+                for k in SRC_COLS}
+        self.ctx.select_refined_device(self._view(), self.cols, n, filter, bits, bset, sub_bits, cset, rows, None,
+                                       cnt[1:2])
+        total = int(cnt.cpu()[1])  # (torch's stream was ordered after the ctx's)
+        w = cset.cpu().numpy().view(np.uint64)
+        cells = np.flatnonzero(np.unpackbits(w.view(np.uint8), bitorder="little")).astype(np.int64)
+        if total == 0:
+            return b"", cells
+        src = ChangeSrc(*[C.c_void_p(rows[k].data_ptr()) for k in SRC_COLS])
+        need = U64()
+        _chk("drp_encode_size", self.ctx.L.drp_encode_size(self.ctx.h, C.byref(src), total, C.byref(need)))
+        foff = torch.zeros(total + 1, dtype=torch.int64, device=dev)
+        out = torch.zeros(max(int(need.value), 1), dtype=torch.uint8, device=dev)
+        self.ctx.encode_device(rows, self._view(), total, foff, out, int(need.value))
+        return out.cpu().numpy()[:int(need.value)].tobytes(), cells
 
 
 class Comm:

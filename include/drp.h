@@ -37,6 +37,10 @@
  *       -> no reference counterpart: a digest of the rows per bucket of identities, the buckets in
  *          which two digests differ, and the select of those buckets' rows (two hubs without a shared
  *          `change` counter reconciling their stores).
+ *   drp_digest_refine_device / drp_digest_diff_cells_device / drp_select_refined_device
+ *       -> no reference counterpart: a second level of digest cells inside the differing buckets
+ *          only, the cells in which two such levels differ, and the select of those cells' rows
+ *          (the same reconcile sending a few rows per altered key, not the whole bucket).
  *   drp_stream_stats + drp_index_scan
  *       -> no reference counterpart (the reference is single-stream); they build the
  *          global frame index after the per-GPU stats tables are all-gathered.
@@ -667,6 +671,59 @@ int drp_select_buckets_device(drp_ctx *ctx, const uint8_t *bytes, uint64_t nbyte
                               const drp_changes *cols, uint64_t n, const drp_filter *filter, uint32_t bits,
                               const uint64_t *bucket_set, const drp_change_src *out_rows, uint64_t *sel_idx,
                               uint64_t *n_selected);
+
+/* ---- refined digests: a second level inside the differing buckets --------------------------- */
+/* At DRP_DIGEST_MAX_BITS a bucket of a large store still holds many keys, and one altered key sends
+ * them all; a dense digest of more bits would outweigh the snapshot. The second level is sparse: cells
+ * only for the buckets of a set (the buckets in which the first-level digests differ), addressed by
+ * the next sub_bits bits of the same identity hash. Both hubs hold both first-level digests, so both
+ * derive the same bucket_set; each sends its second-level cells, and each then sends the rows of the
+ * cells that differ. No reference counterpart.
+ *   Defined bit for bit, as the first level is. ident, fp, the candidates and bucket(row) are those of
+ * the section above; bucket_set is the bit set drp_digest_diff_device writes for `bits`;
+ * 1 <= sub_bits <= DRP_DIGEST_MAX_SUB_BITS:
+ *     slot(b)    = the number of set bits of bucket_set below bit b        (only for a set b)
+ *     sub(row)   = (ident >> (64 - bits - sub_bits)) & (2^sub_bits - 1)    (bits = 0: ident >> (64 - sub_bits))
+ *     cell2(row) = slot(bucket(row)) * 2^sub_bits + sub(row)
+ *     n_set      = the set bits of bucket_set;   ncells = n_set << sub_bits
+ *     cells2[c]  = { count, sum of fp } of the candidates whose bucket is set and whose cell2 is c
+ * Consequence: the 2^sub_bits cells of slot s add up (count and sum, modulo 2^64) to the first-level
+ * cell of the s-th set bucket. With bits < 6 only the low 2^bits bits of the one word name buckets. */
+#define DRP_DIGEST_MAX_SUB_BITS 8
+
+/* The second-level cells of the candidates among decoded rows [0, n) whose bucket's bit is set in
+ * bucket_set (device, max(1, 2^bits / 64) words). totals (device, three entries, required): [0] the
+ * rows digested (the candidates in set buckets), [1] the selected rows left out for a range outside
+ * the wire (drp_digest_device's count, whatever the set), [2] n_set. If ncells <= cells_cap,
+ * cells2[0, ncells) (device) is zeroed and filled and the entries from ncells on are left untouched;
+ * otherwise nothing is written to cells2 and totals is still complete (drp_fanout_device's rows_cap
+ * convention). With n_set == 0 nothing is written to cells2. Of a candidate outside the set buckets
+ * only the key and subset bytes are read, never the value. The other arguments and DRP_E_INVAL cases
+ * are drp_digest_device's, and sub_bits of 0 or above DRP_DIGEST_MAX_SUB_BITS, a NULL bucket_set,
+ * cells2 or totals. Device pointers only; asynchronous on drp_stream(ctx), no host synchronisation
+ * inside; the result is a function of the input alone. Scratch from the ctx's: the filter's 512
+ * bytes and a rank table of 4 bytes per word of bucket_set. */
+int drp_digest_refine_device(drp_ctx *ctx, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                             const drp_changes *cols, uint64_t n, const drp_filter *filter, uint32_t bits,
+                             const uint64_t *bucket_set, uint32_t sub_bits, drp_digest_cell *cells2,
+                             uint64_t cells_cap, uint64_t *totals);
+/* drp_digest_diff_device for any cell count (a host number, at most 65536 << 8; the caller has n_set
+ * on the host by now, it sizes what it sends from it): cell_set (device, max(1, ceil(ncells / 64))
+ * words) gets bit c set iff a[c] and b[c] differ in count or sum, the unused high bits of the last
+ * word are 0; *n_diff (device) = the bits set. ncells == 0: *n_diff = 0 and the one word is 0.
+ * Asynchronous on drp_stream(ctx); no scratch. DRP_E_INVAL: a NULL pointer, ncells above the most. */
+int drp_digest_diff_cells_device(drp_ctx *ctx, const drp_digest_cell *a, const drp_digest_cell *b, uint64_t ncells,
+                                 uint64_t *cell_set, uint64_t *n_diff);
+/* drp_select_buckets_device with the further condition that bit cell2(row) of cell_set (device, as
+ * drp_digest_diff_cells_device writes it for ncells) is set: the same stable compaction and the same
+ * out_rows, sel_idx and n_selected contract. Under one filter, bits, bucket_set and sub_bits the rows
+ * kept are exactly the rows drp_digest_refine_device counted in the set cells. DRP_E_INVAL cases:
+ * drp_select_buckets_device's, and sub_bits of 0 or above DRP_DIGEST_MAX_SUB_BITS or a NULL cell_set.
+ * Asynchronous on drp_stream(ctx). Scratch from the ctx's: drp_select_device's and the rank table. */
+int drp_select_refined_device(drp_ctx *ctx, const uint8_t *bytes, uint64_t nbytes, const drp_frames *frames,
+                              const drp_changes *cols, uint64_t n, const drp_filter *filter, uint32_t bits,
+                              const uint64_t *bucket_set, uint32_t sub_bits, const uint64_t *cell_set,
+                              const drp_change_src *out_rows, uint64_t *sel_idx, uint64_t *n_selected);
 
 /* ---- multi-GPU global index ---------------------------------------------- */
 /* stats[nranks*per_rank] (device): all-gathered per-stream tables in rank order.

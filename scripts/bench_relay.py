@@ -66,6 +66,17 @@ probe, and the host relay through drp_relay_staged against the host round trip i
               DRP_PY); --digest-baseline reads such a file, and the ratios (digest / compact, reconcile /
               snapshot) are then over the parent's figures. With --digest-only every other leg is left out.
 
+  digest refine  (--digest-refine-out, default profiles/relay/digest_refine_bench.json; no other leg runs)
+              The digest leg's two stores and altered shares. The single-level reconcile at bits 16
+              (digest, diff, bucket select, encode), then per sub_bits in 2, 4, 8:
+              drp_digest_refine_device, drp_digest_diff_cells_device, drp_select_refined_device and
+              drp_encode_device, the rows out (checked to hold every altered key) and the bytes one hub
+              sends: first-level cells, cells2 and frames. A probe of the refine's LDS copy of the cells
+              (every row a member of 256 .. 4096 cells). --digest-refine-baseline-out: the yardsticks
+              and the single-level reconcile only, to be taken with the parent commit's library and
+              binding (DRP_LIB, DRP_PY); --digest-refine-baseline reads such a file, and the ratios are
+              then over the parent's figures.
+
 Prints one JSON line (and writes it to --out). Needs an MI355X: there is no CPU path.
 
   hipcc -O3 --offload-arch=gfx950 scripts/probe_bw.hip -o exp/probe_bw
@@ -1068,6 +1079,163 @@ def digest_leg(ctx, drp_amd, torch, frames, iters, parent=None):
     return res
 
 
+# ---- refined digests --------------------------------------------------------------------------------
+
+REFINE_SUB_BITS = (2, 4, 8)
+REFINE_SHARES = (0.001, 0.10)
+
+
+def _timers(ctx, torch, dev, iters):
+    ext = ctx._ext(dev)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record(ext)
+        fn()
+        e1.record(ext)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    return lambda fn: _stat([timed(fn) for it in range(iters + 3)][3:])
+
+
+def _peer_cols(torch, store, keys, share, dev):
+    """The digest leg's peer: the same rows with `change` raised on a random share of the keys."""
+    gen = torch.Generator(device="cpu").manual_seed(int(share * 1000))
+    hit = torch.randperm(keys, generator=gen)[:max(1, int(keys * share))].to(dev)
+    cols = dict(store.cols)
+    cols["change"] = store.cols["change"].clone()
+    cols["change"][hit] += 1
+    return cols, hit
+
+
+def _single_level(ctx, torch, store, keys, fb, iters):
+    """The single-level reconcile at RECONCILE_BITS per altered share, through calls every commit with
+    the digest has: digest, diff, bucket select, encode."""
+    dev = torch.device("cuda", 0)
+    runs = _timers(ctx, torch, dev, iters)
+    view, n, bits = store.arena, store.max_keys, RECONCILE_BITS
+    mine = torch.zeros((1 << bits, 2), dtype=torch.int64, device=dev)
+    t_dig = runs(lambda: ctx.digest_device(view, store.cols, n, None, bits, mine, None))
+    bset = torch.zeros((1 << bits) // 64, dtype=torch.int64, device=dev)
+    cnt = torch.zeros(2, dtype=torch.int64, device=dev)
+    rows = _row_tensors(torch, dev, keys)
+    foff = torch.zeros(keys + 1, dtype=torch.int64, device=dev)
+    out = torch.zeros(keys * fb, dtype=torch.uint8, device=dev)
+    res = {"digest_ms": t_dig}
+    for share in REFINE_SHARES:
+        peer_cols, hit = _peer_cols(torch, store, keys, share, dev)
+        peer = torch.zeros((1 << bits, 2), dtype=torch.int64, device=dev)
+        ctx.digest_device(view, peer_cols, n, None, bits, peer, None)
+        t_diff = runs(lambda: ctx.digest_diff_device(mine, peer, bits, bset, cnt[0:1]))
+        t_sel = runs(lambda: ctx.select_buckets_device(view, store.cols, n, None, bits, bset, rows, None, cnt[1:2]))
+        nd, nsel = [int(v) for v in cnt.cpu()]
+        t_enc = runs(lambda: ctx.encode_device(rows, view, nsel, foff, out, nsel * fb))
+        res[f"share{share}"] = {
+            "keys_altered": int(len(hit)), "buckets_differing": nd, "rows_out": nsel, "diff_ms": t_diff,
+            "select_buckets_ms": t_sel, "encode_ms": t_enc,
+            "total_ms_median": t_dig["median"] + t_diff["median"] + t_sel["median"] + t_enc["median"],
+            "bytes": {"cells": 16 << bits, "frames": nsel * fb, "total": (16 << bits) + nsel * fb}}
+    return res
+
+
+def digest_refine_baseline(ctx, drp_amd, torch, frames, iters):
+    res = {"bench": "relay_digest_refine_baseline", "frames": frames, "iters": iters}
+    for shape in ("keyed", "big_values"):
+        store, keys, fb = _digest_store(ctx, drp_amd, torch, shape, frames)
+        res[shape] = _digest_yardsticks(ctx, drp_amd, torch, store, keys, fb, iters)
+        res[shape]["single_level"] = _single_level(ctx, torch, store, keys, fb, iters)
+        print("digest refine baseline", shape, res[shape], file=sys.stderr, flush=True)
+        store = None
+        torch.cuda.empty_cache()
+    return res
+
+
+def digest_refine_leg(ctx, drp_amd, torch, frames, iters, parent=None):
+    """Per store and altered share: the single-level reconcile of this build, and per sub_bits the
+    refine, the cell diff, the refined select and the encode, the rows out and the bytes one hub sends
+    (first-level cells, cells2, frames). Ratios are over the parent's figures where given."""
+    dev = torch.device("cuda", 0)
+    runs = _timers(ctx, torch, dev, iters)
+    res = {"frames": frames, "iters": iters, "yardsticks_from": "parent" if parent else "this commit"}
+    for shape in ("keyed", "big_values"):
+        store, keys, fb = _digest_store(ctx, drp_amd, torch, shape, frames)
+        r = _digest_yardsticks(ctx, drp_amd, torch, store, keys, fb, iters)
+        r["single_level"] = _single_level(ctx, torch, store, keys, fb, iters)
+        base = (parent or {}).get(shape, r)
+        r["parent"] = base if parent else None
+        view, n, bits = store.arena, store.max_keys, RECONCILE_BITS
+        mine = torch.zeros((1 << bits, 2), dtype=torch.int64, device=dev)
+        ctx.digest_device(view, store.cols, n, None, bits, mine, None)
+        bset = torch.zeros((1 << bits) // 64, dtype=torch.int64, device=dev)
+        cnt = torch.zeros(3, dtype=torch.int64, device=dev)
+        tot = torch.zeros(3, dtype=torch.int64, device=dev)
+        rows = _row_tensors(torch, dev, keys)
+        idx_t = torch.zeros(keys, dtype=torch.int64, device=dev)
+        foff = torch.zeros(keys + 1, dtype=torch.int64, device=dev)
+        out = torch.zeros(keys * fb, dtype=torch.uint8, device=dev)
+        r["refined"] = {}
+        for share in REFINE_SHARES:
+            peer_cols, hit = _peer_cols(torch, store, keys, share, dev)
+            peer = torch.zeros((1 << bits, 2), dtype=torch.int64, device=dev)
+            ctx.digest_device(view, peer_cols, n, None, bits, peer, None)
+            ctx.digest_diff_device(mine, peer, bits, bset, cnt[0:1])
+            nd = int(cnt.cpu()[0])
+            one = base["single_level"][f"share{share}"]
+            per = {}
+            for sub_bits in REFINE_SUB_BITS:
+                ncells = nd << sub_bits
+                c_mine = torch.zeros((ncells, 2), dtype=torch.int64, device=dev)
+                c_peer = torch.zeros((ncells, 2), dtype=torch.int64, device=dev)
+                cset = torch.zeros((ncells + 63) // 64, dtype=torch.int64, device=dev)
+                ctx.digest_refine_device(view, peer_cols, n, None, bits, bset, sub_bits, c_peer, ncells, tot)
+                t_ref = runs(lambda: ctx.digest_refine_device(view, store.cols, n, None, bits, bset, sub_bits, c_mine,
+                                                              ncells, tot))
+                t = [int(v) for v in tot.cpu()]
+                assert t[1] == 0 and t[2] == nd and t[0] == one["rows_out"], ("refine totals", t, nd, one["rows_out"])
+                t_diff = runs(lambda: ctx.digest_diff_cells_device(c_mine, c_peer, ncells, cset, cnt[1:2]))
+                t_sel = runs(lambda: ctx.select_refined_device(view, store.cols, n, None, bits, bset, sub_bits, cset, rows,
+                                                               idx_t, cnt[2:3]))
+                _, nd2, nsel = [int(v) for v in cnt.cpu()]
+                got = torch.zeros(keys, dtype=torch.bool, device=dev)
+                got[idx_t[:nsel]] = True
+                assert bool(got[hit].all()) and len(hit) >= nd2 > 0 and one["rows_out"] >= nsel >= len(hit), "refined rows"
+                t_enc = runs(lambda: ctx.encode_device(rows, view, nsel, foff, out, nsel * fb))
+                assert int(foff[nsel].cpu()) == nsel * fb, "refined bytes"
+                total = (base["single_level"]["digest_ms"]["median"] + one["diff_ms"]["median"] + t_ref["median"] +
+                         t_diff["median"] + t_sel["median"] + t_enc["median"])
+                nbytes = (16 << bits) + 16 * ncells + nsel * fb
+                per[f"sub_bits{sub_bits}"] = {
+                    "cells2": ncells, "cells_differing": nd2, "rows_out": nsel, "refine_ms": t_ref, "diff_cells_ms": t_diff,
+                    "select_refined_ms": t_sel, "encode_ms": t_enc, "total_ms_median": total,
+                    "bytes": {"cells": 16 << bits, "cells2": 16 * ncells, "frames": nsel * fb, "total": nbytes},
+                    "over_single_level": total / one["total_ms_median"],
+                    "over_snapshot": total / base["snapshot"]["total_ms_median"],
+                    "bytes_over_single_level": nbytes / one["bytes"]["total"],
+                    "bytes_over_snapshot": nbytes / base["snapshot"]["out_bytes"]}
+                c_mine = c_peer = cset = None
+            r["refined"][f"share{share}"] = {
+                "keys_altered": int(len(hit)), "buckets_differing": nd,
+                "single_level_bytes_over_snapshot": one["bytes"]["total"] / base["snapshot"]["out_bytes"],
+                "single_level_over_snapshot": one["total_ms_median"] / base["snapshot"]["total_ms_median"], **per}
+            print("digest refine", shape, share, r["refined"][f"share{share}"], file=sys.stderr, flush=True)
+        # the LDS copy of the cells: every row a member, 256 and 1024 cells (summed in LDS) against 2048 and
+        # 4096 (summed in global memory)
+        r["lds_probe_ms"] = {}
+        for b in (0, 2, 3, 4):
+            full = torch.full((1,), (1 << (1 << b)) - 1, dtype=torch.int64, device=dev)
+            c2 = torch.zeros((256 << b, 2), dtype=torch.int64, device=dev)
+            r["lds_probe_ms"][f"cells{256 << b}"] = runs(
+                lambda: ctx.digest_refine_device(view, store.cols, n, None, b, full, 8, c2, 256 << b, tot))
+            assert [int(v) for v in tot.cpu()] == [keys, 0, 1 << b] and int(c2[:, 0].sum().cpu()) == keys
+        print("digest refine lds probe", shape, r["lds_probe_ms"], file=sys.stderr, flush=True)
+        res[shape] = r
+        store = view = rows = out = mine = None
+        torch.cuda.empty_cache()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20_000_000)
@@ -1099,6 +1267,13 @@ def main():
     ap.add_argument("--digest-baseline-out", default=None,
                     help="only the digest leg's yardsticks (compact, full snapshot; any commit's library), written here")
     ap.add_argument("--digest-baseline", default=None, help="such a file of the parent commit, read into the digest leg's result")
+    ap.add_argument("--digest-refine-out", nargs="?", default=None,
+                    const=os.path.join(ROOT, "profiles", "relay", "digest_refine_bench.json"),
+                    help="run only the refined-digest leg and write its JSON line here")
+    ap.add_argument("--digest-refine-baseline-out", default=None,
+                    help="only the yardsticks and the single-level reconcile (any commit's library with the digest), written here")
+    ap.add_argument("--digest-refine-baseline", default=None,
+                    help="such a file of the parent commit, read into the refined-digest leg's result")
     a = ap.parse_args()
     if a.digest_only and not a.digest_out:
         ap.error("--digest-only needs --digest-out")
@@ -1117,6 +1292,23 @@ def main():
     torch.cuda.init()
     import _streams as S
     import drp_amd
+    if a.digest_refine_baseline_out:
+        with drp_amd.Ctx(0) as ctx:
+            base = digest_refine_baseline(ctx, drp_amd, torch, a.frames, a.iters)
+        with open(a.digest_refine_baseline_out, "w") as f:
+            f.write(json.dumps(base) + "\n")
+        print(json.dumps(base))
+        return
+    if a.digest_refine_out:
+        parent = json.loads(open(a.digest_refine_baseline).read()) if a.digest_refine_baseline else None
+        assert parent is None or parent["frames"] == a.frames
+        with drp_amd.Ctx(0) as ctx:
+            dr = {"bench": "relay_digest_refine",
+                  "device": digest_refine_leg(ctx, drp_amd, torch, a.frames, a.iters, parent)}
+        with open(a.digest_refine_out, "w") as f:
+            f.write(json.dumps(dr) + "\n")
+        print(json.dumps(dr))
+        return
     if a.digest_baseline_out:
         with drp_amd.Ctx(0) as ctx:
             base = digest_baseline(ctx, drp_amd, torch, a.frames, a.iters)
