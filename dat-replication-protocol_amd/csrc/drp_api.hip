@@ -592,7 +592,7 @@ int run_decode_spec(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const uin
     P.walk_hop = c->claims_mode == 3 ? 1u : 2u;  // 2: by the density sample
     P.walk_tpr = drp_walk_tiles_per_region(NT, (int)P.walk_hop);
   }
-  // claims_fast's per-frame records (fast_records, 24 B per frame slot): emit_lean expands them into
+  // claims_fast's per-frame records (fast_records, 20 B per frame slot): emit_lean expands them into
   // columns without reading the wire again (DRP_CREC=0: off; a buffer that cannot be had: off)
   const uint64_t rec_bytes = (NT * drp_spec_rec_words() * 4ull + 255) & ~255ull;
   if (c->crec && c->recbuf.ensure(rec_bytes + (cap / 64 + 2) * 4)) {

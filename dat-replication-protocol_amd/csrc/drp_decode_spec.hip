@@ -1214,12 +1214,23 @@ __device__ __forceinline__ uint32_t fast_claims_jump(const DecodeParams &P, uint
 // expands the records of the tiles verification lets it (tile_recok) into columns without staging
 // the tile again (decode.js:144-169 / 205-214 deliver the same frames in the same order). Per tile,
 // CR_CAP slots in slot order = chain order (the threads' frame counts, prefix-summed), word-major so
-// each word of a wave's frames is one coalesced store:
+// each word of a wave's frames is one coalesced store. crec_frame gives a frame's CR_WORDS fields:
 //   w0  payload offset from the tile's first byte (14 bits) | id << 14 | partial (a blob cut by the
 //       stream end) << 16 | has value << 17 | key length varint bytes << 18
 //   w1  payload length (the header's, as the column)
 //   w2  key length | value offset << 16 (payload-relative)
 //   w3..w5 change, from, to
+// and crec_pack stores them in 2, 3 or 5 of the slot's CR_PWORDS words (crec_unpack: the same
+// CR_WORDS fields back):
+//   p0  w0's 20 bits | (value offset - key end, 0 without a value) << 20 | narrow << 25 |
+//       (payload length >> 18) << 26
+//   p1  key length (14 bits) | payload length << 14 (its low 18 bits)
+//   p2  narrow (change, from and to all < 2^10): change | from << 10 | to << 20; else change
+//   p3, p4  from, to of a record that is not narrow (a wide one)
+// A blob keeps p0 and p1, a narrow Change p0..p2, a wide one all five: fast_records stores, and
+// emit_recs loads, p3 and p4 only in the lanes of wide records, so the lines of those words are
+// never touched for a tile of narrow records. The words a record does not store keep an earlier
+// batch's bytes: only the record's own p0 says which words are its own.
 // Recorded: blob frames, and Change payloads in protocol-buffers' own shape without a subset: key
 // (length varint of <= 2 bytes) change from to [value], one-byte tags, numbers < 2^32, the last field
 // ending the payload. Anything else (a subset, longer varints, a field header near the stream end,
@@ -1229,8 +1240,19 @@ __device__ __forceinline__ uint32_t fast_claims_jump(const DecodeParams &P, uint
 #ifndef DRP_CREC_STAGE
 #define DRP_CREC_STAGE 2  // (A/B builds: 0 stops after the frame list, 1 after the field decode)
 #endif
-constexpr uint32_t CR_CAP = NT, CR_WORDS = 6, CR_TILE_WORDS = CR_CAP * CR_WORDS;
+constexpr uint32_t CR_CAP = NT, CR_WORDS = 6;
 static_assert(CR_CAP == NT, "one frame per thread in the record decode");
+// the stored form's field widths: numbers of a narrow record, value offset past the key, payload
+// length (split: the low CRP_PL_LO bits in p1), key length
+constexpr uint32_t CR_PWORDS = 5, CRP_NB = 10, CRP_VD_BITS = 5, CRP_PL_BITS = 21, CRP_KL_BITS = 14, CRP_PL_LO = 32 - CRP_KL_BITS;
+constexpr uint32_t CR_TILE_WORDS = CR_CAP * CR_PWORDS;
+static_assert(IMG + 4u <= (1u << 14), "payload offset: header offset < IMG, + 3 length bytes + the id");
+static_assert(CRP_PL_BITS == 3 * 7, "payload length: crec_frame's length varint of <= 3 bytes");
+static_assert(CRP_KL_BITS == 2 * 7, "key length: crec_frame's key varint of <= 2 bytes");
+static_assert(3u * (1u + 5u) + 1u + 4u < (1u << CRP_VD_BITS), "value offset past the key: three numbers of <= 5 bytes, "
+                                                               "the value's tag and length of <= 4 bytes");
+static_assert(3 * CRP_NB <= 32, "a narrow record's three numbers share p2");
+static_assert(26 + CRP_PL_BITS - CRP_PL_LO <= 32 && 20 + CRP_VD_BITS <= 25, "p0's fields");
 
 // one frame's fields from the 28 bytes at payload-relative ke (numbers of any width up to 5 bytes,
 // value length up to 4 bytes): false when the payload is in another shape
@@ -1338,6 +1360,41 @@ __device__ __forceinline__ bool crec_frame(const uint32_t *w32, uint32_t o, uint
   return ok;
 }
 
+// The stored form of a record crec_frame accepted (layout above): the number of words of p that
+// hold it (2, 3 or 5), or 0 when a field does not fit its width (the tile then has no records;
+// nothing is truncated).
+__device__ __forceinline__ uint32_t crec_pack(const uint32_t (&w)[CR_WORDS], uint32_t (&p)[CR_PWORDS]) {
+  const uint32_t id = (w[0] >> 14) & 3u, hv = (w[0] >> 17) & 1u, kb = (w[0] >> 18) & 3u;
+  const uint32_t pl = w[1], klen = w[2] & 0xFFFFu, vo = w[2] >> 16;
+  const uint32_t vd = hv ? vo - (1u + kb + klen) : 0u;  // (a value offset before the key's end: does not fit)
+  bool fits = !(w[0] >> 20) && pl < (1u << CRP_PL_BITS) && klen < (1u << CRP_KL_BITS) && vd < (1u << CRP_VD_BITS);
+  fits = fits && (hv || !vo) && (id == 1u || !(hv | kb | w[2] | w[3] | w[4] | w[5]));
+  const bool narrow = (w[3] | w[4] | w[5]) < (1u << CRP_NB);
+  p[0] = w[0] | (vd << 20) | ((narrow ? 1u : 0u) << 25) | ((pl >> CRP_PL_LO) << 26);
+  p[1] = klen | (pl << CRP_KL_BITS);
+  p[2] = narrow ? w[3] | (w[4] << CRP_NB) | (w[5] << (2u * CRP_NB)) : w[3];
+  p[3] = w[4];
+  p[4] = w[5];
+  return !fits ? 0u : (id != 1u ? 2u : (narrow ? 3u : 5u));
+}
+// crec_frame's words back from the stored form: p[2] is read only for a Change, p[3] and p[4]
+// only for a wide one (callers need not load the words a record does not hold).
+__device__ __forceinline__ void crec_unpack(const uint32_t (&p)[CR_PWORDS], uint32_t (&w)[CR_WORDS]) {
+  const uint32_t hv = (p[0] >> 17) & 1u, kb = (p[0] >> 18) & 3u, vd = (p[0] >> 20) & ((1u << CRP_VD_BITS) - 1u);
+  const bool ch = ((p[0] >> 14) & 3u) == 1u, narrow = (p[0] >> 25) & 1u;
+  const uint32_t klen = p[1] & ((1u << CRP_KL_BITS) - 1u), m = (1u << CRP_NB) - 1u;
+  w[0] = p[0] & 0xFFFFFu;
+  w[1] = (p[1] >> CRP_KL_BITS) | (((p[0] >> 26) & ((1u << (CRP_PL_BITS - CRP_PL_LO)) - 1u)) << CRP_PL_LO);
+  w[2] = ch ? klen | ((hv ? 1u + kb + klen + vd : 0u) << 16) : 0u;
+  w[3] = !ch ? 0u : (narrow ? p[2] & m : p[2]);
+  w[4] = !ch ? 0u : (narrow ? (p[2] >> CRP_NB) & m : p[3]);
+  w[5] = !ch ? 0u : (narrow ? (p[2] >> (2u * CRP_NB)) & m : p[4]);
+}
+// the words of the record whose first word is p0 (crec_pack's count)
+__device__ __forceinline__ uint32_t crec_words(uint32_t p0) {
+  return ((p0 >> 14) & 3u) != 1u ? 2u : (((p0 >> 25) & 1u) ? 3u : 5u);
+}
+
 // Records of the tile's delivered frames (after the claim; whole workgroup). E / nf: this thread's
 // settled entry and frame count (0 for a non-carrier), exactly as its per-thread record has them.
 // v / hv: this thread's 64 bytes of the tile and (threads < HALO / 16) 16 bytes of the halo, still
@@ -1382,17 +1439,21 @@ __device__ __forceinline__ void fast_records(const DecodeParams &P, uint64_t t, 
     uint32_t w[CR_WORDS];
     bad = !crec_frame(reinterpret_cast<const uint32_t *>(S.img), f & 0x3FFFu, min(se_rel, IMG), (f >> 14) & 3u,
                       (f >> 16) & 1u, w);
+    uint32_t p[CR_PWORDS];
+    const uint32_t np = crec_pack(w, p);
+    bad = bad || !np;
     uint32_t *rr = DRP_KARG(rec) + t * CR_TILE_WORDS + tid;
     if (DRP_CREC_STAGE == 1) {  // (A/B: keep the decode, store nothing)
-      if ((w[0] ^ w[2] ^ w[3] ^ w[4] ^ w[5]) == 0x7FFFFFFFu && !bad) rr[0] = w[1];
+      if ((p[0] ^ p[2] ^ p[3] ^ p[4]) == 0x7FFFFFFFu && !bad) rr[0] = p[1];
       bad = true;
     }
     if (!bad) {
-      rr[0] = w[0];
-      rr[CR_CAP] = w[1];
-      if ((w[0] >> 14 & 3u) == 1u) {
-#pragma unroll
-        for (uint32_t k = 2; k < CR_WORDS; k++) rr[k * CR_CAP] = w[k];
+      rr[0] = p[0];
+      rr[CR_CAP] = p[1];
+      if (np > 2u) rr[2 * CR_CAP] = p[2];
+      if (np > 3u) {  // (a wide record: a tile of narrow ones never touches these lines)
+        rr[3 * CR_CAP] = p[3];
+        rr[4 * CR_CAP] = p[4];
       }
     }
   }
@@ -2741,7 +2802,8 @@ __device__ __forceinline__ void st_col(T *base, uint32_t i, T v) {
 
 // ---- record emission: columns from claims_fast's per-frame records (fast_records) -------------
 // The tiles verification lets it take (tile_recok = 1 + the slot of the tile's first row): rows
-// [tile_base, + tile_count) from slot tile_recok - 1 on. Reads 24 B per row and writes the columns;
+// [tile_base, + tile_count) from slot tile_recok - 1 on. Reads 12 B per row of narrow records (20 B in
+// the lanes of wide ones, 8 B of a blob's 12 used) and writes the columns;
 // the wire is not read again.
 // one row (i: relative to C's first row): its columns from the record words (the tile's first
 // byte at A)
@@ -2793,31 +2855,61 @@ __global__ __launch_bounds__(ER_WAVES * WAVE) void emit_recs(DecodeParams P) {
   const uint64_t total = umin64(ldc(P.tile_base + ntiles - 1) + ldc(P.tile_count + ntiles - 1), P.cap);
   if (c * 64 >= total) return;  // (whole wave)
   const uint64_t r = c * 64 + lane;
-  const uint64_t t0 = ldc(P.chunk_tile + c);
-  const uint64_t t1 = (c + 1) * 64 < total ? (uint64_t)ldc(P.chunk_tile + c + 1) : ntiles - 1;
-  // this lane's tile: the last tile in [t0, t1] whose first row is <= r
-  uint64_t t = t0;
-  const uint64_t b1 = t1 > t0 ? ldc(P.tile_base + t0 + 1) : ~0ull;
-  if (t1 == t0 + 1 || t1 == t0) {  // (nearly always: tiles of more than 64 rows)
-    if (r >= b1) t = t0 + 1;
-  } else if (r >= b1) {  // (tiles of few rows, or runs of empty tiles: search)
-    uint64_t lo = t0 + 1, hi = t1;  // base[lo] <= r; find the last such
-    while (lo < hi) {
-      const uint64_t mid = (lo + hi + 1) >> 1;
-      if (P.tile_base[mid] <= r) lo = mid;
-      else hi = mid - 1;
+  // (the next chunk's tile is loaded whether or not it is used: chunk_tile has the slot, and the
+  // two loads go together)
+  const uint64_t t0 = ldc(P.chunk_tile + c), t1n = ldc(P.chunk_tile + c + 1);
+  const uint64_t t1 = (c + 1) * 64 < total ? t1n : ntiles - 1;
+  // This lane's tile: the last tile in [t0, t1] whose first row is <= r. Nearly always (tiles of
+  // more than 64 rows) that is t0 or t0 + 1, both uniform: the first row, the mark and the
+  // geometry of both tiles are then loaded together, one round trip after chunk_tile's, and the
+  // lane picks; the record words follow. (A load each of base, mark and geometry behind the
+  // lane's choice of tile, as before the records were packed, made five dependent round trips
+  // of a wave's life, and emit_recs' time follows their number, not its bytes.)
+  uint64_t t, bt, A;
+  uint32_t rk;
+  if (t1 <= t0 + 1) {
+    const uint64_t tn = t1;  // (t0 itself when the chunk lies in one tile)
+    const uint64_t bt0 = ldc(P.tile_base + t0), bt1 = ldc(P.tile_base + tn);
+    const uint32_t rk0 = ldc(P.tile_recok + t0), rk1 = ldc(P.tile_recok + tn);
+    // (tile_geo's A for both, their stream indices loaded together before either's offsets)
+    uint64_t s0 = 0, s1 = 0;
+    if (P.tile_stream) {
+      s0 = umin64(ldc(P.tile_stream + t0), P.nstreams - 1);
+      s1 = umin64(ldc(P.tile_stream + tn), P.nstreams - 1);
     }
-    t = lo;
+    const uint64_t tf0 = ldc(P.tile_prefix + s0), tf1 = ldc(P.tile_prefix + s1);
+    const uint64_t so0 = ldc(P.stream_off + s0), so1 = ldc(P.stream_off + s1);
+    const uint64_t A0 = (so0 & ~(uint64_t)(TILE - 1)) + (t0 - tf0) * TILE, A1 = (so1 & ~(uint64_t)(TILE - 1)) + (tn - tf1) * TILE;
+    const bool nx = tn != t0 && r >= bt1;
+    t = nx ? tn : t0;
+    bt = nx ? bt1 : bt0;
+    rk = nx ? rk1 : rk0;
+    A = nx ? A1 : A0;
+  } else {  // (tiles of few rows, or runs of empty tiles: search)
+    t = t0;
+    if (r >= ldc(P.tile_base + t0 + 1)) {
+      uint64_t lo = t0 + 1, hi = t1;  // base[lo] <= r; find the last such
+      while (lo < hi) {
+        const uint64_t mid = (lo + hi + 1) >> 1;
+        if (P.tile_base[mid] <= r) lo = mid;
+        else hi = mid - 1;
+      }
+      t = lo;
+    }
+    A = tile_geo(P, t).A;
+    rk = P.tile_recok[t];
+    bt = P.tile_base[t];
   }
-  if (r >= total) return;
-  const uint32_t rk = P.tile_recok[t];
-  if (!rk) return;  // (emit_lean writes this row)
-  const uint64_t bt = P.tile_base[t];
+  if (r >= total || !rk) return;  // (no record: emit_lean writes this row)
   const uint32_t *rr = P.rec + t * CR_TILE_WORDS + (uint32_t)(r - bt) + rk - 1u;
-  uint32_t w[CR_WORDS];
-#pragma unroll
-  for (uint32_t k = 0; k < CR_WORDS; k++) w[k] = rr[k * CR_CAP];
-  const uint64_t A = tile_geo(P, t).A;
+  // (p2 with the first two, whatever the record is: a blob's is an earlier batch's and not used;
+  // p3 and p4, a second round trip, only in the lanes p0 says are wide)
+  uint32_t p[CR_PWORDS] = {rr[0], rr[CR_CAP], rr[2 * CR_CAP], 0u, 0u}, w[CR_WORDS];
+  if (crec_words(p[0]) > 3u) {
+    p[3] = rr[3 * CR_CAP];
+    p[4] = rr[4 * CR_CAP];
+  }
+  crec_unpack(p, w);
   const RowCols C = row_cols(P, c * 64);
   emit_rec_row(C, lane, A, w[0], w[1], w[2], w[3], w[4], w[5]);
 }

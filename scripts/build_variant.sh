@@ -6,7 +6,7 @@ NAME=$1; shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/exp/$NAME
 mkdir -p $OUT/build
-SRCS="drp_decode drp_decode_spec drp_walk drp_encode drp_select drp_latest drp_store drp_fanout drp_keys drp_comm drp_api drp_relay"
+SRCS="drp_decode drp_decode_spec drp_walk drp_encode drp_select drp_latest drp_store drp_digest drp_fanout drp_keys drp_comm drp_api drp_relay"
 FLAGS="-O3 -std=c++17 -fPIC -fvisibility=hidden -fno-strict-aliasing --offload-arch=gfx950 -Wno-unused-result -Wno-unused-value $*"
 pids=""
 for s in $SRCS; do
