@@ -141,6 +141,7 @@ struct drp_ctx {
   int blob_skip = DRP_BLOB_SKIP_AUTO;
   uint64_t latest_hash_mask = ~0ull;  // drp_set_latest_hash_mask (test hook)
   uint32_t fanout_latest_pass = 0;    // drp_set_fanout_latest_pass (test hook; 0: FLAT_PASS_DEFAULT)
+  int order_skip = 1;                 // drp_order_device switches constant-digit passes off (DRP_ORDER_SKIP=0: A/B)
   bool blob_heavy = false;     // the last host batch was mostly blob payload (AUTO: stage in pieces)
   uint64_t blob_run = 0;       // bytes from a piece's start to its blob's payload, last seen
   uint64_t piece_span = 0;     // batch bytes one blob-skipping piece covered on average, last seen

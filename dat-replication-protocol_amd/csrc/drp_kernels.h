@@ -297,6 +297,36 @@ constexpr uint32_t DIG_RANK_BLK = 1024;  // one workgroup, one word of the set p
 // up to DIG_LDS_BITS bits (DESIGN.md "Refined digests" has the measurement)
 constexpr uint32_t DIG_REFINE_LDS_CELLS = 1u << DIG_LDS_BITS;
 
+// drp_order.hip: the segmented order-by-change of encoder rows. A sort workgroup takes ORD_TILE
+// (change, row) pairs; a pass's count table holds 256 counts per workgroup and is scanned in
+// first-level blocks of ORD_SCAN; passes 0 .. 7 take the key's bytes, pass ORD_SEG_PASS the segment
+constexpr uint32_t ORD_TILE = 4096, ORD_SCAN = 1024, ORD_PASSES = 9, ORD_SEG_PASS = 8;
+// the control block, written on the device (ord_init, ord_plan)
+struct OrdCtl {
+  uint64_t n, b0, nwg;  // rows that take part (0: the input is not valid), row_base[0], ceil(n / ORD_TILE)
+  uint32_t act[ORD_PASSES], src[ORD_PASSES];  // the pass runs; what it reads (0: the input, 1 / 2: a pair buffer)
+  uint32_t final_src, valid;                  // where the finished permutation lies (0: it is the identity)
+};
+struct OrderParams {
+  drp_change_src rows;
+  const uint64_t *row_base;  // [nseg + 1]
+  uint32_t nseg, flags;
+  uint64_t rows_cap;
+  RowOut out;               // out.sel_idx: the permuted sel_idx, may be null
+  const uint64_t *sel_idx;  // read where out.sel_idx is set
+  uint64_t *out_base;       // [nseg + 1]
+  uint32_t skip;            // 1: a pass whose digit is the same in every key does not run
+  // scratch, placed by the launcher: per sort workgroup the OR and the AND of its keys, two pair
+  // buffers of rows_cap entries (keys, rows), the count table, its block sums
+  OrdCtl *ctl;
+  uint64_t *part_or, *part_and, *key[2];
+  uint32_t *idx[2], *hist, *bsum;
+};
+// the per-segment limits as a launch argument (UINT64_MAX: none)
+struct OrdLimits {
+  uint64_t v[DRP_FANOUT_MAX];
+};
+
 }  // namespace drp
 
 extern "C" {
@@ -415,6 +445,13 @@ hipError_t drp_launch_digest_refine(const drp::RefineParams *R, const drp::Selec
                                     hipStream_t st);
 hipError_t drp_launch_select_refined(const drp::RefineParams *R, const drp::SelectBytes *fb, void *scratch,
                                      hipStream_t st);
+// drp_order.hip. Scratch for rows_cap entries: 24 bytes per entry (two buffers of 8-byte keys and
+// 4-byte rows) and 1 KiB of counts, 16 bytes of key bits and 1 byte of block sums per ORD_TILE
+// entries. out_max: an upper bound of the rows all outputs hold together (the limits' sum, saturated;
+// with DRP_ORDER_KEEP_TIES an output may pass its limit: ~0).
+uint64_t drp_order_scratch_bytes(uint64_t rows_cap);
+hipError_t drp_launch_order(const drp::OrderParams *P, const drp::OrdLimits *lim, uint64_t out_max, void *scratch,
+                            hipStream_t st);
 hipError_t drp_launch_fanout_scatter(const drp::FanParams *P, hipStream_t st);
 hipError_t drp_launch_fanout_splice(const drp::FanParams *P, hipStream_t st);
 // out_off[f] = frame_off[row_base[f]] (f <= nfilters); blob_pos[f * nb + j] = frame_off[row_base[f] +

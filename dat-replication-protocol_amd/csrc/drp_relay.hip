@@ -5,9 +5,9 @@
 // drp_fanout_latest_device / drp_fanout_latest_staged (latest per key under each), and the store
 // (drp_store_*: the latest-per-key step, then the merge into caller-owned device memory), and the
 // digest calls (drp_digest_device, drp_digest_diff_device, drp_select_buckets_device, and their second
-// level drp_digest_refine_device, drp_digest_diff_cells_device, drp_select_refined_device). The kernels
-// are in drp_select.hip, drp_latest.hip, drp_fanout.hip, drp_store.hip and drp_digest.hip; the
-// context is drp_api.hip's (drp_ctx.h).
+// level drp_digest_refine_device, drp_digest_diff_cells_device, drp_select_refined_device), and the ordered
+// catch-up (drp_order_device). The kernels are in drp_select.hip, drp_latest.hip, drp_fanout.hip,
+// drp_store.hip, drp_digest.hip and drp_order.hip; the context is drp_api.hip's (drp_ctx.h).
 #include <algorithm>
 #include <cstring>
 
@@ -525,6 +525,44 @@ int drp_select_refined_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes,
   R.d.sel.out = row_out(out_rows, sel_idx);
   R.d.sel.n_selected = n_selected;
   CHK(drp_launch_select_refined(&R, &fb, c->scratch.p, c->st));
+  return DRP_OK;
+}
+
+// ---- ordered catch-up ---------------------------------------------------------------------------
+static bool src_cols_ok(const drp_change_src *r) {
+  return r->key_off && r->key_len && r->subset_off && r->subset_len && r->value_off && r->value_len && r->change &&
+         r->from && r->to && r->flags;
+}
+
+int drp_order_device(drp_ctx *c, const drp_change_src *rows, const uint64_t *row_base, uint32_t nseg,
+                     uint64_t rows_cap, const uint64_t *limit, uint32_t flags, const drp_change_src *out_rows,
+                     const uint64_t *sel_idx, uint64_t *out_sel_idx, uint64_t *out_base) {
+  if (!c || !rows || !row_base || !out_rows || !out_base || nseg == 0 || nseg > DRP_FANOUT_MAX) return DRP_E_INVAL;
+  if ((flags & ~(uint32_t)DRP_ORDER_KEEP_TIES) || (out_sel_idx && !sel_idx) || rows_cap > 0xFFFFFFFFull)
+    return DRP_E_INVAL;
+  if (rows_cap && (!src_cols_ok(rows) || !src_cols_ok(out_rows))) return DRP_E_INVAL;
+  if (out_rows->change && out_rows->change == rows->change) return DRP_E_INVAL;  // (no in-place sort)
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  // (the decode scratch: free between decodes, and every user is ordered on the ctx's stream)
+  if (!c->scratch.ensure(drp_order_scratch_bytes(rows_cap))) return DRP_E_NOMEM;
+  OrderParams P = {};
+  OrdLimits L;
+  uint64_t out_max = 0;
+  for (uint32_t f = 0; f < DRP_FANOUT_MAX; f++) {
+    L.v[f] = limit && f < nseg ? limit[f] : ~0ull;
+    if (f < nseg) out_max = out_max + L.v[f] < out_max ? ~0ull : out_max + L.v[f];
+  }
+  P.rows = *rows;
+  P.row_base = row_base;
+  P.nseg = nseg;
+  P.flags = flags;
+  P.rows_cap = rows_cap;
+  P.out = row_out(out_rows, out_sel_idx);
+  P.sel_idx = sel_idx;
+  P.out_base = out_base;
+  P.skip = c->order_skip ? 1 : 0;
+  if (flags & DRP_ORDER_KEEP_TIES) out_max = ~0ull;  // (a cut that moves to its run's end passes the limit)
+  CHK(drp_launch_order(&P, &L, out_max, c->scratch.p, c->st));
   return DRP_OK;
 }
 

@@ -33,7 +33,7 @@ EXPORTS = [
     "drp_latest_device", "drp_latest_staged", "drp_set_latest_hash_mask",
     "drp_fanout_latest_device", "drp_fanout_latest_staged", "drp_set_fanout_latest_pass",
     "drp_store_table_bytes", "drp_store_init", "drp_store_merge_device", "drp_store_merge_staged",
-    "drp_store_compact", "drp_store_query",
+    "drp_store_compact", "drp_store_query", "drp_order_device",
     "drp_digest_device", "drp_digest_diff_device", "drp_select_buckets_device",
     "drp_digest_refine_device", "drp_digest_diff_cells_device", "drp_select_refined_device",
     "drp_comm_id", "drp_comm_init_rank", "drp_comm_init_all", "drp_comm_destroy",
@@ -48,6 +48,8 @@ SEL_MAX_BYTES = 256
 FANOUT_MAX = 64
 DIGEST_MAX_BITS = 16
 DIGEST_MAX_SUB_BITS = 8
+ORDER_KEEP_TIES = 1
+ORDER_TILE, ORDER_SCAN = 4096, 1024  # csrc/drp_kernels.h ORD_TILE, ORD_SCAN: pairs per sort workgroup, counts per scan block
 DIGEST_LDS_BITS = 10  # csrc/drp_kernels.h DIG_LDS_BITS: up to here dig_cells sums in LDS, above in global memory
 COMM_ID_BYTES = 128
 
@@ -226,6 +228,7 @@ def lib():
         L.drp_store_merge_staged.argtypes = [P, C.POINTER(StoreDesc), C.POINTER(Filter), C.POINTER(StoreInfo)]
         L.drp_store_compact.argtypes = [P, C.POINTER(StoreDesc), P, U64]
         L.drp_store_query.argtypes = [P, C.POINTER(StoreDesc), C.POINTER(StoreInfo)]
+        L.drp_order_device.argtypes = [P, C.POINTER(ChangeSrc), P, U32, U64, P, U32, C.POINTER(ChangeSrc), P, P, P]
         L.drp_digest_device.argtypes = [P, P, U64, C.POINTER(Frames), C.POINTER(Changes), U64, C.POINTER(Filter), U32,
                                         P, P]
         L.drp_digest_diff_device.argtypes = [P, P, P, U32, P, P]
@@ -257,7 +260,7 @@ def lib():
                   "drp_fanout_device", "drp_fanout_staged", "drp_latest_device", "drp_latest_staged",
                   "drp_set_latest_hash_mask", "drp_fanout_latest_device", "drp_fanout_latest_staged",
                   "drp_set_fanout_latest_pass", "drp_store_init", "drp_store_merge_device", "drp_store_merge_staged",
-                  "drp_store_compact", "drp_store_query", "drp_digest_device", "drp_digest_diff_device",
+                  "drp_store_compact", "drp_store_query", "drp_order_device", "drp_digest_device", "drp_digest_diff_device",
                   "drp_select_buckets_device", "drp_digest_refine_device", "drp_digest_diff_cells_device",
                   "drp_select_refined_device", "drp_stream_stats_from_results", "drp_device", "drp_comm_id", "drp_comm_init_rank",
                   "drp_comm_init_all", "drp_index_allgather", "drp_index_allgather_multi",
@@ -727,6 +730,33 @@ class Ctx:
         _chk("drp_store_query", self.L.drp_store_query(self.h, C.byref(store.desc()), C.byref(info)))
         return info
 
+    # ---- ordered catch-up: a fan-out's outputs in change order, with a per-peer limit -------------
+    def order_device(self, rows, row_base_t, nseg, rows_cap, out_rows, out_base_t, limit=None, keep_ties=False,
+                     sel_idx_t=None, out_sel_idx_t=None, flags=None):
+        """drp_order_device over torch CUDA tensors (asynchronous, on this ctx's stream): rows and
+        row_base_t (int64, nseg + 1) as fanout_device / fanout_latest_device leave them, out_rows a
+        second set of drp_change_src columns of rows_cap entries, out_base_t (int64, nseg + 1) the
+        bounds of the outputs. Output f holds the rows of segment f in ascending change (unsigned,
+        ties in input order), cut to limit[f] rows (limit: None, one int for every segment, or a list;
+        an entry of None or 2**64 - 1: no limit); keep_ties: a cut inside a run of equal change moves
+        to the run's end. out_sel_idx_t receives sel_idx_t in the same order (both int64, rows_cap
+        entries). flags overrides the flag word (tests of the error returns)."""
+        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        mk = lambda r: C.byref(ChangeSrc(*[tp(r.get(k)) for k in SRC_COLS])) if r is not None else None
+        lim = None
+        if limit is not None:
+            vals = [limit] * nseg if isinstance(limit, int) else list(limit)
+            lim = (U64 * max(1, len(vals)))(*[0xFFFFFFFFFFFFFFFF if v is None else int(v) for v in vals])
+        fl = (ORDER_KEEP_TIES if keep_ties else 0) if flags is None else flags
+        ref = next((t for t in (row_base_t, out_base_t) if t is not None), None)
+        if ref is not None:
+            self.order_after_torch(ref)
+        rc = self.L.drp_order_device(self.h, mk(rows), tp(row_base_t), nseg, rows_cap, lim, fl, mk(out_rows),
+                                     tp(sel_idx_t), tp(out_sel_idx_t), tp(out_base_t))
+        _chk("drp_order_device", rc)
+        if ref is not None:
+            self.order_torch_after(ref)
+
     # ---- digest / reconcile: what differs between two stores ------------------------------------
     def digest_device(self, wire_t, cols, n, filter, bits, cells_t, totals_t=None):
         """drp_digest_device over torch CUDA tensors (asynchronous, on this ctx's stream): wire_t and
@@ -910,6 +940,41 @@ class Store:
         self.ctx.encode_device(rows, self.arena[:self.arena_bytes], total, foff, out, int(need.value))
         fo, o = foff.cpu().numpy(), out.cpu().numpy()
         return [o[int(fo[rb[f]]):int(fo[rb[f + 1]])].tobytes() for f in range(len(filters))]
+
+    def catch_up(self, filters, limit=None, keep_ties=True, n=None):
+        """The ordered catch-up: fanout_rows over the store, one order_device and one encode_device
+        with the arena as the heap. filters as fanout takes them (peer f at version T: change_range=
+        (T + 1, 2**64 - 1)); limit: None, one int for every peer, or a list (rows per page); keep_ties:
+        a page never ends inside a run of equal change. Returns, per filter, (wire bytes, rows sent,
+        last_change): the peer's rows in ascending change as change frames, their number, and the
+        change of the last one (None for an empty page). The paging loop: send a page, the peer's new
+        T is last_change, repeat until a page is empty."""
+        import torch
+        K = len(filters)
+        rows, base = self.fanout_rows(filters, n)
+        total = int(base.cpu()[K])  # (torch's stream was ordered after the ctx's)
+        if total == 0:
+            return [(b"", 0, None)] * K
+        dev = self.arena.device
+        out_rows = {k: torch.zeros(total, dtype=v.dtype, device=dev) for k, v in rows.items()}
+        out_base = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+        self.ctx.order_device(rows, base, K, total, out_rows, out_base, limit=limit, keep_ties=keep_ties)
+        ob = [int(v) for v in out_base.cpu()]
+        sent = ob[K]
+        if sent == 0:
+            return [(b"", 0, None)] * K
+        src = ChangeSrc(*[C.c_void_p(out_rows[k].data_ptr()) for k in SRC_COLS])
+        need = U64()
+        _chk("drp_encode_size", self.ctx.L.drp_encode_size(self.ctx.h, C.byref(src), sent, C.byref(need)))
+        foff = torch.zeros(sent + 1, dtype=torch.int64, device=dev)
+        out = torch.zeros(max(int(need.value), 1), dtype=torch.uint8, device=dev)
+        self.ctx.encode_device(out_rows, self._view(), sent, foff, out, int(need.value))
+        fo, o = foff.cpu().numpy(), out.cpu().numpy()
+        ends = [ob[f + 1] - 1 for f in range(K) if ob[f + 1] > ob[f]]
+        last = out_rows["change"][torch.tensor(ends, dtype=torch.int64, device=dev)].cpu().numpy().view(np.uint64)
+        last = dict(zip(ends, (int(v) for v in last)))
+        return [(o[int(fo[ob[f]]):int(fo[ob[f + 1]])].tobytes(), ob[f + 1] - ob[f], last.get(ob[f + 1] - 1)
+                 if ob[f + 1] > ob[f] else None) for f in range(K)]
 
     def _view(self):
         return self.arena[:self.arena_bytes] if self.arena_bytes else self.arena[:0]

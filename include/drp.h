@@ -33,6 +33,9 @@
  *       -> no reference counterpart: the latest Change per (subset, key) over every batch merged so
  *          far, resident in caller-owned device memory in the layout of a decoded batch, so the
  *          relay calls above run over it unchanged (a hub answering "what changed since T?").
+ *   drp_order_device
+ *       -> no reference counterpart: the rows of every fan-out output in ascending `change` (schema
+ *          messages/schema.proto:1-8), cut to a per-peer limit (a catch-up a peer can resume or page).
  *   drp_digest_device / drp_digest_diff_device / drp_select_buckets_device
  *       -> no reference counterpart: a digest of the rows per bucket of identities, the buckets in
  *          which two digests differ, and the select of those buckets' rows (two hubs without a shared
@@ -607,6 +610,42 @@ int drp_store_compact(drp_ctx *ctx, const drp_store *s, uint8_t *arena2, uint64_
 int drp_store_query(drp_ctx *ctx, const drp_store *s, drp_store_info *info_host);
 /* drp_set_latest_hash_mask applies to the store's table as well (test hook): a store must see one
  * mask from drp_store_init on, for its whole life. */
+
+/* ---- ordered catch-up: a fan-out's outputs in `change` order, with a per-peer limit ---------- */
+/* Every output of the select, fan-out and latest calls above is in row order; over a store that is
+ * the order in which identities first entered. A peer names its position in a feed by one number,
+ * its version T, so a catch-up it can resume ("I have everything up to T'") or take in pages ("the
+ * next M changes after T") must reach it in `change` order. The call below sits between a fan-out
+ * and the encode. No reference counterpart (the reference has no relay); the field read is `change`
+ * of messages/schema.proto:1-8.
+ *   Order: output segment f holds the rows of input segment f in ascending `change`, compared as
+ * unsigned 64-bit; rows of equal `change` keep their input order (after a fan-out: source row order).
+ *   Limit: limit is a HOST array of nseg entries, read before the call returns (NULL, or an entry of
+ * UINT64_MAX: no limit). With cnt_f = row_base[f + 1] - row_base[f], output f keeps the first
+ * min(cnt_f, limit[f]) rows of that order. With DRP_ORDER_KEEP_TIES a cut that falls inside a run of
+ * equal `change` moves forward to the end of the run: the output may then exceed the limit, never
+ * cnt_f, a limit of 0 still keeps nothing, and a peer that resumes with change > the last change
+ * sent loses no row and every page makes progress. Without the flag the cut is exact. */
+#define DRP_ORDER_KEEP_TIES 0x01
+/* rows: encoder rows (rows_cap entries per array) and row_base (device, nseg + 1 entries) as
+ * drp_fanout_device and drp_fanout_latest_device leave them: segment f is rows [row_base[f],
+ * row_base[f + 1]). out_rows: a second, caller-owned set of rows_cap entries per array; out_base
+ * (device, nseg + 1 entries): out_base[0] = 0, out_base[f + 1] = out_base[f] + the rows output f
+ * keeps, so the outputs lie end to end and one drp_encode_device over out_base[nseg] rows encodes
+ * every peer's page. out_sel_idx (may be NULL; needs sel_idx) receives sel_idx in the same order.
+ * Entries of out_rows and out_sel_idx at or beyond out_base[nseg] are left untouched. Not a valid
+ * input: row_base[nseg] > rows_cap (the fan-out wrote no rows then), or a row_base that is not
+ * non-decreasing; out_base[0 .. nseg] is then all 0 and out_rows and out_sel_idx are left untouched.
+ * The result is a function of the input alone. Device pointers only; asynchronous on
+ * drp_stream(ctx), no host synchronisation inside (the counts are read on the device).
+ * DRP_E_INVAL: nseg 0 or above DRP_FANOUT_MAX; a NULL rows, row_base, out_rows or out_base (or, with
+ * rows_cap > 0, a NULL array in rows or out_rows); out_sel_idx without sel_idx; out_rows->change ==
+ * rows->change (no in-place sort); unknown flag bits; rows_cap above 2^32 - 1 (row indices are
+ * 32-bit inside). Scratch, from the ctx's (DRP_E_NOMEM if it cannot be had): 24 bytes per entry of
+ * rows_cap, and about 1 KiB per 4096 entries. */
+int drp_order_device(drp_ctx *ctx, const drp_change_src *rows, const uint64_t *row_base, uint32_t nseg,
+                     uint64_t rows_cap, const uint64_t *limit, uint32_t flags, const drp_change_src *out_rows,
+                     const uint64_t *sel_idx, uint64_t *out_sel_idx, uint64_t *out_base);
 
 /* ---- digest / reconcile: what differs between two stores, without a shared version ---------- */
 /* "What changed since T?" needs two parties that share one `change` counter. Two hubs that each hold

@@ -77,6 +77,18 @@ probe, and the host relay through drp_relay_staged against the host round trip i
               binding (DRP_LIB, DRP_PY); --digest-refine-baseline reads such a file, and the ratios are
               then over the parent's figures.
 
+  order       (--order-out, default profiles/relay/order_bench.json; no other leg runs) The store leg's
+              final store and its catch-up shapes K = 1, 8, 64. Per shape, HIP events, three warm-up
+              rounds and --iters timed ones: drp_fanout_device and drp_encode_device over all rows (the
+              yardstick), drp_order_device alone, the same with limit = 1000 per peer and the encode of
+              those pages, drp_order_device with every pass left on (a second ctx opened under
+              DRP_ORDER_SKIP=0), and both again over uniform 64-bit keys in the same rows. Every timed
+              call's output is checked once against numpy's stable argsort per segment.
+              --order-baseline-out: only the yardstick, to be taken with the parent commit's library
+              and binding (DRP_LIB, DRP_PY); --order-baseline reads such a file, and the ratio order /
+              encode is then also given over the parent's figure. --order-profile: K = 64 and the plain
+              calls alone, for a rocprofv3 --kernel-trace --stats run (profiles/relay/order_kernel_stats.csv).
+
 Prints one JSON line (and writes it to --out). Needs an MI355X: there is no CPU path.
 
   hipcc -O3 --offload-arch=gfx950 scripts/probe_bw.hip -o exp/probe_bw
@@ -900,6 +912,145 @@ def store_leg(ctx, drp_amd, torch, frames, seqs, iters):
     return res
 
 
+# ---- ordered catch-up -----------------------------------------------------------------------------
+
+ORDER_KS = (1, 8, 64)
+ORDER_LIMIT = 1000
+
+
+def _final_store(ctx, drp_amd, torch, frames):
+    """The store leg's final store: the keyed stream merged as 8 batches into an empty store, compacted."""
+    dev = torch.device("cuda", 0)
+    key_ids, wire_t, cols, n, m = _store_input(ctx, drp_amd, torch, frames)
+    keys = int(len(np.unique(key_ids)))
+    store = drp_amd.Store(ctx, keys, 80 * (keys + STORE_BATCHES * m) // 2)
+    for b in range(STORE_BATCHES):
+        ctx.store_merge_device(store, wire_t, {k: v[b * m:] for k, v in cols.items()}, m)
+    before = store.query()
+    assert before.rows == keys and before.refused == 0, (before.rows, keys)
+    a2 = torch.zeros(before.arena_used, dtype=torch.uint8, device=dev)
+    ctx.store_compact(store, a2)
+    assert store.query().refused == 0
+    store.arena, store.arena_bytes = a2, a2.numel()
+    del wire_t, cols
+    torch.cuda.empty_cache()
+    return store, keys, n
+
+
+def _order_shape(ctx, drp_amd, torch, store, ch, K, stat):
+    """The catch-up shape K of the store leg: its filters, the fan-out's rows and bounds, and the
+    timings of drp_fanout_device and of drp_encode_device over all rows (the yardstick)."""
+    dev = torch.device("cuda", 0)
+    ts_ = [(100 * f) // K for f in range(K)]
+    flt = [drp_amd.make_filter(change_range=(t + 1, 2**64 - 1)) for t in ts_]
+    counts = [int((ch > t).sum()) for t in ts_]
+    total = sum(counts)
+    rows = _row_tensors(torch, dev, total)
+    rb_t = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+    foff = torch.zeros(total + 1, dtype=torch.int64, device=dev)
+    out = torch.zeros(total * 86, dtype=torch.uint8, device=dev)
+    tf = stat(lambda: ctx.fanout_device(store.arena, store.cols, store.max_keys, flt, rows, total, None, rb_t))
+    te = stat(lambda: ctx.encode_device(rows, store.arena, total, foff, out, out.numel()))
+    rb = rb_t.cpu().numpy()
+    assert [int(rb[f + 1] - rb[f]) for f in range(K)] == counts, "catch-up counts"
+    assert int(foff[total].cpu()) == total * 86, "catch-up bytes"
+    res = {"filters": K, "rows_out": total, "fanout_ms": tf, "encode_ms": te}
+    return res, rows, rb_t, rb, foff, out
+
+
+def order_baseline(ctx, drp_amd, torch, frames, iters):
+    """The yardstick alone (no call of this commit): the parent's library and binding can take it."""
+    store, keys, n = _final_store(ctx, drp_amd, torch, frames)
+    ch = store.cols["change"][:keys].cpu().numpy()
+    stat = _timers(ctx, torch, torch.device("cuda", 0), iters)
+    res = {"bench": "relay_order_baseline", "frames": n, "keys": keys, "iters": iters}
+    for K in ORDER_KS:
+        res[f"K{K}"] = _order_shape(ctx, drp_amd, torch, store, ch, K, stat)[0]
+        print("order baseline", K, res[f"K{K}"], file=sys.stderr, flush=True)
+        torch.cuda.empty_cache()
+    return res
+
+
+def _order_expect(chg, rb, limit=None):
+    """numpy: per segment the stable argsort of the keys (unsigned), cut to `limit` rows."""
+    perm, ob = [], [0]
+    for f in range(len(rb) - 1):
+        lo, hi = int(rb[f]), int(rb[f + 1])
+        o = lo + np.argsort(chg[lo:hi], kind="stable")
+        if limit is not None:
+            o = o[:limit]
+        perm.append(o)
+        ob.append(ob[-1] + len(o))
+    return np.concatenate(perm), ob
+
+
+def order_leg(ctx, drp_amd, torch, frames, iters, parent=None, profile=False):
+    dev = torch.device("cuda", 0)
+    store, keys, n = _final_store(ctx, drp_amd, torch, frames)
+    ch = store.cols["change"][:keys].cpu().numpy()
+    stat = _timers(ctx, torch, dev, iters)
+    if profile:  # (for a kernel trace: K = 64 and the plain call alone, so that a kernel's total is per call)
+        K = ORDER_KS[-1]
+        r, rows, rb_t, rb, foff, out = _order_shape(ctx, drp_amd, torch, store, ch, K, stat)
+        out_rows = _row_tensors(torch, dev, r["rows_out"])
+        ob_t = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+        r["order_ms"] = stat(lambda: ctx.order_device(rows, rb_t, K, r["rows_out"], out_rows, ob_t))
+        r["order_calls"] = iters + 3
+        return {"frames": n, "keys": keys, "iters": iters, f"K{K}": r}
+    os.environ["DRP_ORDER_SKIP"] = "0"  # (read when a ctx opens: ctx2 runs every pass)
+    ctx2 = drp_amd.Ctx(0)
+    del os.environ["DRP_ORDER_SKIP"]
+    stat2 = _timers(ctx2, torch, dev, iters)
+    res = {"frames": n, "keys": keys, "iters": iters, "limit": ORDER_LIMIT}
+    for K in ORDER_KS:
+        r, rows, rb_t, rb, foff, out = _order_shape(ctx, drp_amd, torch, store, ch, K, stat)
+        total = r["rows_out"]
+        out_rows = _row_tensors(torch, dev, total)
+        ob_t = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+        sel = torch.arange(total, dtype=torch.int64, device=dev)
+        osel = torch.zeros(total, dtype=torch.int64, device=dev)
+
+        def checked(c, src, limit=None):
+            """One call with sel_idx = arange against numpy: the permutation, the keys, out_base."""
+            c.order_device(src, rb_t, K, total, out_rows, ob_t, limit=limit, sel_idx_t=sel, out_sel_idx_t=osel)
+            torch.cuda.synchronize()
+            chg = src["change"].cpu().numpy().view(np.uint64)
+            perm, ob = _order_expect(chg, rb, limit)
+            assert [int(v) for v in ob_t.cpu()] == ob, "order out_base"
+            assert np.array_equal(osel[:ob[-1]].cpu().numpy(), perm), "order permutation"
+            assert np.array_equal(out_rows["change"][:ob[-1]].cpu().numpy().view(np.uint64), chg[perm]), "order keys"
+            return ob[-1]
+
+        checked(ctx, rows)
+        r["order_ms"] = stat(lambda: ctx.order_device(rows, rb_t, K, total, out_rows, ob_t))
+        checked(ctx2, rows)
+        r["order_every_pass_ms"] = stat2(lambda: ctx2.order_device(rows, rb_t, K, total, out_rows, ob_t))
+        sent = checked(ctx, rows, ORDER_LIMIT)
+        r["order_limit_ms"] = stat(lambda: ctx.order_device(rows, rb_t, K, total, out_rows, ob_t, limit=ORDER_LIMIT))
+        r["page_rows"] = sent
+        r["encode_page_ms"] = stat(lambda: ctx.encode_device(out_rows, store.arena, sent, foff, out, out.numel()))
+        assert int(foff[sent].cpu()) == sent * 86, "page bytes"
+        # uniform 64-bit keys in the same rows and segments
+        r32 = lambda: torch.randint(0, 2**32, (total,), dtype=torch.int64, device=dev)
+        uni = dict(rows, change=(r32() << 32) | r32())
+        checked(ctx, uni)
+        r["uniform_order_ms"] = stat(lambda: ctx.order_device(uni, rb_t, K, total, out_rows, ob_t))
+        checked(ctx2, uni)
+        r["uniform_order_every_pass_ms"] = stat2(lambda: ctx2.order_device(uni, rb_t, K, total, out_rows, ob_t))
+        r["order_over_encode"] = r["order_ms"]["median"] / r["encode_ms"]["median"]
+        if parent is not None:
+            p = parent[f"K{K}"]
+            assert p["rows_out"] == total
+            r["parent_fanout_ms"], r["parent_encode_ms"] = p["fanout_ms"], p["encode_ms"]
+            r["order_over_parent_encode"] = r["order_ms"]["median"] / p["encode_ms"]["median"]
+        res[f"K{K}"] = r
+        print("order", K, r, file=sys.stderr, flush=True)
+        rows = out_rows = uni = foff = out = sel = osel = None
+        torch.cuda.empty_cache()
+    ctx2.close()
+    return res
+
+
 # ---- digest / reconcile -----------------------------------------------------------------------------
 
 DIGEST_BITS = (8, 12, 16)
@@ -1274,6 +1425,13 @@ def main():
                     help="only the yardsticks and the single-level reconcile (any commit's library with the digest), written here")
     ap.add_argument("--digest-refine-baseline", default=None,
                     help="such a file of the parent commit, read into the refined-digest leg's result")
+    ap.add_argument("--order-out", nargs="?", default=None, const=os.path.join(ROOT, "profiles", "relay", "order_bench.json"),
+                    help="run the ordered catch-up leg alone and write its JSON line here")
+    ap.add_argument("--order-profile", action="store_true",
+                    help="with --order-out: K = 64 and the plain drp_order_device calls alone (for a kernel trace)")
+    ap.add_argument("--order-baseline-out", default=None,
+                    help="only the order leg's yardstick (fan-out and encode over the final store) to this file")
+    ap.add_argument("--order-baseline", default=None, help="such a file of the parent commit, read into the order leg's result")
     a = ap.parse_args()
     if a.digest_only and not a.digest_out:
         ap.error("--digest-only needs --digest-out")
@@ -1292,6 +1450,22 @@ def main():
     torch.cuda.init()
     import _streams as S
     import drp_amd
+    if a.order_baseline_out:
+        with drp_amd.Ctx(0) as ctx:
+            base = order_baseline(ctx, drp_amd, torch, a.frames, a.iters)
+        with open(a.order_baseline_out, "w") as f:
+            f.write(json.dumps(base) + "\n")
+        print(json.dumps(base))
+        return
+    if a.order_out:
+        parent = json.loads(open(a.order_baseline).read()) if a.order_baseline else None
+        assert parent is None or parent["frames"] == a.frames - a.frames % STORE_BATCHES
+        with drp_amd.Ctx(0) as ctx:
+            od = {"bench": "relay_order", "device": order_leg(ctx, drp_amd, torch, a.frames, a.iters, parent, a.order_profile)}
+        with open(a.order_out, "w") as f:
+            f.write(json.dumps(od) + "\n")
+        print(json.dumps(od))
+        return
     if a.digest_refine_baseline_out:
         with drp_amd.Ctx(0) as ctx:
             base = digest_refine_baseline(ctx, drp_amd, torch, a.frames, a.iters)
