@@ -190,6 +190,7 @@ void drp_close(drp_ctx *c) {
   c->keybuf.release();
   c->keytext.release();
   c->fan_rows.release();
+  c->news.release();
   c->fan_tab.release();
   if (c->fan_ev) (void)hipEventDestroy(c->fan_ev);
   if (c->dstats) (void)hipFree(c->dstats);
@@ -1760,6 +1761,7 @@ int drp_decode_stage(drp_ctx *c, const uint8_t *bytes, uint64_t n, drp_carry *ca
   H.flat = bytes;
   H.n = n;
   c->staged.valid = false;
+  c->staged.seq++;
   const int rc = stage_decode(c, H, carry, n_frames, err_frame, err_code, err_detail);
   c->staged.valid = rc == DRP_OK;
   return rc;
@@ -1782,6 +1784,7 @@ int drp_decode_stage_v(drp_ctx *c, const drp_chunk *chunks, uint64_t nchunks, dr
   }
   if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
   c->staged.valid = false;
+  c->staged.seq++;
   HostSrc E;
   const int rc = stage_decode(c, H.n ? H : E, carry, n_frames, err_frame, err_code, err_detail);
   c->staged.valid = rc == DRP_OK;
@@ -1814,6 +1817,7 @@ int drp_decode_batch(drp_ctx *c, const uint8_t *bytes, uint64_t n, drp_carry *ca
   c->dcap = cap;
   c->dfetched = 0;
   c->staged.valid = false;
+  c->staged.seq++;
   int rc = stage_decode(c, H, carry, n_frames, err_frame, err_code, err_detail);
   c->staged.valid = rc == DRP_OK;
   c->dfr = nullptr;

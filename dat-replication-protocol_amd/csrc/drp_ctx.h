@@ -157,6 +157,11 @@ struct drp_ctx {
   drp::PinBuf fan_tab;
   hipEvent_t fan_ev = nullptr;
   drp::DevBuf fan_rows;
+  // drp_store_merge_news_staged's news column (one byte per delivered GPU row) for
+  // drp_fanout_news_staged, and the staged batch (staged.seq) it belongs to
+  drp::DevBuf news;
+  bool news_held = false;
+  uint64_t news_seq = 0;
   // the staged host-batch decode: row 0 is a host-built blob continuation when nf0 == 1; GPU
   // rows follow, each piece's payload_off relative to the batch offset where that piece was
   // staged (pieces: {first GPU row, batch offset}; one piece unless blobs were skipped)
@@ -170,6 +175,7 @@ struct drp_ctx {
     const uint8_t *wire = nullptr;
     uint64_t wire_bytes = 0, base = 0, good = 0;
     bool valid = false;
+    uint64_t seq = 0;  // counts the stage calls: what was derived from an earlier batch is told apart
     uint64_t off0 = 0;
     uint32_t len0 = 0;
     uint8_t ty0 = 0;

@@ -255,7 +255,18 @@ struct StoreMerge {
   // ST_MISC further sums (replaced, unchanged, stale, skipped, dead bytes)
   uint64_t *blk_ins, *blk_bytes, *blk_misc;
   uint64_t nblk;
-  uint64_t *ctl;  // [0] the inserted winners, [1] the bytes needed, [2] the dead bytes
+  uint64_t *ctl;  // [0] the inserted winners, [1] the bytes needed, [2] the dead bytes, [3] the stale winners
+};
+// the report of one merge (include/drp.h "merge report"), written by the rep_* steps behind st_commit.
+// Every output may be null; the two scratch columns are placed by the caller
+struct StoreReport {
+  uint32_t flags;           // DRP_REPORT_*
+  const uint8_t *type;      // the batch's type column (read with DRP_REPORT_KEEP_BLOBS)
+  uint8_t *outcome, *news_type;  // [n]
+  const uint64_t *src_row;  // per winner: its batch row (drp_launch_latest's sel_idx); with outcome / news_type
+  RowOut reply;             // the stale winners' store rows (reply.sel_idx: reply_idx), reply_cap entries
+  uint64_t *n_reply, reply_cap;
+  uint64_t *blk_stale;      // per workgroup of ST_BLK winners: its stale winners (scanned in place); with n_reply
 };
 constexpr uint32_t ST_BLK = 256, ST_WAVES = ST_BLK / 64, ST_MISC = 5;
 constexpr uint32_t ST_GRP = 16;  // lanes that copy one payload, 16 bytes each per step
@@ -419,11 +430,13 @@ hipError_t drp_launch_fanout_latest(const drp::FanParams *P, uint64_t hash_mask,
 hipError_t drp_launch_count_scan(uint64_t *cnt, uint64_t nblk, uint64_t *total, hipStream_t st);
 // drp_store.hip. The table's slots for max_keys (0: out of range); an empty store; steps 2 to 6 of a
 // merge over the winners in M (its state is placed in `scratch`, drp_store_merge_scratch_bytes(n)
-// bytes); a compact into arena2 (scratch: drp_store_compact_scratch_bytes(max_keys)).
+// bytes), then, with a report R (null: none), the rep_* steps; a compact into arena2 (scratch:
+// drp_store_compact_scratch_bytes(max_keys)).
 uint64_t drp_store_nslots(uint64_t max_keys);
 hipError_t drp_launch_store_init(const drp::StoreDev *S, hipStream_t st);
 uint64_t drp_store_merge_scratch_bytes(uint64_t n);
-hipError_t drp_launch_store_merge(const drp::StoreMerge *M, void *scratch, hipStream_t st);
+hipError_t drp_launch_store_merge(const drp::StoreMerge *M, const drp::StoreReport *R, void *scratch, hipStream_t st);
+uint64_t drp_store_blocks(uint64_t n);  // the workgroups of ST_BLK winners a merge of n rows runs (>= 1)
 uint64_t drp_store_compact_scratch_bytes(uint64_t max_keys);
 hipError_t drp_launch_store_compact(const drp::StoreDev *S, uint8_t *arena2, uint64_t arena2_bytes, void *scratch,
                                     hipStream_t st);

@@ -3,7 +3,8 @@
 // the batch last staged (select or latest per key, then the encoder with the staged wire as its
 // heap), drp_fanout_device / drp_fanout_staged (many filters over one pass) and
 // drp_fanout_latest_device / drp_fanout_latest_staged (latest per key under each), and the store
-// (drp_store_*: the latest-per-key step, then the merge into caller-owned device memory), and the
+// (drp_store_*: the latest-per-key step, then the merge into caller-owned device memory; with a
+// report, drp_store_merge_report_device, drp_store_merge_news_staged / drp_fanout_news_staged), and the
 // digest calls (drp_digest_device, drp_digest_diff_device, drp_select_buckets_device, and their second
 // level drp_digest_refine_device, drp_digest_diff_cells_device, drp_select_refined_device), and the ordered
 // catch-up (drp_order_device). The kernels are in drp_select.hip, drp_latest.hip, drp_fanout.hip,
@@ -26,6 +27,11 @@ static bool rows_ok(const drp_frames *frames, const drp_changes *cols, const drp
   return !n || (cols_ok(frames, cols, n) && out_rows->key_off && out_rows->key_len && out_rows->subset_off &&
                 out_rows->subset_len && out_rows->value_off && out_rows->value_len && out_rows->change &&
                 out_rows->from && out_rows->to && out_rows->flags);
+}
+
+static bool src_cols_ok(const drp_change_src *r) {
+  return r->key_off && r->key_len && r->subset_off && r->subset_len && r->value_off && r->value_len && r->change &&
+         r->from && r->to && r->flags;
 }
 
 // drp_filter -> the kernels' filter record and its byte strings (fb: FAN_FBYTES bytes, zeroed by the
@@ -270,14 +276,17 @@ static int fanout_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, cons
   return DRP_OK;
 }
 
-// drp_fanout_staged, or with `latest` drp_fanout_latest_staged (no splice table: blob_row NULL)
+// drp_fanout_staged, or with `latest` drp_fanout_latest_staged (no splice table: blob_row NULL), or
+// with `news` drp_fanout_news_staged: the column drp_store_merge_news_staged kept in the staged type
+// column's place
 static int fanout_staged(drp_ctx *c, const drp_filter *filters, uint32_t nfilters, uint8_t *out, uint64_t cap,
                          uint64_t *out_off, uint64_t *n_selected, uint64_t *blob_row, uint64_t *blob_pos,
-                         uint64_t blob_cap, uint64_t *n_blobs, bool latest) {
+                         uint64_t blob_cap, uint64_t *n_blobs, bool latest, bool news = false) {
   if (!c || !out_off || !n_selected || (!out && cap)) return DRP_E_INVAL;
   if (blob_row ? (!n_blobs || (!blob_pos && blob_cap)) : (n_blobs != nullptr)) return DRP_E_INVAL;
   const auto &S = c->staged;
   if (!S.valid) return DRP_E_INVAL;
+  if (news && !(c->news_held && c->news_seq == S.seq)) return DRP_E_INVAL;
   FanParams P = {};
   if (const int rc = fanout_filters(c, filters, nfilters, P)) return rc;
   const uint32_t K = nfilters;
@@ -300,6 +309,7 @@ static int fanout_staged(drp_ctx *c, const drp_filter *filters, uint32_t nfilter
   if (const int rc = fanout_send_filters(c, P)) return rc;
   // (c->host_tmp's filter table has been copied out: the piece table may pass through it)
   if (const int rc = staged_src(c, P.src, c->scratch.at<uint64_t>(o_piece))) return rc;
+  if (news) P.src.type = c->news.at<uint8_t>(0);
   CHK(launch_fanout_count(c, P, latest));
   uint64_t rb[DRP_FANOUT_MAX + 2];
   CHK(hipMemcpyAsync(rb, drb, (K + 2) * 8, hipMemcpyDeviceToHost, st));
@@ -382,21 +392,25 @@ static bool store_dev(const drp_ctx *c, const drp_store *s, StoreDev &D) {
 // A merge of the rows `src` describes (the caller's, or the staged batch's when `staged`): the
 // latest-per-key step into winner rows in the ctx's scratch, then drp_store.hip's steps over them.
 // Scratch: drp_launch_latest's words, the winners' count, the staged piece table, the winner rows
-// (ten columns of n entries), the merge's state
-static int store_merge(drp_ctx *c, const StoreDev &D, const RowSrc *caller, const drp_filter *filter) {
+// (ten columns of n entries), the merge's state; behind it, only when the report `rep` (NULL: none)
+// asks for them, the winners' source rows and the workgroups' stale counts
+static int store_merge(drp_ctx *c, const StoreDev &D, const RowSrc *caller, const drp_filter *filter,
+                       const drp_merge_report *rep = nullptr) {
   SelectParams P = {};
   SelectBytes fb = {};
   if (const int rc = select_filter(filter, P.f, fb.b)) return rc;
   if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
   const auto &S = c->staged;
   const uint64_t n = caller ? caller->n : S.good, np = caller ? 0 : S.pieces.size();
+  const bool by_row = rep && (rep->outcome || rep->news_type), reply = rep && rep->n_reply;
   const size_t o_cnt = al(drp_latest_scratch_bytes(n)), o_piece = o_cnt + 256, o_rows = o_piece + al(2 * np * 8),
-               col = al(n * 8), o_state = o_rows + 10 * col;
-  if (!c->scratch.ensure(o_state + drp_store_merge_scratch_bytes(n))) return DRP_E_NOMEM;
+               col = al(n * 8), o_state = o_rows + 10 * col, o_src = o_state + drp_store_merge_scratch_bytes(n),
+               o_stale = o_src + (by_row ? col : 0), o_end = o_stale + (reply ? al(drp_store_blocks(n) * 8) : 0);
+  if (!c->scratch.ensure(o_end)) return DRP_E_NOMEM;
   if (caller) P.src = *caller;
   else if (const int rc = staged_src(c, P.src, c->scratch.at<uint64_t>(o_piece))) return rc;
   const drp_change_src rows = carve_rows(c->scratch, o_rows, col);
-  P.out = row_out(&rows, nullptr);
+  P.out = row_out(&rows, by_row ? c->scratch.at<uint64_t>(o_src) : nullptr);
   P.n_selected = c->scratch.at<uint64_t>(o_cnt);
   CHK(drp_launch_latest(&P, &fb, c->latest_hash_mask, c->scratch.p, c->st));
   StoreMerge M = {};
@@ -406,8 +420,28 @@ static int store_merge(drp_ctx *c, const StoreDev &D, const RowSrc *caller, cons
   M.w = rows;
   M.nw = P.n_selected;
   M.n = n;
-  CHK(drp_launch_store_merge(&M, c->scratch.at<char>(o_state), c->st));
+  StoreReport R = {};
+  if (by_row || reply) {
+    R.flags = rep->flags;
+    R.type = P.src.type;
+    R.outcome = rep->outcome;
+    R.news_type = rep->news_type;
+    R.src_row = P.out.sel_idx;
+    if (rep->reply_rows && rep->reply_cap) R.reply = row_out(rep->reply_rows, rep->reply_idx);
+    R.n_reply = rep->n_reply;
+    R.reply_cap = rep->reply_rows ? rep->reply_cap : 0;
+    R.blk_stale = reply ? c->scratch.at<uint64_t>(o_stale) : nullptr;
+  }
+  CHK(drp_launch_store_merge(&M, (by_row || reply) ? &R : nullptr, c->scratch.at<char>(o_state), c->st));
   return DRP_OK;
+}
+
+// the report's own DRP_E_INVAL cases (type: the batch's type column)
+static bool report_ok(const drp_merge_report *rep, const uint8_t *type) {
+  if (!rep) return true;
+  if (rep->flags & ~(uint32_t)DRP_REPORT_KEEP_BLOBS) return false;
+  if (rep->reply_rows && (!rep->n_reply || (rep->reply_cap && !src_cols_ok(rep->reply_rows)))) return false;
+  return !(rep->news_type && rep->news_type == type);
 }
 
 static int store_query(drp_ctx *c, const drp_store_info *dev, drp_store_info *host) {
@@ -529,11 +563,6 @@ int drp_select_refined_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes,
 }
 
 // ---- ordered catch-up ---------------------------------------------------------------------------
-static bool src_cols_ok(const drp_change_src *r) {
-  return r->key_off && r->key_len && r->subset_off && r->subset_len && r->value_off && r->value_len && r->change &&
-         r->from && r->to && r->flags;
-}
-
 int drp_order_device(drp_ctx *c, const drp_change_src *rows, const uint64_t *row_base, uint32_t nseg,
                      uint64_t rows_cap, const uint64_t *limit, uint32_t flags, const drp_change_src *out_rows,
                      const uint64_t *sel_idx, uint64_t *out_sel_idx, uint64_t *out_base) {
@@ -585,15 +614,55 @@ int drp_store_merge_device(drp_ctx *c, const drp_store *s, const uint8_t *bytes,
   return store_merge(c, D, &R, filter);
 }
 
-int drp_store_merge_staged(drp_ctx *c, const drp_store *s, const drp_filter *filter, drp_store_info *info_host) {
+int drp_store_merge_report_device(drp_ctx *c, const drp_store *s, const uint8_t *bytes, uint64_t nbytes,
+                                  const drp_frames *frames, const drp_changes *cols, uint64_t n,
+                                  const drp_filter *filter, const drp_merge_report *report) {
+  StoreDev D = {};
+  if (!c || !s || !frames || !cols || (!bytes && nbytes) || !store_dev(c, s, D)) return DRP_E_INVAL;
+  if (!cols_ok(frames, cols, n) || !report_ok(report, frames->type)) return DRP_E_INVAL;
+  const RowSrc R = caller_src(bytes, nbytes, frames, cols, n);
+  return store_merge(c, D, &R, filter, report);
+}
+
+// drp_store_merge_staged, or with `news` drp_store_merge_news_staged: the merge's news column, blobs
+// kept, into c->news (a buffer of its own: the scratch is the next call's)
+static int store_merge_staged(drp_ctx *c, const drp_store *s, const drp_filter *filter, drp_store_info *info_host,
+                              bool news) {
   StoreDev D = {};
   if (!c || !s || !store_dev(c, s, D)) return DRP_E_INVAL;
   if (!c->staged.valid) return DRP_E_INVAL;
-  if (const int rc = store_merge(c, D, nullptr, filter)) return rc;
+  drp_merge_report rep = {};
+  if (news) {
+    c->news_held = false;
+    if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+    if (!c->news.ensure(c->staged.good + 16)) return DRP_E_NOMEM;
+    rep.flags = DRP_REPORT_KEEP_BLOBS;
+    rep.news_type = c->news.at<uint8_t>(0);
+  }
+  if (const int rc = store_merge(c, D, nullptr, filter, news ? &rep : nullptr)) return rc;
   drp_store_info I;
   if (const int rc = store_query(c, D.info, &I)) return rc;
+  if (news) {  // (held after a refusal too: nothing is news then, and the blobs are still listed)
+    c->news_held = true;
+    c->news_seq = c->staged.seq;
+  }
   if (info_host) *info_host = I;
   return I.refused ? DRP_E_CAPACITY : DRP_OK;
+}
+
+int drp_store_merge_staged(drp_ctx *c, const drp_store *s, const drp_filter *filter, drp_store_info *info_host) {
+  return store_merge_staged(c, s, filter, info_host, false);
+}
+
+int drp_store_merge_news_staged(drp_ctx *c, const drp_store *s, const drp_filter *filter, drp_store_info *info_host) {
+  return store_merge_staged(c, s, filter, info_host, true);
+}
+
+int drp_fanout_news_staged(drp_ctx *c, const drp_filter *filters, uint32_t nfilters, uint8_t *out, uint64_t cap,
+                           uint64_t *out_off, uint64_t *n_selected, uint64_t *blob_row, uint64_t *blob_pos,
+                           uint64_t blob_cap, uint64_t *n_blobs) {
+  return fanout_staged(c, filters, nfilters, out, cap, out_off, n_selected, blob_row, blob_pos, blob_cap, n_blobs,
+                       false, true);
 }
 
 int drp_store_compact(drp_ctx *c, const drp_store *s, uint8_t *arena2, uint64_t arena2_bytes) {

@@ -31,6 +31,7 @@
 //               per step: a 4 KB value takes 16, a 40-byte payload one, and four winners share a
 //               wave), the allocation's tail zeroed; the group's first lane writes the columns.
 //   st_commit   rows, arena_used, arena_dead, merges.
+// With a report (include/drp.h "merge report") the rep_* steps follow: see "report" below.
 // The compact is the same shape: the live allocations' sizes and their prefix, the scan, the verdict
 // with the commit (nothing later reads the old totals), the copy.
 #include "drp_select.h"  // (wire_has, bytes_eq; drp_device.h: xxh, ld_agent, the wave scans)
@@ -292,6 +293,87 @@ __global__ void st_commit_kernel(const StoreMerge M) {
   I->merges += 1;
 }
 
+// ---- report -----------------------------------------------------------------------------------
+// The steps behind st_commit that say which rows the counts of the record were (include/drp.h "merge
+// report"). By then the verdict is in the record and where[i] of a stale winner is its store row.
+//   rep_clear  the batch's n rows, REP_ROWS per lane: outcome zeroed, news_type zeroed or, with
+//              DRP_REPORT_KEEP_BLOBS, the blob rows' type byte. A kernel of its own before rep_mark:
+//              the winners' bytes lie anywhere among these, and two kernels order the two writes.
+//   rep_mark   one winner per lane: outcome[row] = its code, news_type[row] = DRP_TYPE_CHANGE for an
+//              inserted or replaced one unless the merge was refused. Winners have distinct rows.
+//              The workgroup's stale count leaves blk_misc here (st_verdict has read it) for the scan.
+//   scan       drp_select.hip's, over the workgroups' stale counts.
+//   rep_reply  the stale winners: place = the scanned count + the rank among the workgroup's stale
+//              winners (ballots and the waves' counts, as st_lookup ranks the inserted); if the total
+//              fits reply_cap, the store row's ten columns as row_load / row_store write them.
+constexpr uint32_t REP_ROWS = 16;
+
+// the bytes of w whose low six bits are DRP_TYPE_BLOB, the others 0
+__device__ __forceinline__ uint32_t rep_blobs(uint32_t w) {
+  const uint32_t y = (w & 0x3F3F3F3Fu) ^ (0x01010101u * DRP_TYPE_BLOB);  // (a byte is 0 where it matches)
+  const uint32_t nz = ((y + 0x7F7F7F7Fu) | y) & 0x80808080u;             // (y's bytes are < 0x40: no carry leaves one)
+  return w & (((nz ^ 0x80808080u) >> 7) * 0xFFu);
+}
+
+// dst[0, n) = 0 or the blob bytes of src[0, n): chunk t of REP_ROWS bytes from dst's first 16-byte
+// boundary on with one 16-byte store (src is read where it lies: unaligned), the bytes before that
+// boundary and behind the last whole chunk one at a time by lane `nchunk`. Nothing at or beyond n.
+__device__ __forceinline__ void rep_fill(uint8_t *dst, const uint8_t *src, uint64_t n, uint64_t t) {
+  const uint64_t head = umin64(n, (16 - ((uintptr_t)dst & 15)) & 15), nchunk = (n - head) / REP_ROWS;
+  if (t < nchunk) {
+    const uint64_t at = head + t * REP_ROWS;
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (src) {
+      __builtin_memcpy(&v, src + at, 16);
+      v = make_uint4(rep_blobs(v.x), rep_blobs(v.y), rep_blobs(v.z), rep_blobs(v.w));
+    }
+    *reinterpret_cast<uint4 *>(dst + at) = v;
+  } else if (t == nchunk) {
+    const uint64_t tail = head + nchunk * REP_ROWS;  // (n - tail < REP_ROWS)
+    for (uint64_t k = 0; k < head; k++) dst[k] = src && (src[k] & 0x3F) == DRP_TYPE_BLOB ? src[k] : 0;
+    for (uint64_t k = tail; k < n; k++) dst[k] = src && (src[k] & 0x3F) == DRP_TYPE_BLOB ? src[k] : 0;
+  }
+}
+
+__global__ __launch_bounds__(ST_BLK) void rep_clear_kernel(const StoreReport R, uint64_t n) {
+  const uint64_t t = (uint64_t)blockIdx.x * ST_BLK + threadIdx.x;
+  if (R.outcome) rep_fill(R.outcome, nullptr, n, t);
+  if (R.news_type) rep_fill(R.news_type, (R.flags & DRP_REPORT_KEEP_BLOBS) ? R.type : nullptr, n, t);
+}
+
+__global__ __launch_bounds__(ST_BLK) void rep_mark_kernel(const StoreMerge M, const StoreReport R) {
+  const uint64_t i = (uint64_t)blockIdx.x * ST_BLK + threadIdx.x;
+  if (threadIdx.x == 0 && R.blk_stale) R.blk_stale[blockIdx.x] = M.blk_misc[(uint64_t)blockIdx.x * ST_MISC + 2];
+  if (i >= *M.nw || i >= M.n || !R.src_row) return;
+  const uint64_t r = R.src_row[i];
+  if (r >= M.n) return;  // (not reached: a winner is a row of the batch)
+  const uint32_t code = M.meta[i] & 0xFF;
+  if (R.outcome) R.outcome[r] = (uint8_t)code;
+  if (R.news_type && (code == ST_INSERT || code == ST_REPLACE) && !M.s.info->refused) R.news_type[r] = DRP_TYPE_CHANGE;
+}
+
+__global__ __launch_bounds__(ST_BLK) void rep_reply_kernel(const StoreMerge M, const StoreReport R) {
+  __shared__ uint32_t wcnt[ST_WAVES];
+  const StoreDev &S = M.s;
+  const uint64_t i = (uint64_t)blockIdx.x * ST_BLK + threadIdx.x;
+  const bool stale = i < *M.nw && i < M.n && (M.meta[i] & 0xFF) == ST_STALE;
+  const uint32_t wv = threadIdx.x >> 6, lane = lane_id();
+  const uint64_t bs = __ballot(stale);
+  if (lane == 0) wcnt[wv] = (uint32_t)__popcll(bs);
+  __syncthreads();
+  const uint64_t total = M.ctl[3];
+  if (i == 0) *R.n_reply = total;
+  if (!stale || total > R.reply_cap) return;
+  uint64_t j = R.blk_stale[blockIdx.x] + (uint32_t)__popcll(bs & ((1ull << lane) - 1ull));
+  for (uint32_t k = 0; k < wv; k++) j += wcnt[k];
+  const uint64_t r = M.where[i];
+  if (j >= R.reply_cap || r >= S.max_keys) return;  // (not reached: j < total, and a stale winner was found in a row)
+  RowSrc V = {};  // the store's view (offsets absolute into the arena: no piece shift)
+  V.payload_off = S.payload_off;
+  V.cols = S.cols;
+  row_store(R.reply, j, row_load(V, r), r);
+}
+
 // ---- compact ----------------------------------------------------------------------------------
 struct StoreCompact {
   StoreDev s;
@@ -367,7 +449,10 @@ extern "C" uint64_t drp_store_merge_scratch_bytes(uint64_t n) {
   return 3 * st_al(m * 8) + 2 * st_al(m * 4) + 2 * st_al(nblk * 8) + st_al(nblk * ST_MISC * 8) + 256;
 }
 
-extern "C" hipError_t drp_launch_store_merge(const StoreMerge *Mp, void *scratch, hipStream_t st) {
+extern "C" uint64_t drp_store_blocks(uint64_t n) { return st_nblk(n); }
+
+extern "C" hipError_t drp_launch_store_merge(const StoreMerge *Mp, const StoreReport *R, void *scratch,
+                                             hipStream_t st) {
   StoreMerge M = *Mp;
   const uint64_t nblk = st_nblk(M.n), m = nblk * ST_BLK;
   if (nblk >= (1ull << 31) / ST_GRP) return hipErrorInvalidValue;
@@ -392,6 +477,19 @@ extern "C" hipError_t drp_launch_store_merge(const StoreMerge *Mp, void *scratch
   hipLaunchKernelGGL(st_write_kernel, dim3((uint32_t)(nblk * ST_GRP)), blk, 0, st, M);
   hipLaunchKernelGGL(st_commit_kernel, dim3(1), dim3(1), 0, st, M);
   drp_dbg_mark("store_merge", st);
+  if (R) {
+    const bool rows = R->src_row && (R->outcome || R->news_type), reply = R->n_reply && R->blk_stale;
+    if (rows && M.n) {
+      const uint64_t lanes = M.n / REP_ROWS + 1;  // (the chunks, and the lane behind them for the ends)
+      hipLaunchKernelGGL(rep_clear_kernel, dim3((uint32_t)((lanes + ST_BLK - 1) / ST_BLK)), blk, 0, st, *R, M.n);
+    }
+    if (rows || reply) hipLaunchKernelGGL(rep_mark_kernel, grid, blk, 0, st, M, *R);
+    if (reply) {
+      if (const hipError_t e = drp_launch_count_scan(R->blk_stale, nblk, M.ctl + 3, st)) return e;
+      hipLaunchKernelGGL(rep_reply_kernel, grid, blk, 0, st, M, *R);
+    }
+    drp_dbg_mark("store_report", st);
+  }
   return hipGetLastError();
 }
 

@@ -34,6 +34,7 @@ EXPORTS = [
     "drp_fanout_latest_device", "drp_fanout_latest_staged", "drp_set_fanout_latest_pass",
     "drp_store_table_bytes", "drp_store_init", "drp_store_merge_device", "drp_store_merge_staged",
     "drp_store_compact", "drp_store_query", "drp_order_device",
+    "drp_store_merge_report_device", "drp_store_merge_news_staged", "drp_fanout_news_staged",
     "drp_digest_device", "drp_digest_diff_device", "drp_select_buckets_device",
     "drp_digest_refine_device", "drp_digest_diff_cells_device", "drp_select_refined_device",
     "drp_comm_id", "drp_comm_init_rank", "drp_comm_init_all", "drp_comm_destroy",
@@ -49,6 +50,8 @@ FANOUT_MAX = 64
 DIGEST_MAX_BITS = 16
 DIGEST_MAX_SUB_BITS = 8
 ORDER_KEEP_TIES = 1
+MERGE_NONE, MERGE_INSERTED, MERGE_REPLACED, MERGE_UNCHANGED, MERGE_STALE, MERGE_SKIPPED = 0, 1, 2, 3, 4, 5
+REPORT_KEEP_BLOBS = 1
 ORDER_TILE, ORDER_SCAN = 4096, 1024  # csrc/drp_kernels.h ORD_TILE, ORD_SCAN: pairs per sort workgroup, counts per scan block
 DIGEST_LDS_BITS = 10  # csrc/drp_kernels.h DIG_LDS_BITS: up to here dig_cells sums in LDS, above in global memory
 COMM_ID_BYTES = 128
@@ -154,6 +157,12 @@ class StoreDesc(C.Structure):
                 ("table", P), ("info", P), ("reserved", U64)]
 
 
+class MergeReport(C.Structure):
+    """drp_merge_report: a host struct of device pointers (reply_rows: a host pointer to a ChangeSrc)."""
+    _fields_ = [("flags", U32), ("reserved", U32), ("outcome", P), ("news_type", P), ("reply_rows", C.POINTER(ChangeSrc)),
+                ("reply_idx", P), ("n_reply", P), ("reply_cap", U64), ("reserved2", U64)]
+
+
 class DigestCell(C.Structure):
     """drp_digest_cell: the rows of one bucket and the sum of their fingerprints (mod 2^64)."""
     _fields_ = [("count", U64), ("sum", U64)]
@@ -226,6 +235,9 @@ def lib():
         L.drp_store_merge_device.argtypes = [P, C.POINTER(StoreDesc), P, U64, C.POINTER(Frames), C.POINTER(Changes),
                                              U64, C.POINTER(Filter)]
         L.drp_store_merge_staged.argtypes = [P, C.POINTER(StoreDesc), C.POINTER(Filter), C.POINTER(StoreInfo)]
+        L.drp_store_merge_report_device.argtypes = L.drp_store_merge_device.argtypes + [C.POINTER(MergeReport)]
+        L.drp_store_merge_news_staged.argtypes = L.drp_store_merge_staged.argtypes
+        L.drp_fanout_news_staged.argtypes = L.drp_fanout_staged.argtypes
         L.drp_store_compact.argtypes = [P, C.POINTER(StoreDesc), P, U64]
         L.drp_store_query.argtypes = [P, C.POINTER(StoreDesc), C.POINTER(StoreInfo)]
         L.drp_order_device.argtypes = [P, C.POINTER(ChangeSrc), P, U32, U64, P, U32, C.POINTER(ChangeSrc), P, P, P]
@@ -261,6 +273,7 @@ def lib():
                   "drp_set_latest_hash_mask", "drp_fanout_latest_device", "drp_fanout_latest_staged",
                   "drp_set_fanout_latest_pass", "drp_store_init", "drp_store_merge_device", "drp_store_merge_staged",
                   "drp_store_compact", "drp_store_query", "drp_order_device", "drp_digest_device", "drp_digest_diff_device",
+                  "drp_store_merge_report_device", "drp_store_merge_news_staged", "drp_fanout_news_staged",
                   "drp_select_buckets_device", "drp_digest_refine_device", "drp_digest_diff_cells_device",
                   "drp_select_refined_device", "drp_stream_stats_from_results", "drp_device", "drp_comm_id", "drp_comm_init_rank",
                   "drp_comm_init_all", "drp_index_allgather", "drp_index_allgather_multi",
@@ -600,7 +613,7 @@ class Ctx:
         _chk("drp_fanout_device", rc)
         self.order_torch_after(wire_t)
 
-    def fanout_staged(self, filters, cap=None, splice=False, out=None, blob_cap=None):
+    def fanout_staged(self, filters, cap=None, splice=False, out=None, blob_cap=None, _fn="drp_fanout_staged"):
         """drp_fanout_staged over the batch last staged (decode_staged), filters a list of
         make_filter results (None: keep every Change): returns ([wire bytes per filter],
         [n_selected per filter], splice_or_None). cap=None: len(filters) times the staged batch's
@@ -623,10 +636,10 @@ class Ctx:
             brow = np.full(max(blob_cap, 1), 0x5555555555555555, np.uint64)
             bpos = np.full(max(K * blob_cap, 1), 0x5555555555555555, np.uint64)
             nbl = np.zeros(1, np.uint64)
-        rc = self.L.drp_fanout_staged(self.h, filter_array(filters), K, _p(buf), cap, _p(out_off), _p(nsel),
-                                      _p(brow), _p(bpos), blob_cap or 0, _p(nbl))
+        rc = getattr(self.L, _fn)(self.h, filter_array(filters), K, _p(buf), cap, _p(out_off), _p(nsel),
+                                  _p(brow), _p(bpos), blob_cap or 0, _p(nbl))
         if rc != DRP_OK:
-            e = DrpError("drp_fanout_staged", rc)
+            e = DrpError(_fn, rc)
             e.written = int(out_off[K]) if K <= FANOUT_MAX else 0
             e.n_selected = [int(v) for v in nsel[:K]]
             raise e
@@ -703,18 +716,53 @@ class Ctx:
         _chk("drp_store_merge_device", rc)
         self.order_torch_after(wire_t)
 
-    def store_merge_staged(self, store, filter=None):
+    def store_merge_staged(self, store, filter=None, _fn="drp_store_merge_staged"):
         """drp_store_merge_staged over the batch last staged (decode_staged): returns the StoreInfo
         record; a refused merge raises DrpError(DRP_E_CAPACITY) with .info = the record."""
         info = StoreInfo()
         self.order_after_torch(store.arena)
-        rc = self.L.drp_store_merge_staged(self.h, C.byref(store.desc()), C.byref(filter) if filter is not None else None,
-                                           C.byref(info))
+        rc = getattr(self.L, _fn)(self.h, C.byref(store.desc()), C.byref(filter) if filter is not None else None,
+                                  C.byref(info))
         if rc != DRP_OK:
-            e = DrpError("drp_store_merge_staged", rc)
+            e = DrpError(_fn, rc)
             e.info = info
             raise e
         return info
+
+    # ---- merge report: per-row outcomes, the news view and the stale reply -----------------------
+    def store_merge_report_device(self, store, wire_t, cols, n, filter=None, outcome_t=None, news_type_t=None,
+                                  reply_rows=None, reply_idx_t=None, n_reply_t=None, reply_cap=0, flags=0,
+                                  report=True):
+        """drp_store_merge_report_device: store_merge_device's arguments and merge, and the report's
+        outputs (all optional, uint8 / int64 CUDA tensors): outcome_t and news_type_t of n entries,
+        reply_rows a dict of drp_change_src columns and reply_idx_t of reply_cap entries, n_reply_t of
+        one. flags: REPORT_KEEP_BLOBS. report=False passes a NULL report. Asynchronous."""
+        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
+        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
+                     tp(cols["flags"]), None)
+        rep = None
+        if report:
+            dst = ChangeSrc(*[tp(reply_rows.get(k)) for k in SRC_COLS]) if reply_rows is not None else None
+            rep = MergeReport(flags, 0, tp(outcome_t), tp(news_type_t), C.pointer(dst) if dst is not None else None,
+                              tp(reply_idx_t), tp(n_reply_t), reply_cap, 0)
+        self.order_after_torch(wire_t)
+        rc = self.L.drp_store_merge_report_device(self.h, C.byref(store.desc()), tp(wire_t), wire_t.numel(),
+                                                  C.byref(fr), C.byref(co), n,
+                                                  C.byref(filter) if filter is not None else None,
+                                                  C.byref(rep) if rep is not None else None)
+        _chk("drp_store_merge_report_device", rc)
+        self.order_torch_after(wire_t)
+
+    def store_merge_news_staged(self, store, filter=None):
+        """drp_store_merge_news_staged: store_merge_staged's arguments, result and errors; the ctx
+        keeps the merge's news column (blobs kept) for fanout_news_staged."""
+        return self.store_merge_staged(store, filter, _fn="drp_store_merge_news_staged")
+
+    def fanout_news_staged(self, filters, cap=None, splice=False, out=None, blob_cap=None):
+        """drp_fanout_news_staged: fanout_staged's arguments, results and errors, over the Changes of
+        the staged batch that the last store_merge_news_staged found to be news (and its blobs)."""
+        return self.fanout_staged(filters, cap, splice, out, blob_cap, _fn="drp_fanout_news_staged")
 
     def store_compact(self, store, arena2_t):
         """drp_store_compact into arena2_t (a uint8 CUDA tensor). Asynchronous; the caller checks
@@ -884,6 +932,74 @@ class Store:
 
     def query(self):
         return self.ctx.store_query(self)
+
+    def merge_report(self, wire_t, cols, n, filter=None, keep_blobs=False, reply=False):
+        """merge_device with the full report: {"outcome", "news_type"} (uint8 tensors of n entries:
+        MERGE_* per batch row, and the type column under which the batch holds only its news), and,
+        with reply=True (else None), {"reply_rows", "reply_idx", "n_reply"}: the store's rows for the
+        batch's stale winners as drp_change_src columns over the arena, their store rows, and the
+        count as an int64 tensor of one element (reply_cap = n). Asynchronous."""
+        import torch
+        dev = self.arena.device
+        z = lambda k, dt: torch.zeros(max(int(k), 1), dtype=dt, device=dev)
+        r = {"outcome": z(n, torch.uint8), "news_type": z(n, torch.uint8), "reply_rows": None, "reply_idx": None,
+             "n_reply": None}
+        if reply:
+            r["reply_rows"] = {k: z(n, torch.int32 if k.endswith("_len") else torch.uint8 if k == "flags" else
+                                    torch.int64) for k in SRC_COLS}
+            r["reply_idx"], r["n_reply"] = z(n, torch.int64), z(1, torch.int64)
+        self.ctx.store_merge_report_device(self, wire_t, cols, n, filter, r["outcome"], r["news_type"],
+                                           r["reply_rows"], r["reply_idx"], r["n_reply"], n if reply else 0,
+                                           REPORT_KEEP_BLOBS if keep_blobs else 0)
+        r["outcome"], r["news_type"] = r["outcome"][:n], r["news_type"][:n]
+        return r
+
+    def _encode_outputs(self, rows, base, heap_t, K):
+        """One encode_device of fan-out rows (bounds base, K outputs) over heap_t: [bytes per output]."""
+        import torch
+        rb = [int(v) for v in base.cpu()]  # (torch's stream was ordered after the ctx's)
+        total = rb[K]
+        if total == 0:
+            return [b""] * K
+        src = ChangeSrc(*[C.c_void_p(rows[k].data_ptr()) for k in SRC_COLS])
+        need = U64()
+        _chk("drp_encode_size", self.ctx.L.drp_encode_size(self.ctx.h, C.byref(src), total, C.byref(need)))
+        dev = self.arena.device
+        foff = torch.zeros(total + 1, dtype=torch.int64, device=dev)
+        out = torch.zeros(max(int(need.value), 1), dtype=torch.uint8, device=dev)
+        self.ctx.encode_device(rows, heap_t, total, foff, out, int(need.value))
+        fo, o = foff.cpu().numpy(), out.cpu().numpy()
+        return [o[int(fo[rb[f]]):int(fo[rb[f + 1]])].tobytes() for f in range(K)]
+
+    def relay_news(self, wire_t, cols, n, filters, merge_filter=None):
+        """The hub step: one merge with a report, one fanout_device over the batch with the report's
+        news_type as its type column, one encode_device with the wire as the heap. Returns (info,
+        [wire bytes per filter]): output f holds the batch's Changes that changed the store and pass
+        filters[f], in batch-row order."""
+        import torch
+        dev = self.arena.device
+        news = torch.zeros(max(int(n), 1), dtype=torch.uint8, device=dev)
+        self.ctx.store_merge_report_device(self, wire_t, cols, n, merge_filter, None, news, flags=REPORT_KEEP_BLOBS)
+        K = len(filters)
+        cap = K * int(n)
+        rows = {k: torch.zeros(max(cap, 1), dtype=(torch.int32 if k.endswith("_len") else
+                                                   torch.uint8 if k == "flags" else torch.int64), device=dev)
+                for k in SRC_COLS}
+        base = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+        view = dict(cols)
+        view["type"] = news
+        self.ctx.fanout_device(wire_t, view, n, filters, rows, cap, None, base)
+        outs = self._encode_outputs(rows, base, wire_t, K)
+        return self.query(), outs
+
+    def reply_bytes(self, report):
+        """The bytes to send back to the peer whose batch merge_report(..., reply=True) merged: one
+        encode_device of the reply rows with the arena as the heap."""
+        if report.get("n_reply") is None:
+            raise ValueError("the report holds no reply (merge_report(..., reply=True))")
+        import torch
+        base = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.arena.device), report["n_reply"][:1]])
+        return self._encode_outputs(report["reply_rows"], base, self._view(), 1)[0]
 
     def compact(self, arena2_bytes=None):
         """Compact into a fresh arena of arena2_bytes (default: the live bytes); returns the record.

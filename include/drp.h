@@ -33,6 +33,10 @@
  *       -> no reference counterpart: the latest Change per (subset, key) over every batch merged so
  *          far, resident in caller-owned device memory in the layout of a decoded batch, so the
  *          relay calls above run over it unchanged (a hub answering "what changed since T?").
+ *   drp_store_merge_report_device / drp_store_merge_news_staged / drp_fanout_news_staged
+ *       -> no reference counterpart: that merge saying per batch row what became of it, as a type
+ *          column under which the batch holds exactly the Changes that changed the store (a relay
+ *          forwarding only what was news to it), and the store's rows a stale sender lacks.
  *   drp_order_device
  *       -> no reference counterpart: the rows of every fan-out output in ascending `change` (schema
  *          messages/schema.proto:1-8), cut to a per-peer limit (a catch-up a peer can resume or page).
@@ -610,6 +614,77 @@ int drp_store_compact(drp_ctx *ctx, const drp_store *s, uint8_t *arena2, uint64_
 int drp_store_query(drp_ctx *ctx, const drp_store *s, drp_store_info *info_host);
 /* drp_set_latest_hash_mask applies to the store's table as well (test hook): a store must see one
  * mask from drp_store_init on, for its whole life. */
+
+/* ---- merge report: per-row outcomes, the news view and the stale reply -------------------- */
+/* A merge counts its outcomes in the record; a hub that passes a batch on needs to know which rows
+ * they were. "Forward only what was news to me" is the rule of any relay or gossip topology: relaying
+ * the whole batch sends round again what two upstream peers, or an echo, deliver twice. And a `stale`
+ * winner says the sender lacks a row the hub holds. The report exposes both in a form every relay call
+ * above takes unchanged. No reference counterpart (the reference has no relay); the fields read are
+ * those of messages/schema.proto:1-8.
+ *   The merge itself is exactly drp_store_merge_device's: the same winners, outcomes and all-or-nothing
+ * verdict, the same store bytes and info record; a NULL report, or one whose outputs are all NULL, is
+ * that call. Asynchronous on drp_stream(ctx), no host synchronisation inside.
+ *   outcome[r], for every batch row r in [0, n): DRP_MERGE_NONE if r is not one of the winners
+ * drp_latest_device returns for these arguments, otherwise that winner's outcome as the store section
+ * defines it. After a refused merge the classification is still written (INSERTED and REPLACED then
+ * mean "would have been"); the caller reads `refused` from the record.
+ *   news_type[r], a replacement for frames->type: DRP_TYPE_CHANGE where the merge was not refused and
+ * outcome[r] is INSERTED or REPLACED; with DRP_REPORT_KEEP_BLOBS a row with (type[r] & 0x3F) ==
+ * DRP_TYPE_BLOB keeps type[r] as it is (DRP_FRAME_PARTIAL with it; after a refusal too); 0 everywhere
+ * else. So (bytes, nbytes, {payload_off, payload_len, news_type}, cols, n) is a decoded batch holding
+ * exactly the Changes that changed the store: drp_select_device, drp_fanout_device with its splice
+ * table, drp_latest_device, drp_order_device behind them and drp_digest_device run over it unchanged,
+ * and not one of the other twelve columns is copied. The news rows number inserted + replaced of the
+ * record. news_type == frames->type (aliasing) is DRP_E_INVAL.
+ *   Reply: the stale winners in batch-row order; for each the store's row of that identity (the one
+ * whose greater `change` beat it), written as drp_select_device writes that row over the store's view:
+ * offsets absolute into s->arena (payload_off, + key_len, + key_len + subset_len), flags masked to
+ * DRP_F_SUBSET | DRP_F_VALUE; reply_idx[j] is the store row. *n_reply always carries the true count;
+ * if it exceeds reply_cap nothing is written to the arrays (drp_fanout_device's rows_cap convention),
+ * otherwise entries at or beyond it are left untouched. drp_encode_device(ctx, reply_rows, s->arena,
+ * s->arena_bytes, *n_reply, ...) gives the bytes to send back to that peer. The reply is written
+ * after a refused merge too (a stale row is stale either way); its offsets hold until the next
+ * drp_store_compact.
+ *   Entries of outcome and news_type at or beyond n are left untouched.
+ *   DRP_E_INVAL: drp_store_merge_device's cases; unknown flag bits; reply_rows without n_reply; with
+ * reply_cap > 0 a NULL array in reply_rows; the aliasing above. Scratch, on top of the merge's and
+ * only when asked for: 8 bytes per batch row (the winners' source rows) for outcome or news_type, 8
+ * bytes per 256 rows (the stale scan) for the reply. */
+#define DRP_MERGE_NONE 0 /* the row is no winner: no candidate, or beaten inside the batch */
+#define DRP_MERGE_INSERTED 1
+#define DRP_MERGE_REPLACED 2
+#define DRP_MERGE_UNCHANGED 3
+#define DRP_MERGE_STALE 4
+#define DRP_MERGE_SKIPPED 5
+#define DRP_REPORT_KEEP_BLOBS 0x01
+
+typedef struct drp_merge_report { /* HOST struct of DEVICE pointers, read before the call returns; 64 bytes */
+  uint32_t flags, reserved;
+  uint8_t *outcome;                 /* n entries, may be NULL */
+  uint8_t *news_type;               /* n entries, may be NULL */
+  const drp_change_src *reply_rows; /* HOST pointer to a struct of writable device arrays, reply_cap entries each; NULL: no reply */
+  uint64_t *reply_idx;              /* reply_cap entries, may be NULL */
+  uint64_t *n_reply;                /* one entry; required with reply_rows */
+  uint64_t reply_cap;
+  uint64_t reserved2;
+} drp_merge_report;
+
+int drp_store_merge_report_device(drp_ctx *ctx, const drp_store *s, const uint8_t *bytes, uint64_t nbytes,
+                                  const drp_frames *frames, const drp_changes *cols, uint64_t n,
+                                  const drp_filter *filter, const drp_merge_report *report);
+/* drp_store_merge_staged (the same rows, return codes and store) that also keeps the merge's news
+ * column, with DRP_REPORT_KEEP_BLOBS, in a device buffer of the ctx for the call below. */
+int drp_store_merge_news_staged(drp_ctx *ctx, const drp_store *s, const drp_filter *filter, drp_store_info *info_host);
+/* drp_fanout_staged with that column in the staged type column's place: the same outputs, splice
+ * numbering and DRP_E_CAPACITY contract (it can be called again with a larger out; a merge could not
+ * be repeated to retry, the second time nothing would be news), the same bytes in every
+ * drp_set_blob_skip mode. After a refused merge every output is empty and the blobs are still listed.
+ * DRP_E_INVAL: no news is held (before any drp_store_merge_news_staged, after anything that ends the
+ * staged batch for drp_fanout_staged, after a new stage); drp_fanout_staged's cases. */
+int drp_fanout_news_staged(drp_ctx *ctx, const drp_filter *filters, uint32_t nfilters, uint8_t *out, uint64_t cap,
+                           uint64_t *out_off, uint64_t *n_selected, uint64_t *blob_row, uint64_t *blob_pos,
+                           uint64_t blob_cap, uint64_t *n_blobs);
 
 /* ---- ordered catch-up: a fan-out's outputs in `change` order, with a per-peer limit ---------- */
 /* Every output of the select, fan-out and latest calls above is in row order; over a store that is

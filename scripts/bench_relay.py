@@ -89,6 +89,20 @@ probe, and the host relay through drp_relay_staged against the host round trip i
               encode is then also given over the parent's figure. --order-profile: K = 64 and the plain
               calls alone, for a rocprofv3 --kernel-trace --stats run (profiles/relay/order_kernel_stats.csv).
 
+  news        (--news-out, default profiles/relay/news_bench.json; no other leg runs) The store leg's
+              stream and sequences of 8 merges into an empty store, three ways: drp_store_merge_device,
+              drp_store_merge_report_device with a NULL report, and with a full report (outcome,
+              news_type with KEEP_BLOBS, reply with reply_cap = the batch's rows). Then the hub step
+              over batch 0 for K = 1, 8, 64 all-pass peers (the merge with its news column,
+              drp_fanout_device over the news view, drp_encode_device: what Store.relay_news composes)
+              with 0 %, 10 % and 100 % of the batch's winners news to the store (the store holds the
+              batch; holds it but for a raised `change` on every tenth key; is empty), a fresh store
+              before every timed round, against relaying the whole batch (drp_fanout_device and
+              drp_encode_device over all its rows); times and bytes out. --news-baseline-out: the plain
+              merge sequences and the whole-batch relay only, to be taken with the parent commit's
+              library and binding (DRP_LIB, DRP_PY); --news-baseline reads such a file, and the result
+              says per batch whether this build's medians lie inside the parent's own min-max spread.
+
 Prints one JSON line (and writes it to --out). Needs an MI355X: there is no CPU path.
 
   hipcc -O3 --offload-arch=gfx950 scripts/probe_bw.hip -o exp/probe_bw
@@ -912,6 +926,162 @@ def store_leg(ctx, drp_amd, torch, frames, seqs, iters):
     return res
 
 
+# ---- merge report: the plain merge, the report's cost, the hub step ---------------------------------
+
+NEWS_KS = (1, 8, 64)
+NEWS_SHARES = (0, 10, 100)  # per cent of the hub batch's winners that are news to the store
+
+
+def _news_timed(ctx, torch, dev):
+    ext = ctx._ext(dev)
+
+    def timed(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record(ext)
+        fn()
+        e1.record(ext)
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+    return timed
+
+
+def _merge_sequences(ctx, drp_amd, torch, wire_t, cols, m, keys, arena_bytes, seqs, merge):
+    """The store leg's sequences (8 batches into an empty store, one warm-up sequence) under
+    merge(store, view): [seq][batch] ms, and the last store's record."""
+    timed = _news_timed(ctx, torch, torch.device("cuda", 0))
+    out, store = [], None
+    for it in range(seqs + 1):
+        store = None
+        torch.cuda.empty_cache()
+        store = drp_amd.Store(ctx, keys, arena_bytes)
+        tm = []
+        for b in range(STORE_BATCHES):
+            view = {k: v[b * m:] for k, v in cols.items()}
+            tm.append(timed(lambda: merge(store, view)))
+        if it:
+            out.append(tm)
+    return out, store.query().as_dict()
+
+
+def _whole_batch_relay(ctx, drp_amd, torch, wire_t, view, m, iters):
+    """Relaying the whole batch to K all-pass peers: drp_fanout_device and drp_encode_device over its m
+    rows (what a hub without the report sends)."""
+    dev = torch.device("cuda", 0)
+    timed = _news_timed(ctx, torch, dev)
+    res = {}
+    for K in NEWS_KS:
+        total = K * m
+        rows = _row_tensors(torch, dev, total)
+        rb_t = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+        foff = torch.zeros(total + 1, dtype=torch.int64, device=dev)
+        out = torch.zeros(total * 86, dtype=torch.uint8, device=dev)
+        flt = [None] * K
+        tf, te = [], []
+        for it in range(iters + 2):
+            a = timed(lambda: ctx.fanout_device(wire_t, view, m, flt, rows, total, None, rb_t))
+            b = timed(lambda: ctx.encode_device(rows, wire_t, total, foff, out, out.numel()))
+            if it >= 2:
+                tf.append(a)
+                te.append(b)
+        assert int(rb_t.cpu()[K]) == total and int(foff[total].cpu()) == total * 86
+        res[f"K{K}"] = {"filters": K, "rows_out": total, "out_bytes": total * 86, "fanout_ms": _stat(tf),
+                        "encode_ms": _stat(te), "total_ms_median": statistics.median(tf) + statistics.median(te)}
+        print("whole-batch relay", K, res[f"K{K}"], file=sys.stderr, flush=True)
+        rows = foff = out = None
+        torch.cuda.empty_cache()
+    return res
+
+
+def news_baseline(ctx, drp_amd, torch, frames, seqs, iters):
+    """What the parent commit's library can take: the plain merge sequences and the whole-batch relay."""
+    key_ids, wire_t, cols, n, m = _store_input(ctx, drp_amd, torch, frames)
+    keys = int(len(np.unique(key_ids)))
+    arena_bytes = 80 * (keys + STORE_BATCHES * m) // 2
+    merges, info = _merge_sequences(ctx, drp_amd, torch, wire_t, cols, m, keys, arena_bytes, seqs,
+                                    lambda s, v: ctx.store_merge_device(s, wire_t, v, m))
+    return {"bench": "relay_news_baseline", "frames": n, "batch_rows": m, "seqs": seqs, "merge_ms": _per_batch(merges),
+            "final_info": info, "whole_batch": _whole_batch_relay(ctx, drp_amd, torch, wire_t, cols, m, iters)}
+
+
+def news_leg(ctx, drp_amd, torch, frames, seqs, iters, parent=None):
+    dev = torch.device("cuda", 0)
+    key_ids, wire_t, cols, n, m = _store_input(ctx, drp_amd, torch, frames)
+    keys = int(len(np.unique(key_ids)))
+    arena_bytes = 80 * (keys + STORE_BATCHES * m) // 2
+    timed = _news_timed(ctx, torch, dev)
+    z = lambda k, dt: torch.zeros(max(k, 1), dtype=dt, device=dev)
+    outcome, news, reply, ridx, nrep = z(m, torch.uint8), z(m, torch.uint8), _row_tensors(torch, dev, m), z(m, torch.int64), \
+        z(1, torch.int64)
+    legs = {"merge_ms": lambda s, v: ctx.store_merge_device(s, wire_t, v, m),
+            "null_report_ms": lambda s, v: ctx.store_merge_report_device(s, wire_t, v, m, report=False),
+            "full_report_ms": lambda s, v: ctx.store_merge_report_device(s, wire_t, v, m, None, outcome, news, reply, ridx,
+                                                                         nrep, m, drp_amd.REPORT_KEEP_BLOBS)}
+    res = {"frames": n, "batches": STORE_BATCHES, "batch_rows": m, "keys": keys, "seqs": seqs}
+    infos = {}
+    for name, fn in legs.items():
+        ts, infos[name] = _merge_sequences(ctx, drp_amd, torch, wire_t, cols, m, keys, arena_bytes, seqs, fn)
+        res[name] = _per_batch(ts)
+        res["sum_" + name] = sum(x["median"] for x in res[name])
+        print("news", name, res["sum_" + name], file=sys.stderr, flush=True)
+    assert infos["merge_ms"] == infos["null_report_ms"] == infos["full_report_ms"], "the three merges' stores"
+    res["final_info"] = infos["merge_ms"]
+    res["full_over_merge"] = res["sum_full_report_ms"] / res["sum_merge_ms"]
+    if parent is not None:
+        assert parent["frames"] == n and parent["batch_rows"] == m and parent["final_info"] == res["final_info"]
+        res["parent_merge_ms"] = parent["merge_ms"]
+        res["sum_parent_merge_ms"] = sum(x["median"] for x in parent["merge_ms"])
+        # (a): this build's median inside the parent's own min-max spread, batch by batch
+        for name in ("merge_ms", "null_report_ms"):
+            res[name + "_in_parent_spread"] = [p["min"] <= x["median"] <= p["max"]
+                                               for x, p in zip(res[name], parent["merge_ms"])]
+            res[name + "_over_parent"] = [x["median"] / p["median"] for x, p in zip(res[name], parent["merge_ms"])]
+    # (c) the hub step over batch 0: merge with the news column, fan-out over the news view, encode
+    view = cols
+    raised = torch.from_numpy(np.where(np.asarray(key_ids[:m]) % 10 == 0, 1000, 0).astype(np.int64)).to(dev)
+    bumped = {**view, "change": view["change"][:m] + raised}  # (every row of every tenth key: its winner is replaced)
+    res["whole_batch"] = _whole_batch_relay(ctx, drp_amd, torch, wire_t, view, m, iters)
+    if parent is not None:
+        res["parent_whole_batch"] = parent["whole_batch"]
+    res["hub"] = {}
+    for share in NEWS_SHARES:
+        batch = bumped if share == 10 else view
+        for K in NEWS_KS:
+            total = K * m
+            rows = _row_tensors(torch, dev, total)
+            rb_t = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+            foff = torch.zeros(total + 1, dtype=torch.int64, device=dev)
+            out = torch.zeros(total * 86, dtype=torch.uint8, device=dev)
+            flt = [None] * K
+            tm, tf, te, sent, info = [], [], [], 0, None
+            for it in range(iters + 2):
+                store = drp_amd.Store(ctx, keys, arena_bytes)
+                if share != 100:  # (the store holds the batch already; at 10: all but the raised changes)
+                    ctx.store_merge_device(store, wire_t, view, m)
+                a = timed(lambda: ctx.store_merge_report_device(store, wire_t, batch, m, None, None, news,
+                                                                flags=drp_amd.REPORT_KEEP_BLOBS))
+                b = timed(lambda: ctx.fanout_device(wire_t, {**batch, "type": news}, m, flt, rows, total, None, rb_t))
+                sent = int(rb_t.cpu()[K])
+                c = timed(lambda: ctx.encode_device(rows, wire_t, sent, foff, out, out.numel())) if sent else 0.0
+                info = store.query()
+                if it >= 2:
+                    tm.append(a)
+                    tf.append(b)
+                    te.append(c)
+            assert sent == K * (info.inserted + info.replaced) and info.refused == 0
+            out_bytes = int(foff[sent].cpu()) if sent else 0
+            whole = res["whole_batch"][f"K{K}"]
+            r = {"filters": K, "news_rows": sent // K, "winners": int(info.winners), "rows_out": sent, "out_bytes": out_bytes,
+                 "merge_report_ms": _stat(tm), "fanout_ms": _stat(tf), "encode_ms": _stat(te),
+                 "total_ms_median": statistics.median(tm) + statistics.median(tf) + statistics.median(te),
+                 "whole_batch_total_ms_median": whole["total_ms_median"], "whole_batch_out_bytes": whole["out_bytes"]}
+            res["hub"][f"news{share}_K{K}"] = r
+            print("hub step", share, K, r, file=sys.stderr, flush=True)
+            rows = foff = out = None
+            torch.cuda.empty_cache()
+    return res
+
+
 # ---- ordered catch-up -----------------------------------------------------------------------------
 
 ORDER_KS = (1, 8, 64)
@@ -1425,6 +1595,11 @@ def main():
                     help="only the yardsticks and the single-level reconcile (any commit's library with the digest), written here")
     ap.add_argument("--digest-refine-baseline", default=None,
                     help="such a file of the parent commit, read into the refined-digest leg's result")
+    ap.add_argument("--news-out", nargs="?", default=None, const=os.path.join(ROOT, "profiles", "relay", "news_bench.json"),
+                    help="run the merge report leg alone (over the store leg's stream) and write its JSON line here")
+    ap.add_argument("--news-baseline-out", default=None,
+                    help="run the plain merges and the whole-batch relay alone (no call of this commit) and write them here")
+    ap.add_argument("--news-baseline", default=None, help="such a file of the parent commit, read into the news leg's result")
     ap.add_argument("--order-out", nargs="?", default=None, const=os.path.join(ROOT, "profiles", "relay", "order_bench.json"),
                     help="run the ordered catch-up leg alone and write its JSON line here")
     ap.add_argument("--order-profile", action="store_true",
@@ -1450,6 +1625,21 @@ def main():
     torch.cuda.init()
     import _streams as S
     import drp_amd
+    if a.news_baseline_out:
+        with drp_amd.Ctx(0) as ctx:
+            base = news_baseline(ctx, drp_amd, torch, a.frames, a.store_seqs, a.iters)
+        with open(a.news_baseline_out, "w") as f:
+            f.write(json.dumps(base) + "\n")
+        print(json.dumps(base))
+        return
+    if a.news_out:
+        parent = json.loads(open(a.news_baseline).read()) if a.news_baseline else None
+        with drp_amd.Ctx(0) as ctx:
+            nw = {"bench": "relay_news", "device": news_leg(ctx, drp_amd, torch, a.frames, a.store_seqs, a.iters, parent)}
+        with open(a.news_out, "w") as f:
+            f.write(json.dumps(nw) + "\n")
+        print(json.dumps(nw))
+        return
     if a.order_baseline_out:
         with drp_amd.Ctx(0) as ctx:
             base = order_baseline(ctx, drp_amd, torch, a.frames, a.iters)
