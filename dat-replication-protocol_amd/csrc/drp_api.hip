@@ -164,6 +164,7 @@ int drp_open(int device, drp_ctx **out) {
   if (const char *e = getenv("DRP_CASCADE_MIN")) c->cascade_min = (uint32_t)strtoul(e, nullptr, 10);
   if (const char *e = getenv("DRP_JUMP_MIN")) c->jump_min = strtoll(e, nullptr, 10);
   if (const char *e = getenv("DRP_WALK_MIN")) c->walk_min = strtoull(e, nullptr, 10);
+  if (const char *e = getenv("DRP_SIDE_MIN")) c->side_min = strtoull(e, nullptr, 10);
   if (const char *e = getenv("DRP_PIPE_CHUNK")) c->pipe_chunk = strtoull(e, nullptr, 10) << 20;
   if (const char *e = getenv("DRP_CREC")) c->crec = atoi(e);
   if (const char *e = getenv("DRP_CLAIMS")) c->claims_mode = strcmp(e, "fast") == 0 ? 2 : strcmp(e, "hop") == 0 ? 3 : 0;
@@ -204,6 +205,12 @@ void drp_close(drp_ctx *c) {
   (void)hipStreamSynchronize(c->fst);
   (void)hipStreamDestroy(c->fst);
   (void)hipEventDestroy(c->fev);
+  if (c->sst) {
+    (void)hipStreamSynchronize(c->sst);
+    (void)hipStreamDestroy(c->sst);
+  }
+  for (auto &e : c->sev)
+    if (e) (void)hipEventDestroy(e);
   c->fbounce.release();
   (void)hipStreamDestroy(c->st);
   delete c;
@@ -295,7 +302,7 @@ static DecLayout dec_layout(uint32_t B, uint64_t nbytes, uint64_t ns) {
   L.fmiss = o; o += al(ns * 8);                  // first missed tile per stream (verify)
   L.segw = o; o += al((2 * 64 * 8192 + 8194) * 8 + 65 * 8192);  // segmented repair: candidates, entries,
                                                                 // next-candidate tables, lanes (SEG_NMAX)
-  L.scan_tmp = o; o += al((L.ntiles_max / 4096 + 2) * 8);  // tile scans: block sums
+  L.scan_tmp = o; o += al(2 * (L.ntiles_max / 4096 + 2) * 8);  // tile scans: block sums (the tail's: two arrays)
   L.walk = o; o += al((ns + 2) * 8);                         // region walkers: per-stream region prefix
   L.went = o; o += al((L.ntiles_max + ns + 2) * 8);          // region walkers: entries
   L.wdense = o; o += 64;                                     // region walkers: density sample
@@ -644,8 +651,33 @@ int run_decode_spec(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const uin
   // after a failed prediction, which is repaired below before they run again. A decode whose
   // prediction holds makes one host round trip.
   const uint32_t *abort_flag = P.overflow;
+  // Batches of at least side_min tiles (DRP_SIDE_MIN; off by default) run the side emitters and
+  // stream_counts on the side stream, beside emit_recs (small ones and staged pieces would only
+  // pay the events' host time).
+  DrpSide side = {};
+  const DrpSide *sidep = nullptr;
+  if (NT >= c->side_min) {
+    if (!c->sst) {
+      hipStream_t s = nullptr;
+      if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess ||
+          hipEventCreateWithFlags(&c->sev[0], hipEventDisableTiming) != hipSuccess ||
+          hipEventCreateWithFlags(&c->sev[1], hipEventDisableTiming) != hipSuccess) {
+        if (s) (void)hipStreamDestroy(s);
+        for (auto &e : c->sev) {
+          if (e) (void)hipEventDestroy(e);
+          e = nullptr;
+        }
+        return DRP_E_HIP;
+      }
+      c->sst = s;
+    }
+    side.st = c->sst;
+    side.fork = c->sev[0];
+    side.join = c->sev[1];
+    sidep = &side;
+  }
   auto launch_tail = [&]() -> int {
-    CHK(drp_launch_spec_tail(&P, NT, ns, tstream, sgscan, st));
+    CHK(drp_launch_spec_tail(&P, NT, ns, tstream, sgscan, st, sidep));
     CHK(hipEventRecord(c->ev[2], st));
     CHK(drp_launch_finalize(bytes, stream_off, ns, tile_prefix, P.tile_exit, P.tile_base, P.tile_count, perr,
                             scount, fr->type, co->flags, cap, res, abort_flag, drp_spec_retry_mask(), st));

@@ -829,6 +829,9 @@ __global__ __launch_bounds__(NT, DRP_K1G_WAVES) void spec_claims(DecodeParams P)
 #define DRP_FCAP 512
 #endif
 constexpr uint32_t FCAP = DRP_FCAP;
+#ifndef DRP_PARSE_HOIST
+#define DRP_PARSE_HOIST 4  // the parse's header loads in flight per thread (A/B: 0 in the body, 2 two and two)
+#endif
 #ifndef DRP_HALO_WAVE
 #define DRP_HALO_WAVE 0  // the wave whose lanes build the halo's live masks (A/B: 1, the second wave)
 #endif
@@ -1589,6 +1592,19 @@ __device__ __forceinline__ uint32_t fast_claims(const DecodeParams &P, const Til
   uint32_t cfw[KPT];  // a Change frame leaving the image: payload offset | length << 14
   uint32_t cff[KPT];  // its first field's bytes | key seen << 20
   const uint32_t *w32 = reinterpret_cast<const uint32_t *>(P.bytes + G.A);  // (L2: the tile was just read)
+  // Interior tiles: the header bytes o .. o + 7 of all of this thread's nodes, one byte-addressed
+  // 8-byte load each, issued together before the first body parses: one L2 round trip per
+  // workgroup (a body that loads its own header waits for L2 once per node, KPT times in a row).
+  // A thread without a node i loads the tile's first bytes. DRP_PARSE_HOIST: nodes per group of
+  // loads in flight (A/B builds: 0 loads in the body, as before).
+  constexpr uint32_t PH = EDGE ? 0u : DRP_PARSE_HOIST;
+  static_assert(PH == 0 || KPT % PH == 0, "whole groups of hoisted header loads");
+  uint32_t ho[KPT];
+  uint64_t hx[KPT];
+  if (PH) {
+#pragma unroll
+    for (uint32_t j = 0; j < KPT; j++) ho[j] = tid + j * NT < total ? (uint32_t)lpos[tid + j * NT] : 0u;
+  }
 #pragma unroll
   for (uint32_t j = 0; j < KPT; j++) {
     const uint32_t i = tid + j * NT;
@@ -1597,8 +1613,12 @@ __device__ __forceinline__ uint32_t fast_claims(const DecodeParams &P, const Til
     npos[j] = 0;
     cfw[j] = 0;
     cff[j] = 0;
+    if (PH && j % (PH ? PH : 1u) == 0) {
+#pragma unroll
+      for (uint32_t q = j; q < j + PH; q++) __builtin_memcpy(&hx[q], P.bytes + G.A + ho[q], 8);
+    }
     if (i < total) {
-      const uint32_t o = lpos[i];
+      const uint32_t o = PH ? ho[j] : (uint32_t)lpos[i];
       uint32_t w, wn, k, L, id, succ;
       bool valid, tail, exact = false;
       if (EDGE && o + 16u > se_rel) {  // (edge tiles) the window crosses the stream end: parse_win's grammar
@@ -1612,10 +1632,15 @@ __device__ __forceinline__ uint32_t fast_claims(const DecodeParams &P, const Til
         succ = h.kind == H_VALID ? (uint32_t)(h.succ - G.A) : o + 1u;
         w = wn = 0;
       } else {
-        const uint32_t d = o >> 2, sh = (o & 3u) * 8u;
-        const uint32_t a0 = w32[d], a1 = w32[d + 1], a2 = w32[d + 2];
-        w = __builtin_amdgcn_alignbit(a1, a0, sh);
-        wn = __builtin_amdgcn_alignbit(a2, a1, sh);
+        if (PH) {
+          w = (uint32_t)hx[j];
+          wn = (uint32_t)(hx[j] >> 32);
+        } else {
+          const uint32_t d = o >> 2, sh = (o & 3u) * 8u;
+          const uint32_t a0 = w32[d], a1 = w32[d + 1], a2 = w32[d + 2];
+          w = __builtin_amdgcn_alignbit(a1, a0, sh);
+          wn = __builtin_amdgcn_alignbit(a2, a1, sh);
+        }
         const uint32_t tm = ~w & 0x808080u;  // live => a terminator in bytes 0..2
         k = ((uint32_t)__builtin_ctz(tm | 0x80000000u) >> 3) + 1u;
         const uint32_t L3 = (w & 0x7Fu) | ((w >> 1) & 0x3F80u) | ((w >> 2) & 0x1FC000u);
@@ -2323,6 +2348,92 @@ __global__ __launch_bounds__(SCAN_BLK) void scan_down(const uint64_t *cnt, const
   }
 }
 
+// The speculative tail's scan: both per-tile counts in one pass (tile_count -> tile_base with the
+// capacity check, tile_nch -> tile_nch_base without one; bsum holds the two block-sum arrays one
+// after the other). tile_nch is final once verification has run, so its bases need no pass of
+// their own after emission. The pass also does two small jobs that were launches of their own: it
+// zeroes the list count emit_lean appends to (scan_top2, or the one-block scan_down2), and, for
+// each tile it gives a base, it marks the 64-row output chunks that start in the tile (emit_recs'
+// chunk_tile; the marks need records, rows, and a base below cap, and end at cap).
+struct Scan2 {
+  const uint64_t *cnt, *nch, *tile_prefix;
+  uint64_t nstreams;
+  uint64_t *bsum, *base, *nch_base;
+  uint64_t cap;
+  uint32_t *overflow;
+  uint32_t *vlist_n;       // (may be null)
+  const uint32_t *rec_on;  // counter[13]: claims_fast wrote records (null: no chunk marks)
+  uint32_t *chunk_tile;
+};
+
+__global__ __launch_bounds__(SCAN_BLK) void scan_reduce2(Scan2 S) {
+  __shared__ uint64_t sw[SCAN_BLK / WAVE];
+  const uint64_t nt = S.tile_prefix[S.nstreams];
+  const uint64_t i0 = (uint64_t)blockIdx.x * SCAN_SPAN + threadIdx.x * SCAN_PER;
+  uint64_t v = 0, w = 0;
+  for (uint32_t k = 0; k < SCAN_PER; k++)
+    if (i0 + k < nt) {
+      v += S.cnt[i0 + k];
+      w += S.nch[i0 + k];
+    }
+  uint64_t tv, tw;
+  (void)block_excl_scan64(v, sw, tv);
+  (void)block_excl_scan64(w, sw, tw);
+  if (threadIdx.x == 0) {
+    S.bsum[blockIdx.x] = tv;
+    S.bsum[gridDim.x + blockIdx.x] = tw;
+  }
+}
+
+__global__ __launch_bounds__(SCAN_BLK) void scan_top2(uint64_t *bsum, uint64_t nb, uint32_t *vlist_n) {
+  __shared__ uint64_t sw[SCAN_BLK / WAVE];
+  if (vlist_n && threadIdx.x == 0) *vlist_n = 0;
+  for (uint32_t a = 0; a < 2; a++) {
+    uint64_t *b = bsum + a * nb;
+    uint64_t carry = 0;
+    for (uint64_t c0 = 0; c0 < nb; c0 += SCAN_BLK) {
+      const uint64_t i = c0 + threadIdx.x;
+      const uint64_t v = i < nb ? b[i] : 0;
+      uint64_t total;
+      const uint64_t ex = block_excl_scan64(v, sw, total);
+      if (i < nb) b[i] = carry + ex;
+      carry += total;
+    }
+  }
+}
+
+template <bool ONE>
+__global__ __launch_bounds__(SCAN_BLK) void scan_down2(Scan2 S) {
+  __shared__ uint64_t sw[SCAN_BLK / WAVE];
+  if (ONE && S.vlist_n && threadIdx.x == 0) *S.vlist_n = 0;
+  const uint64_t nt = S.tile_prefix[S.nstreams];
+  const uint64_t i0 = (uint64_t)blockIdx.x * SCAN_SPAN + threadIdx.x * SCAN_PER;
+  uint64_t c[SCAN_PER], d[SCAN_PER], v = 0, w = 0;
+  for (uint32_t k = 0; k < SCAN_PER; k++) {
+    c[k] = i0 + k < nt ? S.cnt[i0 + k] : 0;
+    d[k] = i0 + k < nt ? S.nch[i0 + k] : 0;
+    v += c[k];
+    w += d[k];
+  }
+  uint64_t total;
+  uint64_t o = (ONE ? 0ull : S.bsum[blockIdx.x]) + block_excl_scan64(v, sw, total);
+  uint64_t q = (ONE ? 0ull : S.bsum[gridDim.x + blockIdx.x]) + block_excl_scan64(w, sw, total);
+  const bool marks = S.rec_on && *S.rec_on;
+  for (uint32_t k = 0; k < SCAN_PER; k++) {
+    if (i0 + k < nt) {
+      S.base[i0 + k] = o;
+      S.nch_base[i0 + k] = q;
+      if (i0 + k == nt - 1 && o + c[k] > S.cap) atomicOr(S.overflow, 1u);
+      if (marks && c[k] && o < S.cap) {
+        const uint64_t e = umin64(o + c[k], S.cap);
+        for (uint64_t ch = (o + 63) / 64; ch * 64 < e; ch++) S.chunk_tile[ch] = (uint32_t)(i0 + k);
+      }
+    }
+    o += c[k];
+    q += d[k];
+  }
+}
+
 // ==== kernel 3: emission ========================================================================
 // Frame-major: the tile's frame starts go to an LDS list (thread order = stream order), then
 // thread i decodes frames i, i + NT, ... so every column store is a contiguous run.
@@ -2828,22 +2939,12 @@ __device__ __forceinline__ void emit_rec_row(const RowCols &C, uint32_t i, uint6
 }
 // Output rows in chunks of 64, each chunk's stores starting at a 64-row boundary of the columns
 // (scripts/probe_bw.hip: 62 B-per-row column stores run at 5.8 TB/s from 64-aligned chunks and at
-// 2.9 TB/s from chunks shifted off that boundary). chunk_tiles first marks, per chunk, the tile
-// holding its first row; the rows of a chunk then lie in that tile and the ones up to the next
-// chunk's. A wave per chunk: its lanes' rows, their tiles (the first or the next one in the fast
-// path, else a search over the tiles' first rows), and for a tile with records (tile_recok) the
-// row's record words, loaded before the row is stored. Rows of tiles without records are left to
-// emit_lean.
-__global__ __launch_bounds__(256) void chunk_tiles(DecodeParams P) {
-  if (!P.counter[13]) return;  // (claims_fast wrote no records: the hop walkers' claims)
-  const uint64_t t = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  if (t >= P.tile_prefix[P.nstreams]) return;
-  const uint64_t b = P.tile_base[t], n = P.tile_count[t];
-  if (!n || b >= P.cap) return;
-  const uint64_t e = umin64(b + n, P.cap);
-  for (uint64_t c = (b + 63) / 64; c * 64 < e; c++) P.chunk_tile[c] = (uint32_t)t;
-}
-
+// 2.9 TB/s from chunks shifted off that boundary). The tail's scan (scan_down2) first marks, per
+// chunk, the tile holding its first row; the rows of a chunk then lie in that tile and the ones up
+// to the next chunk's. A wave per chunk: its lanes' rows, their tiles (the first or the next one
+// in the fast path, else a search over the tiles' first rows), and for a tile with records
+// (tile_recok) the row's record words, loaded before the row is stored. Rows of tiles without
+// records are left to emit_lean.
 constexpr uint32_t ER_WAVES = 4;  // chunks (waves) per workgroup
 __global__ __launch_bounds__(ER_WAVES * WAVE) void emit_recs(DecodeParams P) {
   if (*P.overflow & (F_MISS | F_WAIT)) return;  // (a failed prediction: emitted after its repair)
@@ -3904,51 +4005,92 @@ extern "C" hipError_t drp_launch_spec_verify_list(const DecodeParams *P, uint64_
   return hipGetLastError();
 }
 
-// Everything after verification: output bases, emission, change-count bases, stream counts.
+// The tail's scan of both per-tile counts (spec::Scan2): one launch when a single block covers every
+// tile (small batches and staged pieces), else reduce, top, down. tmp: two block-sum arrays.
+extern "C" hipError_t drp_launch_tile_scan2(const DecodeParams *P, uint64_t nstreams, uint64_t nt_max, uint64_t *tmp,
+                                            hipStream_t st) {
+  if (nt_max == 0) return hipSuccess;
+  spec::Scan2 S;
+  S.cnt = P->tile_count;
+  S.nch = P->tile_nch;
+  S.tile_prefix = P->tile_prefix;
+  S.nstreams = nstreams;
+  S.bsum = tmp;
+  S.base = P->tile_base;
+  S.nch_base = P->tile_nch_base;
+  S.cap = P->cap;
+  S.overflow = P->overflow;
+  S.vlist_n = P->vlist ? P->vlist_n : nullptr;
+  S.rec_on = P->vlist && P->rec ? P->counter + 13 : nullptr;
+  S.chunk_tile = P->chunk_tile;
+  const uint32_t nb = (uint32_t)((nt_max + spec::SCAN_SPAN - 1) / spec::SCAN_SPAN);
+  if (nb == 1) {  // (small batches: one launch; a staged piece pays each launch's host cost)
+    hipLaunchKernelGGL(spec::scan_down2<true>, dim3(1), dim3(spec::SCAN_BLK), 0, st, S);
+    return hipGetLastError();
+  }
+  hipLaunchKernelGGL(spec::scan_reduce2, dim3(nb), dim3(spec::SCAN_BLK), 0, st, S);
+  hipLaunchKernelGGL(spec::scan_top2, dim3(1), dim3(spec::SCAN_BLK), 0, st, tmp, (uint64_t)nb, S.vlist_n);
+  hipLaunchKernelGGL(spec::scan_down2<false>, dim3(nb), dim3(spec::SCAN_BLK), 0, st, S);
+  return hipGetLastError();
+}
+
+// Everything after verification: the output and change-count bases (one scan, which also zeroes
+// the deferred-tile count and marks emit_recs' chunks), emission, stream counts. With a side
+// stream (side != null: the caller's choice by batch size) the emitters of the few tiles without
+// records and stream_counts run there, forked behind the scan and joined before this returns,
+// beside emit_recs on st: their rows are disjoint from its rows (emit_sparse takes tile_sparse
+// tiles, which have no records; emit_lean skips both marks; emit_tiles takes emit_lean's list).
 extern "C" hipError_t drp_launch_spec_tail(const DecodeParams *P, uint64_t nt_max, uint64_t nstreams,
-                                           uint32_t *tile_stream, uint64_t *scan_tmp, hipStream_t st) {
+                                           uint32_t *tile_stream, uint64_t *scan_tmp, hipStream_t st,
+                                           const DrpSide *side) {
   if (nt_max == 0) return hipSuccess;
   DecodeParams Q = *P;
   Q.tile_stream = nstreams > 1 ? tile_stream : nullptr;
-  hipError_t e = drp_launch_tile_scan(Q.tile_count, Q.tile_prefix, nstreams, nt_max, scan_tmp, Q.tile_base, Q.cap,
-                                      Q.overflow, st);
+  hipError_t e = drp_launch_tile_scan2(&Q, nstreams, nt_max, scan_tmp, st);
   if (e != hipSuccess) return e;
-  drp_dbg_mark("tile_scan(count)", st);
-  if (Q.vlist) {  // the fast kernel, then the general one on the tiles it lists
-    e = hipMemsetAsync(Q.vlist_n, 0, 4, st);
-    if (e != hipSuccess) return e;
-    if (spec::SP_FRAMES && Q.tile_sparse) {  // sparse tiles first (no staging), then every other tile
-      hipLaunchKernelGGL(spec::emit_sparse, dim3((uint32_t)((nt_max + spec::SP_TPB - 1) / spec::SP_TPB)), dim3(256),
-                         0, st, Q);
-      drp_dbg_mark("emit_sparse", st);
-    } else {
-      Q.tile_sparse = nullptr;
-    }
-    if (Q.rec)  // (the tiles with records; emit_lean skips them)
-    {
-      hipLaunchKernelGGL(spec::chunk_tiles, dim3((uint32_t)((nt_max + 255) / 256)), dim3(256), 0, st, Q);
-      const uint64_t nchunks = (Q.cap + 63) / 64;
-      hipLaunchKernelGGL(spec::emit_recs, dim3((uint32_t)((nchunks + spec::ER_WAVES - 1) / spec::ER_WAVES)),
-                         dim3(spec::ER_WAVES * WAVE), 0, st, Q);
-    }
-    hipLaunchKernelGGL(spec::emit_lean,
-                       dim3((uint32_t)(Q.change_checks || Q.rec ? (nt_max + spec::EMIT_LONG_TPW - 1) / spec::EMIT_LONG_TPW
-                                                                : nt_max)),
-                       dim3(spec::NT), 0, st, Q);
-    drp_dbg_mark("emit_fast", st);
-    hipLaunchKernelGGL(spec::emit_tiles, dim3((uint32_t)(nt_max < 16384 ? nt_max : 16384)), dim3(spec::NT), 0,
-                       st, Q);
-    drp_dbg_mark("emit_tiles", st);
-  } else {
-    Q.vlist = nullptr;  // every tile in the general form
+  drp_dbg_mark("tile_scan", st);
+  if (!Q.vlist) {  // every tile in the general form
     hipLaunchKernelGGL(spec::emit_tiles, dim3((uint32_t)nt_max), dim3(spec::NT), 0, st, Q);
     drp_dbg_mark("emit_tiles", st);
+    return drp_launch_stream_counts(Q.tile_prefix, nstreams, Q.tile_count, Q.tile_base, Q.tile_nch, Q.tile_nch_base,
+                                    Q.scount, st, Q.counter + 3);
   }
-  e = drp_launch_tile_scan(Q.tile_nch, Q.tile_prefix, nstreams, nt_max, scan_tmp, Q.tile_nch_base, ~0ull, Q.overflow, st);
-  if (e != hipSuccess) return e;
-  drp_dbg_mark("tile_scan(nch)", st);
-  return drp_launch_stream_counts(Q.tile_prefix, nstreams, Q.tile_count, Q.tile_base, Q.tile_nch, Q.tile_nch_base,
-                                  Q.scount, st, Q.counter + 3);
+  // the fast kernels, then the general one on the tiles emit_lean lists
+  hipStream_t ss = st;
+  if (side) {
+    e = hipEventRecord(side->fork, st);
+    if (e == hipSuccess) e = hipStreamWaitEvent(side->st, side->fork, 0);
+    if (e != hipSuccess) return e;
+    ss = side->st;
+  }
+  if (spec::SP_FRAMES && Q.tile_sparse) {  // sparse tiles first (no staging), then every other tile
+    hipLaunchKernelGGL(spec::emit_sparse, dim3((uint32_t)((nt_max + spec::SP_TPB - 1) / spec::SP_TPB)), dim3(256), 0,
+                       ss, Q);
+    drp_dbg_mark("emit_sparse", ss);
+  } else {
+    Q.tile_sparse = nullptr;
+  }
+  if (Q.rec) {  // (the tiles with records; emit_lean skips them)
+    const uint64_t nchunks = (Q.cap + 63) / 64;
+    hipLaunchKernelGGL(spec::emit_recs, dim3((uint32_t)((nchunks + spec::ER_WAVES - 1) / spec::ER_WAVES)),
+                       dim3(spec::ER_WAVES * WAVE), 0, st, Q);
+    drp_dbg_mark("emit_recs", st);
+  }
+  hipLaunchKernelGGL(spec::emit_lean,
+                     dim3((uint32_t)(Q.change_checks || Q.rec ? (nt_max + spec::EMIT_LONG_TPW - 1) / spec::EMIT_LONG_TPW
+                                                              : nt_max)),
+                     dim3(spec::NT), 0, ss, Q);
+  drp_dbg_mark("emit_fast", ss);
+  hipLaunchKernelGGL(spec::emit_tiles, dim3((uint32_t)(nt_max < 16384 ? nt_max : 16384)), dim3(spec::NT), 0, ss, Q);
+  drp_dbg_mark("emit_tiles", ss);
+  e = drp_launch_stream_counts(Q.tile_prefix, nstreams, Q.tile_count, Q.tile_base, Q.tile_nch, Q.tile_nch_base,
+                               Q.scount, ss, Q.counter + 3);
+  if (side) {  // (joined even after a failed launch: st never runs ahead of the side stream's work)
+    hipError_t j = hipEventRecord(side->join, ss);
+    if (j == hipSuccess) j = hipStreamWaitEvent(st, side->join, 0);
+    if (e == hipSuccess) e = j;
+  }
+  return e;
 }
 
 extern "C" hipError_t drp_launch_blob_bytes(const uint8_t *type, const uint32_t *plen, uint64_t n, uint64_t *out,

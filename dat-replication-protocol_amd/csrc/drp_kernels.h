@@ -375,8 +375,19 @@ hipError_t drp_launch_spec_verify(const drp::DecodeParams *P, uint64_t nt_max, u
                                   uint32_t *tile_stream, hipStream_t st);
 hipError_t drp_launch_spec_verify_list(const drp::DecodeParams *P, uint64_t n, uint64_t nstreams,
                                        uint32_t *tile_stream, hipStream_t st);
+// the tail's side stream (drp_ctx: created on first use) and the events that fork it off the
+// decode stream and join it again
+struct DrpSide {
+  hipStream_t st;
+  hipEvent_t fork, join;
+};
+// side: null keeps every launch on st
 hipError_t drp_launch_spec_tail(const drp::DecodeParams *P, uint64_t nt_max, uint64_t nstreams,
-                                uint32_t *tile_stream, uint64_t *scan_tmp, hipStream_t st);
+                                uint32_t *tile_stream, uint64_t *scan_tmp, hipStream_t st, const DrpSide *side);
+// the tail's scan: tile_count -> tile_base (capacity check) and tile_nch -> tile_nch_base in one
+// pass, which also zeroes vlist_n and writes emit_recs' chunk_tile marks; tmp: 2 block-sum arrays
+hipError_t drp_launch_tile_scan2(const drp::DecodeParams *P, uint64_t nstreams, uint64_t nt_max, uint64_t *tmp,
+                                 hipStream_t st);
 // exclusive scan of a per-tile u64 array over all tiles; flags capacity overflow of the total
 hipError_t drp_launch_tile_scan(const uint64_t *in, const uint64_t *tile_prefix, uint64_t nstreams, uint64_t nt_max,
                                 uint64_t *tmp, uint64_t *out, uint64_t cap, uint32_t *overflow, hipStream_t st);
