@@ -2189,6 +2189,10 @@ __global__ __launch_bounds__(NT) void verify_counts(DecodeParams P) {
     if (tid < k) {
       P.ent[ix] = 0xFF;
       P.ent_n[ix] = 0;
+      // the record slots were laid out from the counts zeroed here: a later full pass's verify_lite
+      // would sum them to sb = 0 and hand emit_recs the slots of the frames before e_t (a
+      // pass-through tile, k = NT, loses nothing: without an entry inside it never gets tile_recok)
+      if (tid == 0 && P.tile_rec) P.tile_rec[t] = REC_NONE;
     }
     exit_t = inside ? claim : et;  // pass-through tiles keep the entry
     miss = !inside && !bogus && claim != C_ID && claim != et;  // (a chain that rejoined the stream's one)

@@ -189,3 +189,106 @@ def shadow_stream_np(nframes, period, shadow_at, small, seed=7):
     for off, h in [(0, hdr), (shadow_at, sh_small), (shadow_at + small, sh_big)]:
         a[:, off:off + len(h)] = np.frombuffer(h, np.uint8)
     return a.reshape(-1)
+
+
+# ---- a second framing that merges with the real one (tests/test_merge_site.py) -------------------
+TILE, SEG = 8192, 64  # the speculative decode's tile and per-thread segment (drp_spec.h)
+SITE_KINDS = ("blob", "narrow", "wide")
+SITE_HOSTS = ("blob", "change")
+
+
+def chain_frame(kind, slen, i, rng):
+    """One well-formed frame of exactly slen bytes (32 <= slen <= 128: a one-byte length): a tiny
+    blob, a Change whose numbers are < 2^10 (a narrow record) or one whose numbers lie in
+    [2^10, 2^32) (a wide, five-word record); key of 6 bytes, the value fills the frame."""
+    assert 32 <= slen <= 128, slen
+    if kind == "blob":
+        f = frame(rng.randbytes(slen - 2), 2)
+    else:
+        lo, hi = (0, 2 ** 10) if kind == "narrow" else (2 ** 10, 2 ** 32)
+        nums = [rng.randrange(lo, hi) for _ in range(3)]
+        head = change_payload(b"s%05d" % (i % 100000), *nums)
+        f = frame(head + b"\x32" + varint(slen - 2 - len(head) - 2) + rng.randbytes(slen - 2 - len(head) - 2))
+    assert len(f) == slen, (kind, slen, len(f))
+    return f
+
+
+def _host_frame(host, total, seed):
+    """A blob, or a Change with a long value, of exactly `total` bytes: (frame bytes, offset of the
+    first byte of the blob payload / the value inside it)."""
+    for body in range(total - 32, total):
+        if host == "blob":
+            hdr = varint(body + 1) + b"\x02"
+        else:
+            pay = change_payload(b"host%06d" % seed, 1, 2, 3) + b"\x32" + varint(body)
+            hdr = varint(len(pay) + body + 1) + b"\x01" + pay
+        if len(hdr) + body == total:
+            return hdr + bytes(body), len(hdr)
+    raise AssertionError((host, total))
+
+
+def merge_site(pre_frames, k, slen, kind, host, whole_tiles, post_frames, seed, j=7, base=0, start=0, chain=True):
+    """One site at which a second valid framing runs beside the real one and merges with it:
+    pre_frames C2 frames, a host frame (a blob, or a Change with a long value) whose header lies in
+    tile t - 1 - whole_tiles (whole_tiles >= 1: tile t - 1 holds host payload only) and whose last
+    byte is t * 8192 + 64 * k + j - 1, so the next real frame starts in segment k (1 <= k <= 127) of
+    tile t, then post_frames C2 frames. From >= 24 bytes into the host's blob payload / value up to
+    its end, the payload is a chain of well-formed slen-byte frames of `kind` (SITE_KINDS) that ends
+    exactly where the host does: a decode started on the chain delivers its frames and then the real
+    frames after the host. The prediction of the tiles inside the payload follows the chain (four
+    frames in a row make it strong, as in shadow_stream), tile t's claim is the real chain's, and the
+    real entry of tile t is the predicted entry of its thread k, with the chain's frames counted by
+    the threads before it. slen > 64 keeps the chain's last header out of segment k.
+    base: the bytes before this wire in a larger one (a frame boundary; tiles are counted from there),
+    start: the first C2 frame's number. chain=False: random filler in place of the chain (the
+    control). Returns (wire, meta): meta's offsets are absolute (base included)."""
+    assert 1 <= k <= 127 and whole_tiles >= 1 and 0 <= j < SEG
+    rng = random.Random(seed)
+    pre = c2_stream(pre_frames, seed=seed, start=start).tobytes()
+    hs = base + len(pre)
+    t = hs // TILE + 1 + whole_tiles
+    he = t * TILE + SEG * k + j
+    hostb, data = _host_frame(host, he - hs, seed)
+    hostb = bytearray(hostb)
+    n = (he - hs - data - 24) // slen
+    cs = he - n * slen
+    hostb[data:cs - hs] = rng.randbytes(cs - hs - data)
+    if chain:
+        hostb[cs - hs:] = b"".join(chain_frame(kind, slen, i, rng) for i in range(n))
+    else:
+        hostb[cs - hs:] = rng.randbytes(n * slen)
+    post = c2_stream(post_frames, seed=seed + 1, start=start + pre_frames + 1).tobytes()
+    meta = {"t": t, "k": k, "whole_tiles": whole_tiles, "host_start": hs, "host_end": he, "chain_start": cs,
+            "chain_frames": n, "slen": slen, "pre_frames": pre_frames, "post_frames": post_frames,
+            "end": he + len(post)}
+    return pre + bytes(hostb) + post, meta
+
+
+def site_cascade(sites, shadow_n=0, between=300, after=(), tail_frames=300, seed=50):
+    """The cascade case: the merge sites `sites` (merge_site keywords without base / start / seed)
+    in C2 traffic, then (shadow_n > 0) a never-merging segment shadow_stream(shadow_n, period=8192,
+    change_every=3) that starts on the next real frame boundary, `between` C2 frames, the sites
+    `after`, and tail_frames C2 frames. Returns (wire, metas): one merge_site meta per site, in
+    stream order, each with "shadow" = (first byte, end) of the segment or None."""
+    wire, metas, nf = b"", [], 0
+
+    def add_sites(lst):
+        nonlocal wire, nf
+        for i, kw in enumerate(lst):
+            w, m = merge_site(base=len(wire), start=nf, seed=seed + 7 * len(metas) + i, **kw)
+            wire += w
+            nf += kw["pre_frames"] + 1 + kw["post_frames"]
+            metas.append(m)
+
+    add_sites(sites)
+    shadow = None
+    if shadow_n:
+        shadow = (len(wire), len(wire) + shadow_n * TILE)
+        wire += shadow_stream(shadow_n, period=TILE, change_every=3, seed=seed + 1)
+        wire += c2_stream(between, seed=seed + 2, start=nf).tobytes()
+        nf += between
+    add_sites(after)
+    wire += c2_stream(tail_frames, seed=seed + 3, start=nf).tobytes()
+    for m in metas:
+        m["shadow"] = shadow
+    return wire, metas
