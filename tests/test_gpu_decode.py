@@ -368,7 +368,8 @@ def test_encode_write_paths_match_oracle(ctx, shape):
     ENC_FMAX frames a block), and all of them interleaved, written at every alignment of the
     output pointer: the wire
     equals the oracle's encode.js + protocol-buffers@2 restatement byte for byte, and the bytes
-    around it are untouched."""
+    around it are untouched. (Fields over 4 KB, frames across blocks and the 128/129-frame switch
+    laid on purpose: tests/test_gpu_encode.py.)"""
     import torch
     rng = np.random.default_rng({"tiny": 1, "c1": 2, "c5": 3, "mixed": 4, "edge": 5}[shape])
     n = {"tiny": 40_000, "c1": 20_000, "c5": 2_000, "mixed": 30_000, "edge": 20_000}[shape]
