@@ -11,6 +11,7 @@ import pytest
 
 import _oracle as O
 import _streams as S
+from _claims import _C2, filler, header_frame, live_count, place, straddle_streams  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -40,79 +41,7 @@ def ctx(request):
     c.close()
 
 
-# ---- stream construction: frames at chosen byte positions, valid frames in between -------------
-_C2 = S.c2_stream(4096, seed=5).reshape(-1, 86)
-
-
-def filler(gap, rng, quiet=False):
-    """Exactly `gap` bytes (0 or >= 2) of whole frames: C2 frames, then one or two blobs. quiet:
-    payload bytes 0x55 only (no live position but the frames' own headers)."""
-    out = []
-    while gap >= 300:
-        if quiet:
-            out.append(S.frame(S.change_payload(b"qqq", 85, 86, 87, value=b"\x55" * 70)))
-        else:
-            out.append(_C2[rng.randrange(len(_C2))].tobytes())
-        gap -= len(out[-1])
-    if gap == 129:
-        out.append(S.frame(bytes(62), 2))
-        gap -= 64
-    if gap:
-        assert gap >= 2, gap
-        n = gap - 2 if gap <= 128 else gap - 3
-        out.append(S.frame(b"\x55" * n if quiet else rng.randbytes(n), 2))
-        assert len(out[-1]) == gap, (len(out[-1]), gap)
-    return b"".join(out)
-
-
-def place(items, rng, end=None, quiet=False):
-    """A stream with frame bytes items[i][1] starting at position items[i][0] (ascending)."""
-    w = bytearray()
-    for pos, fr in items:
-        w += filler(pos - len(w), rng, quiet)
-        w += fr
-    if end is not None:
-        w += filler(end - len(w), rng, quiet)
-    return bytes(w)
-
-
-def header_frame(k, i):
-    """A Change frame whose length varint takes k bytes."""
-    vlen = {1: 40, 2: 300, 3: 17000}[k]
-    f = S.frame(S.change_payload(b"k%06d" % i, i % 100 + 1, i % 128, (i + 1) % 128,
-                                 value=(bytes(range(7, 256)) * (vlen // 249 + 1))[:vlen]))
-    assert f[k - 1] < 0x80 and all(b >= 0x80 for b in f[:k - 1])
-    return f
-
-
-def straddle_streams():
-    """Headers of 1-, 2- and 3-byte length varints (+ the id byte) that begin j = 1..k bytes before
-    the tile end and before every 16-byte edge of the halo (the image's end included): one case
-    per tile (three tiles for the 16 KB frames), streams of at most 40 tiles."""
-    rng = random.Random(41)
-    cases = [(k, j, e) for k in (1, 2, 3) for j in range(1, k + 1) for e in range(0, HALO + 1, 16)]
-    rng.shuffle(cases)
-    streams, items, t = [], [], 1
-    for i, (k, j, e) in enumerate(cases):
-        items.append((t * TILE + e - j, header_frame(k, i)))
-        t += 4 if k == 3 else 1
-        if t > 36:
-            streams.append(place(items, rng, end=t * TILE + 1000))
-            items, t = [], 1
-    if items:
-        streams.append(place(items, rng, end=t * TILE + 1000))
-    return streams
-
-
-def live_count(wire, lo, hi):
-    """Live positions in [lo, hi): a varint of 1..3 bytes, then a byte <= 2 (the claims' listing rule)."""
-    b = np.frombuffer(wire[lo:hi + 4], np.uint8).astype(np.int64)
-    b = np.pad(b, (0, max(0, hi + 4 - lo - len(b))), constant_values=0x55)
-    m, s = b >= 0x80, b <= 2
-    x = ~m[:-1] & s[1:]
-    n = hi - lo
-    live = x[:n] | (m[:n] & x[1:n + 1]) | (m[:n] & m[1:n + 1] & x[2:n + 2])
-    return int(live.sum())
+# stream construction (frames at chosen byte positions, valid frames in between): tests/_claims.py
 
 
 def dense_stream(total_want, halo_share):
