@@ -337,31 +337,46 @@ namespace {
 
 constexpr int kWaitExpired = -100;  // internal: a bounded look-back spin gave up (retryable)
 
-int run_decode_exact_once(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const uint64_t *stream_off,
-                          const uint64_t *entry, uint64_t ns, const drp_frames *fr, const drp_changes *co,
-                          uint64_t cap, drp_stream_result *res) {
-  if (ns == 0) return DRP_OK;
-  if (((uintptr_t)bytes & 15) != 0) return DRP_E_INVAL;
-  const DecLayout L = dec_layout(c->B, nbytes, ns);
-  if (!c->scratch.ensure(L.total)) return DRP_E_NOMEM;
+// The output columns of a (drp_frames, drp_changes) pair, described once: their widths in the order
+// include/drp.h documents for drp_decode_fetch_block, and the pair's members in that order.
+// Everything that carves, advances, copies or packs the columns loops over these.
+constexpr uint32_t kColW[DRP_FETCH_COLS] = {8, 4, 1, 4, 4, 4, 4, 4, 4, 8, 8, 8, 1, 8};
+constexpr int kColPayloadOff = 0, kColKeyHash = 13;
+constexpr uint32_t row_bytes() {
+  uint32_t s = 0;
+  for (uint32_t w : kColW) s += w;
+  return s;
+}
+static_assert(row_bytes() == 70, "a row of the 14 columns is 70 bytes");
+
+void col_ptrs(const drp_frames &fr, const drp_changes &co, void *p[DRP_FETCH_COLS]) {
+  void *m[DRP_FETCH_COLS] = {fr.payload_off, fr.payload_len, fr.type,    co.key_off, co.key_len,
+                             co.subset_off,  co.subset_len,  co.value_off, co.value_len, co.change,
+                             co.from,        co.to,          co.flags,   co.key_hash};
+  memcpy(p, m, sizeof(m));
+}
+void set_cols(void *const p[DRP_FETCH_COLS], drp_frames &fr, drp_changes &co) {
+  fr = {(uint64_t *)p[0], (uint32_t *)p[1], (uint8_t *)p[2]};
+  co = {(uint32_t *)p[3], (uint32_t *)p[4],  (uint32_t *)p[5],  (uint32_t *)p[6], (uint32_t *)p[7], (uint32_t *)p[8],
+        (uint64_t *)p[9], (uint64_t *)p[10], (uint64_t *)p[11], (uint8_t *)p[12], (uint64_t *)p[13]};
+}
+// the pair from row n on (a null key_hash stays null)
+void rows_at(const drp_frames &fr, const drp_changes &co, uint64_t n, drp_frames &f, drp_changes &o) {
+  void *p[DRP_FETCH_COLS];
+  col_ptrs(fr, co, p);
+  for (int k = 0; k < DRP_FETCH_COLS; k++)
+    if (p[k]) p[k] = static_cast<char *>(p[k]) + n * kColW[k];
+  set_cols(p, f, o);
+}
+
+// The part of DecodeParams both decode kernels share: the input, the output columns and the
+// per-tile and per-stream arrays of the scratch layout.
+DecodeParams decode_params(const drp_ctx *c, const DecLayout &L, const uint8_t *bytes, uint64_t nbytes,
+                           const uint64_t *stream_off, const uint64_t *entry, uint64_t ns, const drp_frames *fr,
+                           const drp_changes *co, uint64_t cap) {
   const uint64_t NT = L.ntiles_max;
-  uint64_t *tile_prefix = c->scratch.at<uint64_t>(L.tile_prefix);
-  uint64_t *rec = c->scratch.at<uint64_t>(L.rec);
   uint64_t *tiles = c->scratch.at<uint64_t>(L.tiles);
-  uint64_t *perr = c->scratch.at<uint64_t>(L.perr);
-  uint64_t *scount = c->scratch.at<uint64_t>(L.scount);
   uint32_t *ctrl = c->scratch.at<uint32_t>(L.ctrl);  // [0] tile counter [1] overflow flags
-
-  hipStream_t st = c->st;
-  CHK(hipEventRecord(c->ev[0], st));
-  CHK(hipMemsetAsync(rec, 0, 6 * NT * 8, st));
-  uint8_t *sgrp = c->scratch.at<uint8_t>(L.sgrp);
-  CHK(hipMemsetAsync(sgrp, 0, L.nsg * 32, st));
-  CHK(hipMemsetAsync(perr, 0xFF, ns * 8, st));
-  CHK(hipMemsetAsync(scount, 0, 2 * ns * 8, st));
-  CHK(hipMemsetAsync(ctrl, 0, 16, st));
-  CHK(drp_launch_tile_prefix(c->B, stream_off, ns, tile_prefix, st));
-
   DecodeParams P;
   memset(&P, 0, sizeof(P));
   P.bytes = bytes;
@@ -369,7 +384,7 @@ int run_decode_exact_once(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, con
   P.stream_off = stream_off;
   P.entry = entry;
   P.nstreams = ns;
-  P.tile_prefix = tile_prefix;
+  P.tile_prefix = c->scratch.at<uint64_t>(L.tile_prefix);
   P.payload_off = fr->payload_off;
   P.payload_len = fr->payload_len;
   P.type = fr->type;
@@ -384,6 +399,42 @@ int run_decode_exact_once(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, con
   P.to = co->to;
   P.flags = co->flags;
   P.cap = cap;
+  P.tile_exit = tiles;
+  P.tile_base = tiles + NT;
+  P.tile_count = tiles + 2 * NT;
+  P.tile_nch = tiles + 3 * NT;
+  P.tile_nch_base = tiles + 4 * NT;
+  P.payload_err = c->scratch.at<uint64_t>(L.perr);
+  P.scount = c->scratch.at<uint64_t>(L.scount);
+  P.counter = ctrl;
+  P.overflow = ctrl + 1;
+  return P;
+}
+
+int run_decode_exact_once(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const uint64_t *stream_off,
+                          const uint64_t *entry, uint64_t ns, const drp_frames *fr, const drp_changes *co,
+                          uint64_t cap, drp_stream_result *res) {
+  if (ns == 0) return DRP_OK;
+  if (((uintptr_t)bytes & 15) != 0) return DRP_E_INVAL;
+  const DecLayout L = dec_layout(c->B, nbytes, ns);
+  if (!c->scratch.ensure(L.total)) return DRP_E_NOMEM;
+  const uint64_t NT = L.ntiles_max;
+  uint64_t *tile_prefix = c->scratch.at<uint64_t>(L.tile_prefix);
+  uint64_t *rec = c->scratch.at<uint64_t>(L.rec);
+  DecodeParams P = decode_params(c, L, bytes, nbytes, stream_off, entry, ns, fr, co, cap);
+  uint64_t *perr = P.payload_err, *scount = P.scount;
+  uint32_t *ctrl = P.counter;
+
+  hipStream_t st = c->st;
+  CHK(hipEventRecord(c->ev[0], st));
+  CHK(hipMemsetAsync(rec, 0, 6 * NT * 8, st));
+  uint8_t *sgrp = c->scratch.at<uint8_t>(L.sgrp);
+  CHK(hipMemsetAsync(sgrp, 0, L.nsg * 32, st));
+  CHK(hipMemsetAsync(perr, 0xFF, ns * 8, st));
+  CHK(hipMemsetAsync(scount, 0, 2 * ns * 8, st));
+  CHK(hipMemsetAsync(ctrl, 0, 16, st));
+  CHK(drp_launch_tile_prefix(c->B, stream_off, ns, tile_prefix, st));
+
   P.ywd = rec;
   P.aggv = rec + NT;
   P.inclx = rec + 2 * NT;
@@ -395,13 +446,6 @@ int run_decode_exact_once(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, con
   P.sagg = reinterpret_cast<uint64_t *>(sgrp + L.nsg * 8);
   P.saggn = P.sagg + L.nsg;
   P.scnt = P.saggn + L.nsg;
-  P.tile_exit = tiles;
-  P.tile_base = tiles + NT;
-  P.tile_count = tiles + 2 * NT;
-  P.payload_err = perr;
-  P.scount = scount;
-  P.counter = ctrl;
-  P.overflow = ctrl + 1;
   P.strict = (uint32_t)c->strict;
   unsigned long long *dstats = c->stats ? c->dstats : nullptr;
   if (dstats) {
@@ -426,8 +470,6 @@ int run_decode_exact_once(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, con
   TRACE("decode: nbytes=%llu ns=%llu B=%u grid=%u NT=%llu", (unsigned long long)nbytes,
         (unsigned long long)ns, c->B, grid, (unsigned long long)NT);
   CHK(hipEventRecord(c->ev[1], st));
-  P.tile_nch = tiles + 3 * NT;
-  P.tile_nch_base = tiles + 4 * NT;
   CHK(drp_launch_decode(c->B, &P, grid, st));
   CHK(drp_launch_tile_scan(P.tile_nch, tile_prefix, ns, NT, c->scratch.at<uint64_t>(L.scan_tmp), P.tile_nch_base,
                            ~0ull, P.overflow, st));
@@ -530,52 +572,20 @@ int run_decode_spec(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const uin
   const uint64_t NT = L.ntiles_max;
   uint64_t *tile_prefix = c->scratch.at<uint64_t>(L.tile_prefix);
   uint64_t *rec = c->scratch.at<uint64_t>(L.rec);
-  uint64_t *tiles = c->scratch.at<uint64_t>(L.tiles);
-  uint64_t *perr = c->scratch.at<uint64_t>(L.perr);
-  uint64_t *scount = c->scratch.at<uint64_t>(L.scount);
-  uint32_t *ctrl = c->scratch.at<uint32_t>(L.ctrl);
   uint32_t *tstream = c->scratch.at<uint32_t>(L.tstream);
   uint64_t *sgscan = c->scratch.at<uint64_t>(L.scan_tmp);
   hipStream_t st = c->st;
   CHK(hipEventRecord(c->ev[0], st));
-  DecodeParams P;
-  memset(&P, 0, sizeof(P));
-  P.bytes = bytes;
-  P.nbytes = nbytes;
-  P.stream_off = stream_off;
-  P.entry = entry;
-  P.nstreams = ns;
-  P.tile_prefix = tile_prefix;
-  P.payload_off = fr->payload_off;
-  P.payload_len = fr->payload_len;
-  P.type = fr->type;
-  P.key_off = co->key_off;
-  P.key_len = co->key_len;
-  P.subset_off = co->subset_off;
-  P.subset_len = co->subset_len;
-  P.value_off = co->value_off;
-  P.value_len = co->value_len;
-  P.change = co->change;
-  P.from = co->from;
-  P.to = co->to;
-  P.flags = co->flags;
-  P.cap = cap;
+  DecodeParams P = decode_params(c, L, bytes, nbytes, stream_off, entry, ns, fr, co, cap);
+  uint64_t *perr = P.payload_err, *scount = P.scount;
+  uint32_t *ctrl = P.counter;
   P.claim = rec;
   P.incl_e = rec + NT;
   P.work = reinterpret_cast<uint32_t *>(rec + 2 * NT);
   P.work_n = ctrl + 2;
-  P.tile_exit = tiles;
-  P.tile_base = tiles + NT;
-  P.tile_count = tiles + 2 * NT;
-  P.payload_err = perr;
-  P.scount = scount;
-  P.counter = ctrl;
-  P.overflow = ctrl + 1;
   P.ent = c->scratch.at<uint8_t>(L.ent);
   P.ent_n = P.ent + NT * 128;
   P.ent_c = P.ent_n + NT * 128;
-  P.tile_nch = tiles + 3 * NT;
-  P.tile_nch_base = tiles + 4 * NT;
   P.vlist = reinterpret_cast<uint32_t *>(rec + 2 * NT) + NT;  // (after the dense work list)
   P.vlist_n = ctrl + 5;
   P.tile_k = c->scratch.at<uint8_t>(L.tk);
@@ -835,24 +845,85 @@ int run_decode(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const uint64_t
 
 // carve SoA outputs for `cap` frames out of a device buffer
 void carve(DevBuf &b, uint64_t cap, drp_frames &fr, drp_changes &co) {
+  void *p[DRP_FETCH_COLS];
   size_t o = 0;
-  auto take = [&](size_t bytes) { void *p = b.at<char>(o); o += al(bytes); return p; };
-  fr.payload_off = (uint64_t *)take(cap * 8);
-  fr.payload_len = (uint32_t *)take(cap * 4);
-  fr.type = (uint8_t *)take(cap);
-  co.key_off = (uint32_t *)take(cap * 4);
-  co.key_len = (uint32_t *)take(cap * 4);
-  co.subset_off = (uint32_t *)take(cap * 4);
-  co.subset_len = (uint32_t *)take(cap * 4);
-  co.value_off = (uint32_t *)take(cap * 4);
-  co.value_len = (uint32_t *)take(cap * 4);
-  co.change = (uint64_t *)take(cap * 8);
-  co.from = (uint64_t *)take(cap * 8);
-  co.to = (uint64_t *)take(cap * 8);
-  co.flags = (uint8_t *)take(cap);
-  co.key_hash = (uint64_t *)take(cap * 8);
+  for (int k = 0; k < DRP_FETCH_COLS; o += al(cap * kColW[k]), k++) p[k] = b.at<char>(o);
+  set_cols(p, fr, co);
 }
-size_t carve_bytes(uint64_t cap) { return 14 * 256 + cap * 70; }
+size_t carve_bytes(uint64_t cap) { return DRP_FETCH_COLS * 256 + cap * row_bytes(); }
+
+// ---- from a stream's result to a batch's outcome (every host-batch path ends in these) ----------
+
+// the rows a result keeps: the delivered frames, and the failing Change (its flags say why)
+uint64_t kept_rows(const drp_stream_result &r) {
+  return r.frames + ((r.err_code == DRP_ERR_CHANGE || r.err_code == DRP_ERR_REQUIRED) ? 1 : 0);
+}
+
+// The error and the carry of a batch of n bytes from the result of the stream that ended it: the
+// stream's rows begin at batch row `row0`, its bytes at batch offset `byte0`. An error ends the
+// stream: nothing is carried.
+void finish(const drp_stream_result &r, uint64_t row0, uint64_t byte0, uint64_t n, drp_carry *carry,
+            uint64_t *err_frame, uint32_t *err_code, uint32_t *err_detail) {
+  if (r.err_code) {
+    *err_frame = row0 + r.err_frame;
+    *err_code = r.err_code;
+    *err_detail = r.err_detail;
+  }
+  carry->blob_remaining = r.blob_remaining;
+  carry->consumed = r.err_code ? n : byte0 + r.consumed;
+  carry->tail_kind = r.tail_kind;
+  carry->frame_bytes = r.tail_kind == DRP_TAIL_CHANGE ? r.tail_frame_bytes : 0;
+}
+
+// A blob continuation (decode.js _id == 2 with _missing > 0 across _write calls) is row 0, built
+// on the host. True when the batch is continuation and nothing else: the call is done.
+using Row0 = drp_ctx::Staged::Row0;
+bool carried_blob(uint64_t brem, uint64_t n, Row0 &row, drp_carry *carry, uint64_t *n_frames) {
+  row.off = 0;
+  row.len = brem > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)brem;
+  row.type = DRP_TYPE_BLOB | DRP_FRAME_CONT | (brem > n ? DRP_FRAME_PARTIAL : 0);
+  if (brem < n) return false;
+  carry->blob_remaining = brem - n;
+  carry->consumed = n;
+  carry->tail_kind = carry->blob_remaining ? DRP_TAIL_BLOB : DRP_TAIL_NONE;
+  *n_frames = 1;
+  return true;
+}
+void put_row0(const Row0 &row, const drp_frames &f) {
+  f.payload_off[0] = row.off;
+  f.payload_len[0] = row.len;
+  f.type[0] = row.type;
+}
+
+// Payload offsets relative to each piece's staging offset -> batch offsets: staged GPU rows
+// [g0, g0 + ng), whose offsets lie at poff[0 .. ng) as u64 or (f64; exact below 2^53) as doubles.
+void shift_pieces(const drp_ctx::Staged &S, uint64_t g0, uint64_t ng, void *poff, bool f64) {
+  for (size_t k = 0; k < S.pieces.size(); k++) {
+    const uint64_t r0 = S.pieces[k].first, r1 = k + 1 < S.pieces.size() ? S.pieces[k + 1].first : ~0ull;
+    const uint64_t sh = S.pieces[k].second, lo = std::max(r0, g0), hi = std::min(r1, g0 + ng);
+    if (sh && f64)
+      for (uint64_t g = lo; g < hi; g++) static_cast<double *>(poff)[g - g0] += (double)sh;
+    else if (sh)
+      for (uint64_t g = lo; g < hi; g++) static_cast<uint64_t *>(poff)[g - g0] += sh;
+  }
+}
+
+// A one-stream decode's small device words in the ctx's aux buffer: the stream's bounds and entry,
+// the blob byte sum, the stream result and, behind it, a cut blob's payload offset.
+struct StageAux {
+  uint64_t *soff, *ent, *bsum, *dboff;
+  drp_stream_result *dres;
+};
+bool stage_aux(drp_ctx *c, StageAux &A) {
+  const size_t stage_meta = 256;
+  if (!c->aux.ensure(stage_meta + sizeof(drp_stream_result) + 64)) return false;
+  A.soff = c->aux.at<uint64_t>(0);
+  A.ent = c->aux.at<uint64_t>(16);
+  A.bsum = c->aux.at<uint64_t>(24);
+  A.dres = c->aux.at<drp_stream_result>(stage_meta);
+  A.dboff = c->aux.at<uint64_t>(stage_meta + sizeof(drp_stream_result));
+  return true;
+}
 
 }  // namespace
 
@@ -871,7 +942,6 @@ static int decode_batch_device_out(drp_ctx *c, const uint8_t *bytes, uint64_t n,
                                    const drp_frames *frames, const drp_changes *cols, uint64_t cap,
                                    uint64_t *n_frames, uint64_t *err_frame, uint32_t *err_code,
                                    uint32_t *err_detail) {
-  const bool out_dev = true;
   carry->frame_bytes = 0;
   c->staged.rows = 0;
   c->staged.valid = false;
@@ -879,112 +949,41 @@ static int decode_batch_device_out(drp_ctx *c, const uint8_t *bytes, uint64_t n,
   *err_frame = ~0ull;
   *err_code = DRP_ERR_NONE;
   *err_detail = 0;
-  uint64_t nf0 = 0;
-  const uint64_t brem = carry->blob_remaining;
-  // A blob continuation (decode.js _id == 2 with _missing > 0 across _write calls) is frame 0.
+  const uint64_t brem = carry->blob_remaining, nf0 = brem ? 1 : 0;
   if (brem) {
     if (cap < 1) return DRP_E_CAPACITY;
-    uint64_t off0 = 0;
-    uint32_t len0 = brem > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)brem;
-    uint8_t ty0 = DRP_TYPE_BLOB | DRP_FRAME_CONT | (brem > n ? DRP_FRAME_PARTIAL : 0);
-    if (out_dev) {
-      CHK(hipMemcpyAsync(frames->payload_off, &off0, 8, hipMemcpyHostToDevice, st));
-      CHK(hipMemcpyAsync(frames->payload_len, &len0, 4, hipMemcpyHostToDevice, st));
-      CHK(hipMemcpyAsync(frames->type, &ty0, 1, hipMemcpyHostToDevice, st));
-      CHK(hipStreamSynchronize(st));
-    } else {
-      frames->payload_off[0] = off0;
-      frames->payload_len[0] = len0;
-      frames->type[0] = ty0;
-    }
-    nf0 = 1;
-    if (brem >= n) {
-      carry->blob_remaining = brem - n;
-      carry->consumed = n;
-      carry->tail_kind = carry->blob_remaining ? DRP_TAIL_BLOB : DRP_TAIL_NONE;
-      *n_frames = 1;
-      return DRP_OK;
-    }
+    Row0 row;
+    const bool done = carried_blob(brem, n, row, carry, n_frames);
+    CHK(hipMemcpyAsync(frames->payload_off, &row.off, 8, hipMemcpyHostToDevice, st));
+    CHK(hipMemcpyAsync(frames->payload_len, &row.len, 4, hipMemcpyHostToDevice, st));
+    CHK(hipMemcpyAsync(frames->type, &row.type, 1, hipMemcpyHostToDevice, st));
+    CHK(hipStreamSynchronize(st));
+    if (done) return DRP_OK;
   }
-  const uint64_t entry0 = brem;
   // input: device & aligned, or staged
   const uint8_t *dbytes = bytes;
-  const size_t stage_meta = 256;
-  if (!c->aux.ensure(stage_meta + sizeof(drp_stream_result) + 64)) return DRP_E_NOMEM;
-  uint64_t *soff = c->aux.at<uint64_t>(0);
-  uint64_t *ent = c->aux.at<uint64_t>(16);
-  drp_stream_result *dres = c->aux.at<drp_stream_result>(stage_meta);
+  StageAux A;
+  if (!stage_aux(c, A)) return DRP_E_NOMEM;
   if (!is_device_ptr(bytes) || ((uintptr_t)bytes & 15)) {
     if (!c->in_stage.ensure(n + 64)) return DRP_E_NOMEM;
     if (n) CHK(hipMemcpyAsync(c->in_stage.p, bytes, n, hipMemcpyDefault, st));
     dbytes = (const uint8_t *)c->in_stage.p;
   }
-  uint64_t hv[3] = {0, n, entry0};
-  CHK(hipMemcpyAsync(soff, hv, 16, hipMemcpyHostToDevice, st));
-  CHK(hipMemcpyAsync(ent, hv + 2, 8, hipMemcpyHostToDevice, st));
-  const uint64_t cap_rest = cap - nf0;
+  uint64_t hv[3] = {0, n, brem};
+  CHK(hipMemcpyAsync(A.soff, hv, 16, hipMemcpyHostToDevice, st));
+  CHK(hipMemcpyAsync(A.ent, hv + 2, 8, hipMemcpyHostToDevice, st));
   drp_frames dfr;
   drp_changes dco;
-  if (out_dev) {
-    dfr.payload_off = frames->payload_off + nf0;
-    dfr.payload_len = frames->payload_len + nf0;
-    dfr.type = frames->type + nf0;
-    dco.key_off = cols->key_off + nf0;
-    dco.key_len = cols->key_len + nf0;
-    dco.subset_off = cols->subset_off + nf0;
-    dco.subset_len = cols->subset_len + nf0;
-    dco.value_off = cols->value_off + nf0;
-    dco.value_len = cols->value_len + nf0;
-    dco.change = cols->change + nf0;
-    dco.from = cols->from + nf0;
-    dco.to = cols->to + nf0;
-    dco.flags = cols->flags + nf0;
-    dco.key_hash = cols->key_hash ? cols->key_hash + nf0 : nullptr;
-  } else {
-    if (!c->out_stage.ensure(carve_bytes(cap_rest))) return DRP_E_NOMEM;
-    carve(c->out_stage, cap_rest, dfr, dco);
-  }
-  int rc = run_decode(c, dbytes, n, soff, ent, 1, &dfr, &dco, cap_rest, dres);
+  rows_at(*frames, *cols, nf0, dfr, dco);
+  const int rc = run_decode(c, dbytes, n, A.soff, A.ent, 1, &dfr, &dco, cap - nf0, A.dres);
   if (rc != DRP_OK && rc != DRP_E_CAPACITY) return rc;
   drp_stream_result r;
-  CHK(hipMemcpyAsync(&r, dres, sizeof(r), hipMemcpyDeviceToHost, st));
+  CHK(hipMemcpyAsync(&r, A.dres, sizeof(r), hipMemcpyDeviceToHost, st));
   CHK(hipStreamSynchronize(st));
-  const uint64_t nf = r.frames;
-  // keep the failing Change in the table (its flags say why)
-  uint64_t ncopy = nf + ((r.err_code == DRP_ERR_CHANGE || r.err_code == DRP_ERR_REQUIRED) ? 1 : 0);
-  if (ncopy > cap_rest) ncopy = cap_rest;
-  if (!out_dev && ncopy) {
-    auto cp = [&](void *dst, const void *src, size_t bytes) {
-      return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st);
-    };
-    CHK(cp(frames->payload_off + nf0, dfr.payload_off, ncopy * 8));
-    CHK(cp(frames->payload_len + nf0, dfr.payload_len, ncopy * 4));
-    CHK(cp(frames->type + nf0, dfr.type, ncopy));
-    CHK(cp(cols->key_off + nf0, dco.key_off, ncopy * 4));
-    CHK(cp(cols->key_len + nf0, dco.key_len, ncopy * 4));
-    CHK(cp(cols->subset_off + nf0, dco.subset_off, ncopy * 4));
-    CHK(cp(cols->subset_len + nf0, dco.subset_len, ncopy * 4));
-    CHK(cp(cols->value_off + nf0, dco.value_off, ncopy * 4));
-    CHK(cp(cols->value_len + nf0, dco.value_len, ncopy * 4));
-    CHK(cp(cols->change + nf0, dco.change, ncopy * 8));
-    CHK(cp(cols->from + nf0, dco.from, ncopy * 8));
-    CHK(cp(cols->to + nf0, dco.to, ncopy * 8));
-    CHK(cp(cols->flags + nf0, dco.flags, ncopy));
-    CHK(hipStreamSynchronize(st));
-  }
-  *n_frames = nf0 + nf;
-  if (r.err_code) {
-    *err_frame = nf0 + r.err_frame;
-    *err_code = r.err_code;
-    *err_detail = r.err_detail;
-  }
-  carry->blob_remaining = r.blob_remaining;
-  carry->consumed = r.consumed;
-  carry->tail_kind = r.tail_kind;
-  carry->frame_bytes = r.tail_kind == DRP_TAIL_CHANGE ? r.tail_frame_bytes : 0;
+  *n_frames = nf0 + r.frames;
+  finish(r, nf0, 0, n, carry, err_frame, err_code, err_detail);
   return rc;
 }
-
 
 constexpr uint64_t kPieceMin = 64 << 10;     // bytes of a blob-skipping piece, at least
 constexpr uint64_t kPieceMargin = 64 << 10;  // past the predicted next blob header
@@ -1069,22 +1068,9 @@ static int fetch_staged(drp_ctx *c, const drp_frames *frames, const drp_changes 
 // writes from row 0)
 static int fetch_staged_at(drp_ctx *c, const drp_frames *frames, const drp_changes *cols, uint64_t first,
                            uint64_t rows) {
-  drp_frames f = *frames;
-  drp_changes o = *cols;
-  f.payload_off += first;
-  f.payload_len += first;
-  f.type += first;
-  o.key_off += first;
-  o.key_len += first;
-  o.subset_off += first;
-  o.subset_len += first;
-  o.value_off += first;
-  o.value_len += first;
-  o.change += first;
-  o.from += first;
-  o.to += first;
-  o.flags += first;
-  if (o.key_hash) o.key_hash += first;
+  drp_frames f;
+  drp_changes o;
+  rows_at(*frames, *cols, first, f, o);
   return fetch_staged(c, &f, &o, first, rows);
 }
 
@@ -1098,23 +1084,19 @@ struct FetchCol {
   uint32_t w;
 };
 static int fetch_cols(const drp_ctx *c, const drp_frames *F, const drp_changes *O, FetchCol *col) {
-  const auto &S = c->staged;
-  const void *src[14] = {S.fr.payload_off, S.fr.payload_len, S.fr.type, S.co.key_off, S.co.key_len,
-                         S.co.subset_off, S.co.subset_len, S.co.value_off, S.co.value_len, S.co.change,
-                         S.co.from, S.co.to, S.co.flags, S.co.key_hash};
-  void *dst[14] = {F->payload_off, F->payload_len, F->type, O->key_off, O->key_len, O->subset_off, O->subset_len,
-                   O->value_off, O->value_len, O->change, O->from, O->to, O->flags, O->key_hash};
-  static const uint32_t W[14] = {8, 4, 1, 4, 4, 4, 4, 4, 4, 8, 8, 8, 1, 8};
+  void *src[DRP_FETCH_COLS], *dst[DRP_FETCH_COLS];
+  col_ptrs(c->staged.fr, c->staged.co, src);
+  col_ptrs(*F, *O, dst);
   int n = 0;
-  for (int k = 0; k < 14; k++)
-    if (src[k] && dst[k]) col[n++] = {src[k], dst[k], W[k]};
+  for (int k = 0; k < DRP_FETCH_COLS; k++)
+    if (src[k] && dst[k]) col[n++] = {src[k], dst[k], kColW[k]};
   return n;
 }
 constexpr uint64_t kBounceRows = 1 << 20;  // rows per bounce round (14 columns: <= 112 MiB pinned)
-static uint64_t fetch_bounce_bytes(uint64_t ng) { return 14 * al(std::min(ng, kBounceRows) * 8); }
+static uint64_t fetch_bounce_bytes(uint64_t ng) { return DRP_FETCH_COLS * al(std::min(ng, kBounceRows) * 8); }
 static int fetch_bounce(drp_ctx *c, uint64_t dst, uint64_t g0, uint64_t ng) {
   if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
-  FetchCol col[14];
+  FetchCol col[DRP_FETCH_COLS];
   const int n = fetch_cols(c, c->dfr, c->dco, col);
   uint8_t *b = static_cast<uint8_t *>(c->fbounce.p);
   CHK(hipStreamWaitEvent(c->fst, c->fev, 0));
@@ -1129,13 +1111,7 @@ static int fetch_bounce(drp_ctx *c, uint64_t dst, uint64_t g0, uint64_t ng) {
     for (int k = 0; k < n; o += al(m * col[k].w), k++)
       memcpy(static_cast<uint8_t *>(col[k].dst) + (dst + r) * col[k].w, b + o, m * col[k].w);
   }
-  const auto &S = c->staged;
-  for (size_t k = 0; k < S.pieces.size(); k++) {
-    const uint64_t r0 = S.pieces[k].first, r1 = k + 1 < S.pieces.size() ? S.pieces[k + 1].first : ~0ull;
-    const uint64_t sh = S.pieces[k].second, lo = std::max(r0, g0), hi = std::min(r1, g0 + ng);
-    if (sh)
-      for (uint64_t g = lo; g < hi; g++) c->dfr->payload_off[dst + (g - g0)] += sh;
-  }
+  shift_pieces(c->staged, g0, ng, c->dfr->payload_off + dst, false);
   return DRP_OK;
 }
 
@@ -1167,12 +1143,8 @@ static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, d
     }
   } drain{c, pend};
   auto &S = c->staged;
-  const size_t stage_meta = 256;
-  if (!c->aux.ensure(stage_meta + sizeof(drp_stream_result) + 64)) return DRP_E_NOMEM;
-  uint64_t *soff = c->aux.at<uint64_t>(0);
-  uint64_t *ent = c->aux.at<uint64_t>(16);
-  drp_stream_result *dres = c->aux.at<drp_stream_result>(stage_meta);
-  uint64_t *dboff = c->aux.at<uint64_t>(stage_meta + sizeof(drp_stream_result));
+  StageAux A;
+  if (!stage_aux(c, A)) return DRP_E_NOMEM;
   const uint64_t n = H.n;
   uint64_t copied = 0;
   const uint64_t cap = stage_cap(c, n - pos);
@@ -1189,7 +1161,7 @@ static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, d
   if (c->key_post != DRP_KEY_POST_HASH) S.co.key_hash = nullptr;
   S.cap = cap;
   S.pieces.clear();
-  uint64_t rows = 0, staged = 0, skipped = 0;
+  uint64_t rows = 0, bad = 0, staged = 0, skipped = 0;  // (bad: a failing Change's row, kept behind the frames)
   // the next piece: kPieceMargin past where the last blob seen suggests the next blob header is;
   // doubled within this batch after each piece that met no blob
   uint64_t want = std::max(kPieceMin, c->blob_run + kPieceMargin);
@@ -1249,7 +1221,7 @@ static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, d
       dp = c->in_stage.at<uint8_t>(ps - base0);
       CHK(hipStreamWaitEvent(st, c->pev[pk], 0));
       pk++;
-      hipLaunchKernelGGL(piece_meta_kernel, dim3(1), dim3(1), 0, st, soff, ent, mp, pos - ps);
+      hipLaunchKernelGGL(piece_meta_kernel, dim3(1), dim3(1), 0, st, A.soff, A.ent, mp, pos - ps);
       CHK(hipGetLastError());
     } else {
       pe = std::min(n, pos + want);
@@ -1258,7 +1230,7 @@ static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, d
       dp = c->in_stage.at<uint8_t>(ps - base0);
       CHK(hipEventRecord(c->hev[0], st));
       if (const int rc = h2d_range(c, H, ps, mp, c->in_stage.at<uint8_t>(ps - base0), st, &copied)) return rc;
-      hipLaunchKernelGGL(piece_meta_kernel, dim3(1), dim3(1), 0, st, soff, ent, mp, pos - ps);
+      hipLaunchKernelGGL(piece_meta_kernel, dim3(1), dim3(1), 0, st, A.soff, A.ent, mp, pos - ps);
       CHK(hipGetLastError());
       CHK(hipEventRecord(c->hev[1], st));
       staged += mp;
@@ -1266,21 +1238,8 @@ static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, d
     npieces++;
     drp_frames fr;
     drp_changes co;
-    fr.payload_off = S.fr.payload_off + rows;
-    fr.payload_len = S.fr.payload_len + rows;
-    fr.type = S.fr.type + rows;
-    co.key_off = S.co.key_off + rows;
-    co.key_len = S.co.key_len + rows;
-    co.subset_off = S.co.subset_off + rows;
-    co.subset_len = S.co.subset_len + rows;
-    co.value_off = S.co.value_off + rows;
-    co.value_len = S.co.value_len + rows;
-    co.change = S.co.change + rows;
-    co.from = S.co.from + rows;
-    co.to = S.co.to + rows;
-    co.flags = S.co.flags + rows;
-    co.key_hash = S.co.key_hash ? S.co.key_hash + rows : nullptr;
-    const int rc = run_decode(c, dp, mp, soff, ent, 1, &fr, &co, cap - rows, dres);
+    rows_at(S.fr, S.co, rows, fr, co);
+    const int rc = run_decode(c, dp, mp, A.soff, A.ent, 1, &fr, &co, cap - rows, A.dres);
     if (rc == DRP_E_CAPACITY) return DRP_E_RETRY;
     if (rc != DRP_OK) return rc;
     // (run_decode describes one launch sequence: the call's timing is the sum over its pieces)
@@ -1291,9 +1250,9 @@ static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, d
     sum.exact_retries += c->timing.exact_retries;
     sum.verify_relisted += c->timing.verify_relisted;
     sum.seg_repairs += c->timing.seg_repairs;
-    hipLaunchKernelGGL(piece_tail_kernel, dim3(1), dim3(1), 0, st, dres, fr.payload_off, dboff);
+    hipLaunchKernelGGL(piece_tail_kernel, dim3(1), dim3(1), 0, st, A.dres, fr.payload_off, A.dboff);
     CHK(hipGetLastError());
-    CHK(hipMemcpyAsync(&hr, dres, sizeof(hr), hipMemcpyDeviceToHost, st));
+    CHK(hipMemcpyAsync(&hr, A.dres, sizeof(hr), hipMemcpyDeviceToHost, st));
     {
       const double t0 = now_ms();
       CHK(hipStreamSynchronize(st));
@@ -1301,7 +1260,7 @@ static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, d
     }
     const uint64_t boff = hr.boff;
     if (pipe) {  // the pipelined range is one piece: its rows' payload offsets from pbase
-      const uint64_t nr = r.frames + ((r.err_code == DRP_ERR_CHANGE || r.err_code == DRP_ERR_REQUIRED) ? 1 : 0);
+      const uint64_t nr = kept_rows(r);
       if (nr && ps > pbase) {
         const uint32_t g = (uint32_t)std::min<uint64_t>((nr + 255) / 256, 1024);
         hipLaunchKernelGGL(piece_shift_kernel, dim3(g), dim3(256), 0, st, fr.payload_off, nr, ps - pbase);
@@ -1314,18 +1273,10 @@ static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, d
       S.pieces.emplace_back(rows, ps);
       S.dev = dp;
     }
-    const uint64_t bad = (r.err_code == DRP_ERR_CHANGE || r.err_code == DRP_ERR_REQUIRED) ? 1 : 0;
     if (r.err_code || pe == n) {  // the batch's end or its error: this piece's tail is the batch's
-      if (r.err_code) {
-        *err_frame = S.nf0 + rows + r.err_frame;
-        *err_code = r.err_code;
-        *err_detail = r.err_detail;
-      }
-      rows += r.frames + bad;
-      carry->blob_remaining = r.blob_remaining;
-      carry->consumed = r.err_code ? n : r.consumed + ps;  // (an error ends the stream: nothing carried)
-      carry->tail_kind = r.tail_kind;
-      carry->frame_bytes = r.tail_kind == DRP_TAIL_CHANGE ? r.tail_frame_bytes : 0;
+      finish(r, S.nf0 + rows, ps, n, carry, err_frame, err_code, err_detail);
+      rows += kept_rows(r);
+      bad = kept_rows(r) - r.frames;
       break;
     }
     rows += r.frames;
@@ -1367,9 +1318,7 @@ static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, d
         if (fetch_rc) return fetch_rc;
         uint64_t a = c->dfetched;
         if (a == 0 && S.nf0) {  // (the carried blob's row, built on the host)
-          c->dfr->payload_off[0] = S.off0;
-          c->dfr->payload_len[0] = S.len0;
-          c->dfr->type[0] = S.ty0;
+          put_row0(S.row0, *c->dfr);
           a = 1;
         }
         if (upto > a) {
@@ -1409,7 +1358,7 @@ static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, d
   c->blob_heavy = (skipped + jumped) * 4 >= n;  // (AUTO: keep skipping while it pays)
   c->frames_per_byte = (double)rows / (double)(n - S.pieces[0].second);
   S.rows = S.nf0 + rows;
-  *n_frames = S.nf0 + rows - ((*err_code == DRP_ERR_CHANGE || *err_code == DRP_ERR_REQUIRED) ? 1 : 0);
+  *n_frames = S.nf0 + rows - bad;
   S.good = *n_frames - S.nf0;
   return DRP_OK;
 }
@@ -1417,8 +1366,8 @@ static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, d
 // Decode a host batch (bytes [a, n), a = the 16-byte-aligned start of the bytes after a leading
 // blob continuation) into the ctx's device columns. The frame capacity starts at a guess and is
 // grown to the exact count when the first launch overflows it (the count is exact either way).
-static int stage_decode(drp_ctx *c, const HostSrc &H, drp_carry *carry, uint64_t *n_frames,
-                        uint64_t *err_frame, uint32_t *err_code, uint32_t *err_detail) {
+static int stage_batch(drp_ctx *c, const HostSrc &H, drp_carry *carry, uint64_t *n_frames,
+                       uint64_t *err_frame, uint32_t *err_code, uint32_t *err_detail) {
   hipStream_t st = c->st;
   const uint64_t n = H.n;
   const uint8_t *bytes = H.flat;
@@ -1435,17 +1384,9 @@ static int stage_decode(drp_ctx *c, const HostSrc &H, drp_carry *carry, uint64_t
   c->timing.h2d_skipped = 0;
   c->timing.host_copied = 0;
   const uint64_t brem = carry->blob_remaining;
-  // A blob continuation (decode.js _id == 2 with _missing > 0 across _write calls) is row 0.
   if (brem) {
     S.nf0 = 1;
-    S.off0 = 0;
-    S.len0 = brem > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)brem;
-    S.ty0 = DRP_TYPE_BLOB | DRP_FRAME_CONT | (brem > n ? DRP_FRAME_PARTIAL : 0);
-    if (brem >= n) {
-      carry->blob_remaining = brem - n;
-      carry->consumed = n;
-      carry->tail_kind = carry->blob_remaining ? DRP_TAIL_BLOB : DRP_TAIL_NONE;
-      *n_frames = 1;
+    if (carried_blob(brem, n, S.row0, carry, n_frames)) {
       S.rows = 1;
       return DRP_OK;
     }
@@ -1487,15 +1428,11 @@ static int stage_decode(drp_ctx *c, const HostSrc &H, drp_carry *carry, uint64_t
     h2d_ms = (float)(now_ms() - t0);
     dbytes = (const uint8_t *)c->in_stage.p;
   }
-  const size_t stage_meta = 256;
-  if (!c->aux.ensure(stage_meta + sizeof(drp_stream_result) + 64)) return DRP_E_NOMEM;
-  uint64_t *soff = c->aux.at<uint64_t>(0);
-  uint64_t *ent = c->aux.at<uint64_t>(16);
-  uint64_t *bsum = c->aux.at<uint64_t>(24);
-  drp_stream_result *dres = c->aux.at<drp_stream_result>(stage_meta);
+  StageAux A;
+  if (!stage_aux(c, A)) return DRP_E_NOMEM;
   uint64_t hv[3] = {0, m, brem - a};
-  CHK(hipMemcpyAsync(soff, hv, 16, hipMemcpyHostToDevice, st));
-  CHK(hipMemcpyAsync(ent, hv + 2, 8, hipMemcpyHostToDevice, st));
+  CHK(hipMemcpyAsync(A.soff, hv, 16, hipMemcpyHostToDevice, st));
+  CHK(hipMemcpyAsync(A.ent, hv + 2, 8, hipMemcpyHostToDevice, st));
   uint64_t cap = stage_cap(c, m);
   drp_stream_result r;
   int rc = DRP_OK;
@@ -1504,9 +1441,9 @@ static int stage_decode(drp_ctx *c, const HostSrc &H, drp_carry *carry, uint64_t
     carve(c->dec_cols, cap, S.fr, S.co);
     if (c->key_post != DRP_KEY_POST_HASH) S.co.key_hash = nullptr;
     S.cap = cap;
-    rc = run_decode(c, dbytes, m, soff, ent, 1, &S.fr, &S.co, cap, dres);
+    rc = run_decode(c, dbytes, m, A.soff, A.ent, 1, &S.fr, &S.co, cap, A.dres);
     if (rc != DRP_OK && rc != DRP_E_CAPACITY) return rc;
-    CHK(hipMemcpyAsync(&r, dres, sizeof(r), hipMemcpyDeviceToHost, st));
+    CHK(hipMemcpyAsync(&r, A.dres, sizeof(r), hipMemcpyDeviceToHost, st));
     CHK(hipStreamSynchronize(st));
     if (rc == DRP_OK) break;
     // The chain held more frames than the guess. Rows needed: the delivered frames plus a
@@ -1514,7 +1451,7 @@ static int stage_decode(drp_ctx *c, const HostSrc &H, drp_carry *carry, uint64_t
     // capacity was seen, so nothing before it was missed; the frames after it are not
     // delivered). Otherwise r.frames is the exact chain count or a malformed Change past the
     // capacity ends the stream earlier: retry at that bound.
-    const uint64_t need = r.frames + ((r.err_code == DRP_ERR_CHANGE || r.err_code == DRP_ERR_REQUIRED) ? 1 : 0);
+    const uint64_t need = kept_rows(r);
     if (need <= cap) {
       rc = DRP_OK;
       break;
@@ -1525,9 +1462,9 @@ static int stage_decode(drp_ctx *c, const HostSrc &H, drp_carry *carry, uint64_t
   if (host_in && c->blob_skip == DRP_BLOB_SKIP_AUTO && r.blobs) {
     // the batch's blob payload bytes: mostly blobs -> the next batches are staged in pieces
     uint64_t bb = 0;
-    CHK(hipMemsetAsync(bsum, 0, 8, st));
-    CHK(drp_launch_blob_bytes(S.fr.type, S.fr.payload_len, r.frames, bsum, st));
-    CHK(hipMemcpyAsync(&bb, bsum, 8, hipMemcpyDeviceToHost, st));
+    CHK(hipMemsetAsync(A.bsum, 0, 8, st));
+    CHK(drp_launch_blob_bytes(S.fr.type, S.fr.payload_len, r.frames, A.bsum, st));
+    CHK(hipMemcpyAsync(&bb, A.bsum, 8, hipMemcpyDeviceToHost, st));
     CHK(hipStreamSynchronize(st));
     c->blob_heavy = bb * 2 >= m;
   } else if (host_in) {
@@ -1537,25 +1474,27 @@ static int stage_decode(drp_ctx *c, const HostSrc &H, drp_carry *carry, uint64_t
   c->timing.h2d_bytes = host_in ? m : 0;
   c->timing.host_copied = copied;
   c->frames_per_byte = m ? (double)r.frames / (double)m : 0.0;
-  const uint64_t bad = (r.err_code == DRP_ERR_CHANGE || r.err_code == DRP_ERR_REQUIRED) ? 1 : 0;
   S.pieces.emplace_back(0, a);
   S.dev = dbytes;
   S.wire = dbytes;
   S.wire_bytes = m;
   S.base = a;
   S.good = r.frames;
-  S.rows = S.nf0 + r.frames + bad;
+  S.rows = S.nf0 + kept_rows(r);
   *n_frames = S.nf0 + r.frames;
-  if (r.err_code) {
-    *err_frame = S.nf0 + r.err_frame;
-    *err_code = r.err_code;
-    *err_detail = r.err_detail;
-  }
-  carry->blob_remaining = r.blob_remaining;
-  carry->consumed = r.consumed + a;
-  carry->tail_kind = r.tail_kind;
-  carry->frame_bytes = r.tail_kind == DRP_TAIL_CHANGE ? r.tail_frame_bytes : 0;
+  finish(r, S.nf0, a, n, carry, err_frame, err_code, err_detail);
   return DRP_OK;
+}
+
+// A staged decode of a host batch, whole or in pieces: the batch the fetch and relay calls serve
+// from now on (staged.seq), held (staged.valid) when the decode succeeded.
+static int stage_decode(drp_ctx *c, const HostSrc &H, drp_carry *carry, uint64_t *n_frames,
+                        uint64_t *err_frame, uint32_t *err_code, uint32_t *err_detail) {
+  c->staged.valid = false;
+  c->staged.seq++;
+  const int rc = stage_batch(c, H, carry, n_frames, err_frame, err_code, err_detail);
+  c->staged.valid = rc == DRP_OK;
+  return rc;
 }
 
 // Copy staged rows [first, first + rows) into host columns.
@@ -1567,44 +1506,27 @@ static int fetch_staged(drp_ctx *c, const drp_frames *frames, const drp_changes 
   hipStream_t st = c->st;
   uint64_t dst = 0;  // destination row
   if (first == 0 && S.nf0) {
-    frames->payload_off[0] = S.off0;
-    frames->payload_len[0] = S.len0;
-    frames->type[0] = S.ty0;
+    put_row0(S.row0, *frames);
     dst = 1;
   }
   const uint64_t g0 = first + dst - S.nf0;  // first GPU row
   const uint64_t ng = rows - dst;
   const double t0 = now_ms();
   if (ng) {
-    auto cp = [&](void *d, const void *s_, size_t w) {
-      return hipMemcpyAsync(static_cast<char *>(d) + dst * w, static_cast<const char *>(s_) + g0 * w, ng * w,
-                            hipMemcpyDeviceToHost, st);
-    };
-    CHK(cp(frames->payload_off, S.fr.payload_off, 8));
-    CHK(cp(frames->payload_len, S.fr.payload_len, 4));
-    CHK(cp(frames->type, S.fr.type, 1));
-    CHK(cp(cols->key_off, S.co.key_off, 4));
-    CHK(cp(cols->key_len, S.co.key_len, 4));
-    CHK(cp(cols->subset_off, S.co.subset_off, 4));
-    CHK(cp(cols->subset_len, S.co.subset_len, 4));
-    CHK(cp(cols->value_off, S.co.value_off, 4));
-    CHK(cp(cols->value_len, S.co.value_len, 4));
-    CHK(cp(cols->change, S.co.change, 8));
-    CHK(cp(cols->from, S.co.from, 8));
-    CHK(cp(cols->to, S.co.to, 8));
-    CHK(cp(cols->flags, S.co.flags, 1));
-    if (cols->key_hash) {
-      if (!S.co.key_hash) return DRP_E_INVAL;  // not computed: drp_set_key_post(ctx, 1) first
-      CHK(cp(cols->key_hash, S.co.key_hash, 8));
+    void *from[DRP_FETCH_COLS], *to[DRP_FETCH_COLS];
+    col_ptrs(S.fr, S.co, from);
+    col_ptrs(*frames, *cols, to);
+    for (int k = 0; k < DRP_FETCH_COLS; k++) {
+      if (k == kColKeyHash) {  // only when the caller asks for it
+        if (!to[k]) continue;
+        if (!from[k]) return DRP_E_INVAL;  // not computed: drp_set_key_post(ctx, 1) first
+      }
+      const size_t w = kColW[k];
+      CHK(hipMemcpyAsync(static_cast<char *>(to[k]) + dst * w, static_cast<const char *>(from[k]) + g0 * w, ng * w,
+                         hipMemcpyDeviceToHost, st));
     }
     CHK(hipStreamSynchronize(st));
-    // payload offsets relative to each piece's staging offset -> batch offsets
-    for (size_t k = 0; k < S.pieces.size(); k++) {
-      const uint64_t r0 = S.pieces[k].first, r1 = k + 1 < S.pieces.size() ? S.pieces[k + 1].first : ~0ull;
-      const uint64_t sh = S.pieces[k].second, lo = std::max(r0, g0), hi = std::min(r1, g0 + ng);
-      if (sh)
-        for (uint64_t g = lo; g < hi; g++) frames->payload_off[dst + (g - g0)] += sh;
-    }
+    shift_pieces(S, g0, ng, frames->payload_off + dst, false);
   }
   c->timing.d2h_ms = (float)(now_ms() - t0);
   return DRP_OK;
@@ -1644,10 +1566,10 @@ int drp_decode_fetch_block_ex(drp_ctx *c, void *block, uint64_t block_bytes, con
                               uint64_t rows, uint32_t flags) {
   if (!c || (!block && block_bytes) || !col_off || (flags & ~DRP_FETCH_F64)) return DRP_E_INVAL;
   const bool f64 = flags & DRP_FETCH_F64;
-  static const uint32_t W[DRP_FETCH_COLS] = {8, 4, 1, 4, 4, 4, 4, 4, 4, 8, 8, 8, 1, 8};
-  const bool kh = col_off[13] != ~0ull;
-  for (int k = 0; k < DRP_FETCH_COLS - (kh ? 0 : 1); k++)
-    if (col_off[k] > block_bytes || rows * W[k] > block_bytes - col_off[k]) return DRP_E_INVAL;
+  const bool kh = col_off[kColKeyHash] != ~0ull;
+  const int ncols = DRP_FETCH_COLS - (kh ? 0 : 1);
+  for (int k = 0; k < ncols; k++)
+    if (col_off[k] > block_bytes || rows * kColW[k] > block_bytes - col_off[k]) return DRP_E_INVAL;
   if (rows && is_device_ptr(block)) return DRP_E_INVAL;
   if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
   auto &S = c->staged;
@@ -1660,9 +1582,8 @@ int drp_decode_fetch_block_ex(drp_ctx *c, void *block, uint64_t block_bytes, con
   const uint64_t g0 = first + dst - S.nf0, ng = rows - dst;
   if (ng) {
     if (!c->fetch_tmp.ensure(block_bytes)) return DRP_E_NOMEM;
-    const void *src[DRP_FETCH_COLS] = {S.fr.payload_off, S.fr.payload_len, S.fr.type, S.co.key_off, S.co.key_len,
-                                       S.co.subset_off, S.co.subset_len, S.co.value_off, S.co.value_len,
-                                       S.co.change, S.co.from, S.co.to, S.co.flags, S.co.key_hash};
+    void *src[DRP_FETCH_COLS];
+    col_ptrs(S.fr, S.co, src);
     if (f64) {  // the four u64 columns as doubles, converted into the space after the packed block
       if (!c->fetch_tmp.ensure(block_bytes + 4 * ng * 8 + 256)) return DRP_E_NOMEM;
       double *cv = reinterpret_cast<double *>(static_cast<uint8_t *>(c->fetch_tmp.p) + ((block_bytes + 255) & ~255ull));
@@ -1676,11 +1597,11 @@ int drp_decode_fetch_block_ex(drp_ctx *c, void *block, uint64_t block_bytes, con
     }
     PackSegs P = {};
     uint64_t total = 0;
-    for (int k = 0; k < DRP_FETCH_COLS - (kh ? 0 : 1); k++) {
-      P.src[P.n] = static_cast<const uint8_t *>(src[k]) + g0 * W[k];
-      P.dst[P.n] = col_off[k] + dst * W[k];
-      P.bytes[P.n] = ng * W[k];
-      total += ng * W[k];
+    for (int k = 0; k < ncols; k++) {
+      P.src[P.n] = static_cast<const uint8_t *>(src[k]) + g0 * kColW[k];
+      P.dst[P.n] = col_off[k] + dst * kColW[k];
+      P.bytes[P.n] = ng * kColW[k];
+      total += ng * kColW[k];
       P.n++;
     }
     const uint64_t threads = (total + 15) / 16;
@@ -1689,23 +1610,13 @@ int drp_decode_fetch_block_ex(drp_ctx *c, void *block, uint64_t block_bytes, con
     CHK(hipGetLastError());
     CHK(hipMemcpyAsync(B, c->fetch_tmp.p, block_bytes, hipMemcpyDeviceToHost, c->st));
     CHK(hipStreamSynchronize(c->st));
-    uint64_t *poff = reinterpret_cast<uint64_t *>(B + col_off[0]);
-    double *poffd = reinterpret_cast<double *>(B + col_off[0]);
-    for (size_t k = 0; k < S.pieces.size(); k++) {  // (as fetch_staged: piece offsets -> batch offsets)
-      const uint64_t r0 = S.pieces[k].first, r1 = k + 1 < S.pieces.size() ? S.pieces[k + 1].first : ~0ull;
-      const uint64_t sh = S.pieces[k].second, lo = std::max(r0, g0), hi = std::min(r1, g0 + ng);
-      if (sh && f64)
-        for (uint64_t g = lo; g < hi; g++) poffd[dst + (g - g0)] += (double)sh;  // (exact below 2^53)
-      else if (sh)
-        for (uint64_t g = lo; g < hi; g++) poff[dst + (g - g0)] += sh;
-    }
+    shift_pieces(S, g0, ng, B + col_off[kColPayloadOff] + dst * 8, f64);
   }
   if (dst) {  // (the other columns of that row are zero)
-    for (int k = 3; k < DRP_FETCH_COLS - (kh ? 0 : 1); k++) memset(B + col_off[k], 0, W[k]);
-    if (f64) reinterpret_cast<double *>(B + col_off[0])[0] = (double)S.off0;
-    else reinterpret_cast<uint64_t *>(B + col_off[0])[0] = S.off0;
-    reinterpret_cast<uint32_t *>(B + col_off[1])[0] = S.len0;
-    B[col_off[2]] = S.ty0;
+    for (int k = 3; k < ncols; k++) memset(B + col_off[k], 0, kColW[k]);
+    put_row0(S.row0, {reinterpret_cast<uint64_t *>(B + col_off[0]), reinterpret_cast<uint32_t *>(B + col_off[1]),
+                      B + col_off[2]});
+    if (f64) reinterpret_cast<double *>(B + col_off[0])[0] = (double)S.row0.off;
   }
   c->timing.d2h_ms = (float)(now_ms() - t0);
   return DRP_OK;
@@ -1792,11 +1703,7 @@ int drp_decode_stage(drp_ctx *c, const uint8_t *bytes, uint64_t n, drp_carry *ca
   HostSrc H;
   H.flat = bytes;
   H.n = n;
-  c->staged.valid = false;
-  c->staged.seq++;
-  const int rc = stage_decode(c, H, carry, n_frames, err_frame, err_code, err_detail);
-  c->staged.valid = rc == DRP_OK;
-  return rc;
+  return stage_decode(c, H, carry, n_frames, err_frame, err_code, err_detail);
 }
 
 int drp_decode_stage_v(drp_ctx *c, const drp_chunk *chunks, uint64_t nchunks, drp_carry *carry, uint64_t *n_frames,
@@ -1815,12 +1722,8 @@ int drp_decode_stage_v(drp_ctx *c, const drp_chunk *chunks, uint64_t nchunks, dr
     H.ch = nullptr;
   }
   if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
-  c->staged.valid = false;
-  c->staged.seq++;
   HostSrc E;
-  const int rc = stage_decode(c, H.n ? H : E, carry, n_frames, err_frame, err_code, err_detail);
-  c->staged.valid = rc == DRP_OK;
-  return rc;
+  return stage_decode(c, H.n ? H : E, carry, n_frames, err_frame, err_code, err_detail);
 }
 
 int drp_decode_fetch(drp_ctx *c, const drp_frames *frames, const drp_changes *cols, uint64_t first, uint64_t rows) {
@@ -1848,10 +1751,7 @@ int drp_decode_batch(drp_ctx *c, const uint8_t *bytes, uint64_t n, drp_carry *ca
   c->dco = cols;
   c->dcap = cap;
   c->dfetched = 0;
-  c->staged.valid = false;
-  c->staged.seq++;
   int rc = stage_decode(c, H, carry, n_frames, err_frame, err_code, err_detail);
-  c->staged.valid = rc == DRP_OK;
   c->dfr = nullptr;
   c->dco = nullptr;
   c->key_post = key_post;

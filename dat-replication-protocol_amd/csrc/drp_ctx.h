@@ -185,9 +185,11 @@ struct drp_ctx {
     uint64_t wire_bytes = 0, base = 0, good = 0;
     bool valid = false;
     uint64_t seq = 0;  // counts the stage calls: what was derived from an earlier batch is told apart
-    uint64_t off0 = 0;
-    uint32_t len0 = 0;
-    uint8_t ty0 = 0;
+    struct Row0 {  // the continuation's row (nf0 == 1)
+      uint64_t off = 0;
+      uint32_t len = 0;
+      uint8_t type = 0;
+    } row0;
     drp_frames fr = {};
     drp_changes co = {};
   } staged;

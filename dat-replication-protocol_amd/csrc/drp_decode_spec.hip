@@ -3962,21 +3962,11 @@ extern "C" hipError_t drp_launch_spec_head(const DecodeParams *P, uint64_t nt_ma
       fclose(f);
     }
   }
-  if (Q.vlist) {  // records-only verification, then verify_counts on the tiles it lists
-    const uint64_t nb = (nt_max * spec::VL_G + spec::VL_BLK - 1) / spec::VL_BLK;
-    hipLaunchKernelGGL(spec::verify_lite, dim3((uint32_t)nb), dim3(spec::VL_BLK), 0, st, Q);
-    drp_dbg_mark("verify_lite", st);
-    hipLaunchKernelGGL(spec::verify_counts, dim3((uint32_t)(nt_max < 16384 ? nt_max : 16384)), dim3(spec::NT), 0, st,
-                       Q);
-    drp_dbg_mark("verify_counts", st);
-  } else {
-    hipLaunchKernelGGL(spec::verify_counts, dim3((uint32_t)nt_max), dim3(spec::NT), 0, st, Q);
-    drp_dbg_mark("verify_counts", st);
-  }
-  return hipGetLastError();
+  return drp_launch_spec_verify(&Q, nt_max, nstreams, tile_stream, st);  // (sets the same Q.tile_stream)
 }
 
-// One more verify pass over the repaired claims (the caller clears incl_e and the flags first).
+// A verify pass over every tile: the head's, and one more over the repaired claims (the caller
+// clears incl_e and the flags first).
 extern "C" hipError_t drp_launch_spec_verify(const DecodeParams *P, uint64_t nt_max, uint64_t nstreams,
                                              uint32_t *tile_stream, hipStream_t st) {
   if (nt_max == 0) return hipSuccess;
