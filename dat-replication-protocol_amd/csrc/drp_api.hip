@@ -613,7 +613,7 @@ int run_decode_spec(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const uin
   }
   // claims_fast's per-frame records (fast_records, 20 B per frame slot): emit_lean expands them into
   // columns without reading the wire again (DRP_CREC=0: off; a buffer that cannot be had: off)
-  const uint64_t rec_bytes = (NT * drp_spec_rec_words() * 4ull + 255) & ~255ull;
+  const uint64_t rec_bytes = al(NT * drp_spec_rec_words() * 4ull);
   if (c->crec && c->recbuf.ensure(rec_bytes + (cap / 64 + 2) * 4)) {
     P.rec = c->recbuf.at<uint32_t>(0);
     P.chunk_tile = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(c->recbuf.p) + rec_bytes);
@@ -1586,7 +1586,7 @@ int drp_decode_fetch_block_ex(drp_ctx *c, void *block, uint64_t block_bytes, con
     col_ptrs(S.fr, S.co, src);
     if (f64) {  // the four u64 columns as doubles, converted into the space after the packed block
       if (!c->fetch_tmp.ensure(block_bytes + 4 * ng * 8 + 256)) return DRP_E_NOMEM;
-      double *cv = reinterpret_cast<double *>(static_cast<uint8_t *>(c->fetch_tmp.p) + ((block_bytes + 255) & ~255ull));
+      double *cv = reinterpret_cast<double *>(static_cast<uint8_t *>(c->fetch_tmp.p) + al(block_bytes));
       const int ks[4] = {0, 9, 10, 11};
       const uint32_t grid = (uint32_t)std::min<uint64_t>((ng + 255) / 256, 4096);
       for (int q = 0; q < 4; q++) {

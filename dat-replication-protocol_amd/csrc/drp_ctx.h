@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/drp.h"
+#include "drp_kernels.h"  // (al)
 
 namespace drp {
 
@@ -85,8 +86,6 @@ inline bool is_pinned_host(const void *p) {
   }
   return a.type == hipMemoryTypeHost;
 }
-
-inline size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace drp
 

@@ -1317,12 +1317,7 @@ __global__ __launch_bounds__(64 * WPG, DRP_MIN_WAVES) void decode_tiles(DecodePa
             const uint32_t kk = k < m ? k : m;
             if (kk == 0) { force_tile = true; continue; }
             const uint64_t c = lane < kk ? sc - 1 : 0ull;
-            uint64_t pre = c;  // inclusive prefix over lanes
-#pragma unroll
-            for (uint32_t d = 1; d < WAVE; d <<= 1) {
-              const uint64_t o = shfl_up64(pre, d);
-              if (lane >= d) pre += o;
-            }
+            const uint64_t pre = wave_incl_scan64(c);  // inclusive prefix over lanes
             if (lane < kk) st_agent(&P.inclc[SG * gk + SG - 1], v + pre + 1);
             v += readlane64(pre, kk - 1);
             cur = SG * (k0 + (int64_t)kk) - 1;

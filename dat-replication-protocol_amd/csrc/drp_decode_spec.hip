@@ -2282,26 +2282,6 @@ __global__ __launch_bounds__(NT) void verify_counts(DecodeParams P) {
 // ==== scan: tile_base = exclusive prefix of tile_count (reduce, top, down-sweep) ================
 constexpr uint32_t SCAN_BLK = 1024, SCAN_PER = 4, SCAN_SPAN = SCAN_BLK * SCAN_PER;
 
-__device__ __forceinline__ uint64_t block_excl_scan64(uint64_t v, uint64_t *sw, uint64_t &total) {
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
-  uint64_t x = v;
-#pragma unroll
-  for (uint32_t d = 1; d < WAVE; d <<= 1) {
-    const uint64_t y = shfl_up64(x, d);
-    if (lane >= d) x += y;
-  }
-  if (lane == 63) sw[wid] = x;
-  __syncthreads();
-  uint64_t off = 0;
-  total = 0;
-  for (uint32_t w = 0; w < blockDim.x / WAVE; w++) {
-    if (w < wid) off += sw[w];
-    total += sw[w];
-  }
-  __syncthreads();
-  return off + x - v;
-}
-
 __global__ __launch_bounds__(SCAN_BLK) void scan_reduce(const uint64_t *cnt, const uint64_t *tile_prefix,
                                                          uint64_t nstreams, uint64_t *bsum) {
   __shared__ uint64_t sw[SCAN_BLK / WAVE];
@@ -2311,7 +2291,7 @@ __global__ __launch_bounds__(SCAN_BLK) void scan_reduce(const uint64_t *cnt, con
   for (uint32_t k = 0; k < SCAN_PER; k++)
     if (i0 + k < nt) v += cnt[i0 + k];
   uint64_t total;
-  (void)block_excl_scan64(v, sw, total);
+  (void)block_excl_scan(v, sw, total);
   if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
 
@@ -2322,7 +2302,7 @@ __global__ __launch_bounds__(SCAN_BLK) void scan_top(uint64_t *bsum, uint64_t nb
     const uint64_t i = c0 + threadIdx.x;
     const uint64_t v = i < nb ? bsum[i] : 0;
     uint64_t total;
-    const uint64_t ex = block_excl_scan64(v, sw, total);
+    const uint64_t ex = block_excl_scan(v, sw, total);
     if (i < nb) bsum[i] = carry + ex;
     carry += total;
   }
@@ -2342,7 +2322,7 @@ __global__ __launch_bounds__(SCAN_BLK) void scan_down(const uint64_t *cnt, const
     v += c[k];
   }
   uint64_t total;
-  uint64_t o = (ONE ? 0ull : bsum[blockIdx.x]) + block_excl_scan64(v, sw, total);
+  uint64_t o = (ONE ? 0ull : bsum[blockIdx.x]) + block_excl_scan(v, sw, total);
   for (uint32_t k = 0; k < SCAN_PER; k++) {
     if (i0 + k < nt) {
       base[i0 + k] = o;
@@ -2381,8 +2361,8 @@ __global__ __launch_bounds__(SCAN_BLK) void scan_reduce2(Scan2 S) {
       w += S.nch[i0 + k];
     }
   uint64_t tv, tw;
-  (void)block_excl_scan64(v, sw, tv);
-  (void)block_excl_scan64(w, sw, tw);
+  (void)block_excl_scan(v, sw, tv);
+  (void)block_excl_scan(w, sw, tw);
   if (threadIdx.x == 0) {
     S.bsum[blockIdx.x] = tv;
     S.bsum[gridDim.x + blockIdx.x] = tw;
@@ -2399,7 +2379,7 @@ __global__ __launch_bounds__(SCAN_BLK) void scan_top2(uint64_t *bsum, uint64_t n
       const uint64_t i = c0 + threadIdx.x;
       const uint64_t v = i < nb ? b[i] : 0;
       uint64_t total;
-      const uint64_t ex = block_excl_scan64(v, sw, total);
+      const uint64_t ex = block_excl_scan(v, sw, total);
       if (i < nb) b[i] = carry + ex;
       carry += total;
     }
@@ -2420,8 +2400,8 @@ __global__ __launch_bounds__(SCAN_BLK) void scan_down2(Scan2 S) {
     w += d[k];
   }
   uint64_t total;
-  uint64_t o = (ONE ? 0ull : S.bsum[blockIdx.x]) + block_excl_scan64(v, sw, total);
-  uint64_t q = (ONE ? 0ull : S.bsum[gridDim.x + blockIdx.x]) + block_excl_scan64(w, sw, total);
+  uint64_t o = (ONE ? 0ull : S.bsum[blockIdx.x]) + block_excl_scan(v, sw, total);
+  uint64_t q = (ONE ? 0ull : S.bsum[gridDim.x + blockIdx.x]) + block_excl_scan(w, sw, total);
   const bool marks = S.rec_on && *S.rec_on;
   for (uint32_t k = 0; k < SCAN_PER; k++) {
     if (i0 + k < nt) {

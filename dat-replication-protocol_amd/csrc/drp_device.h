@@ -480,6 +480,52 @@ __device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
   return v;
 }
 
+// ---- workgroup scans ------------------------------------------------------------------
+// Every thread of the workgroup calls these (blockDim.x a multiple of 64); sw is blockDim.x / 64
+// words of the caller's LDS. A barrier follows the waves' stores to sw and a second one the last
+// read of it, so what the caller stored to LDS before the call is published by the first, and sw
+// (or LDS sharing its bytes) can be written again at once after the return.
+__device__ __forceinline__ uint32_t shfl_up(uint32_t v, uint32_t d) { return shfl_up32(v, d); }
+__device__ __forceinline__ uint64_t shfl_up(uint64_t v, uint32_t d) { return shfl_up64(v, d); }
+
+// the exclusive prefix of v over the workgroup's threads; total = the sum over all of them
+template <class T>
+__device__ __forceinline__ T block_excl_scan(T v, T *sw, T &total) {
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
+  T x = v;
+#pragma unroll
+  for (uint32_t d = 1; d < WAVE; d <<= 1) {
+    const T y = shfl_up(x, d);
+    if (lane >= d) x += y;
+  }
+  if (lane == 63) sw[wid] = x;
+  __syncthreads();
+  T off = 0;
+  total = 0;
+  for (uint32_t w = 0; w < blockDim.x / WAVE; w++) {
+    if (w < wid) off += sw[w];
+    total += sw[w];
+  }
+  __syncthreads();
+  return off + x - v;
+}
+
+// One workgroup scans n values exclusively, blockDim.x per round with the carry in a register:
+// store(i, the sum of load(0) .. load(i - 1)) for every i < n; returns the sum of all n.
+template <class Load, class Store>
+__device__ __forceinline__ uint64_t block_scan_rounds(uint64_t n, uint64_t *sw, Load load, Store store) {
+  uint64_t carry = 0;
+  for (uint64_t c0 = 0; c0 < n; c0 += blockDim.x) {
+    const uint64_t i = c0 + threadIdx.x;
+    const uint64_t v = i < n ? load(i) : 0;
+    uint64_t total;
+    const uint64_t ex = block_excl_scan(v, sw, total);
+    if (i < n) store(i, carry + ex);
+    carry += total;
+  }
+  return carry;
+}
+
 // Agent-scope relaxed atomics on 8-byte granules (the value IS the flag: guide §6 G16 R2).
 __device__ __forceinline__ uint64_t ld_agent(const uint64_t *p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

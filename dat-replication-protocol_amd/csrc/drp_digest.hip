@@ -244,19 +244,11 @@ __device__ __forceinline__ bool dig_cell2(const RefineParams &R, uint64_t ident,
 __global__ __launch_bounds__(DIG_RANK_BLK) void dig_rank_kernel(const uint64_t *set, uint32_t nwords, uint64_t mask0,
                                                                 uint32_t *rank, uint64_t *totals) {
   __shared__ uint32_t wsum[DIG_RANK_BLK / 64];
-  const uint32_t t = threadIdx.x, wave = t >> 6;
+  const uint32_t t = threadIdx.x;
   const uint32_t pc = t < nwords ? (uint32_t)__popcll(set[t] & (t ? ~0ull : mask0)) : 0u;
-  const uint32_t incl = wave_incl_scan32(pc);
-  if (lane_id() == 63) wsum[wave] = incl;
-  __syncthreads();
-  uint32_t base = 0, all = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < DIG_RANK_BLK / 64; k++) {
-    const uint32_t s = wsum[k];
-    if (k < wave) base += s;
-    all += s;
-  }
-  if (t < nwords) rank[t] = base + incl - pc;
+  uint32_t all;
+  const uint32_t before = block_excl_scan(pc, wsum, all);
+  if (t < nwords) rank[t] = before;
   if (t == 0 && totals) {
     totals[0] = 0;
     totals[1] = 0;

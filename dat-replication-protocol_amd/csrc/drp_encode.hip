@@ -49,7 +49,7 @@ __device__ __forceinline__ bool in_heap(uint64_t off, uint32_t len, uint64_t hea
 }
 
 __global__ __launch_bounds__(SCAN_BLK) void enc_size_kernel(EncodeParams P) {
-  __shared__ uint64_t part[SCAN_BLK];
+  __shared__ uint64_t part[SCAN_BLK / WAVE];
   const uint64_t i = (uint64_t)blockIdx.x * SCAN_BLK + threadIdx.x;
   uint64_t sz = 0;
   if (i < P.n) {
@@ -62,39 +62,16 @@ __global__ __launch_bounds__(SCAN_BLK) void enc_size_kernel(EncodeParams P) {
     if (fl & DRP_F_VALUE) ok = ok && in_heap(s.value_off[i], s.value_len[i], P.heap_bytes);
     if (!ok) atomicOr(P.overflow, ENC_F_RANGE);
   }
-  part[threadIdx.x] = sz;
-  __syncthreads();
-  for (uint32_t d = 1; d < SCAN_BLK; d <<= 1) {
-    uint64_t v = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-    __syncthreads();
-    part[threadIdx.x] += v;
-    __syncthreads();
-  }
-  if (i < P.n) P.frame_off[i] = part[threadIdx.x] - sz;  // block-local exclusive
-  if (threadIdx.x == SCAN_BLK - 1) P.block_sum[blockIdx.x] = part[SCAN_BLK - 1];
+  uint64_t total;
+  const uint64_t before = block_excl_scan(sz, part, total);
+  if (i < P.n) P.frame_off[i] = before;  // block-local exclusive
+  if (threadIdx.x == SCAN_BLK - 1) P.block_sum[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(SCAN_BLK) void enc_blocksum_kernel(EncodeParams P, uint64_t nblk) {
-  __shared__ uint64_t part[SCAN_BLK];
-  __shared__ uint64_t carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (uint64_t c0 = 0; c0 < nblk; c0 += SCAN_BLK) {
-    const uint64_t b = c0 + threadIdx.x;
-    const uint64_t v0 = b < nblk ? P.block_sum[b] : 0;
-    part[threadIdx.x] = v0;
-    __syncthreads();
-    for (uint32_t d = 1; d < SCAN_BLK; d <<= 1) {
-      uint64_t v = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-      __syncthreads();
-      part[threadIdx.x] += v;
-      __syncthreads();
-    }
-    if (b < nblk) P.block_sum[b] = carry + part[threadIdx.x] - v0;
-    __syncthreads();
-    if (threadIdx.x == SCAN_BLK - 1) carry += part[SCAN_BLK - 1];
-    __syncthreads();
-  }
+  __shared__ uint64_t part[SCAN_BLK / WAVE];
+  const uint64_t carry = block_scan_rounds(
+      nblk, part, [&](uint64_t b) { return P.block_sum[b]; }, [&](uint64_t b, uint64_t ex) { P.block_sum[b] = ex; });
   if (threadIdx.x == 0) {
     // a row outside the heap poisons the total (UINT64_MAX > any cap): nothing is written
     const bool range_bad = (__hip_atomic_load(P.overflow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & ENC_F_RANGE) != 0;
@@ -572,26 +549,9 @@ __global__ __launch_bounds__(256) void enc_write_dense(EncodeParams P) {
 // exclusive prefix of stats[i].frames (single block)
 __global__ __launch_bounds__(1024) void index_scan_kernel(const drp_stream_stats *stats, uint64_t count,
                                                           uint64_t *base) {
-  __shared__ uint64_t part[1024];
-  __shared__ uint64_t carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (uint64_t c0 = 0; c0 < count; c0 += 1024) {
-    const uint64_t i = c0 + threadIdx.x;
-    const uint64_t v0 = i < count ? stats[i].frames : 0;
-    part[threadIdx.x] = v0;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024; d <<= 1) {
-      uint64_t v = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-      __syncthreads();
-      part[threadIdx.x] += v;
-      __syncthreads();
-    }
-    if (i < count) base[i] = carry + part[threadIdx.x] - v0;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry += part[1023];
-    __syncthreads();
-  }
+  __shared__ uint64_t part[1024 / WAVE];
+  (void)block_scan_rounds(
+      count, part, [&](uint64_t i) { return stats[i].frames; }, [&](uint64_t i, uint64_t ex) { base[i] = ex; });
 }
 
 __global__ void stats_kernel(const drp_stream_result *res, const uint64_t *stream_off, uint64_t n,

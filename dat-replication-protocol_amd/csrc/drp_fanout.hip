@@ -91,23 +91,12 @@ __global__ __launch_bounds__(FAN_BLK) void fan_count_kernel(const FanParams P) {
   }
 }
 
-// the sum of a value over the workgroup (every thread gets it); ws: FAN_WAVES words of LDS
-__device__ __forceinline__ uint64_t fan_block_sum(uint64_t v, uint64_t *ws) {
-  const uint64_t s = wave_sum64(v);
-  __syncthreads();  // (ws may still be read from an earlier use)
-  if (lane_id() == 0) ws[threadIdx.x >> 6] = s;
-  __syncthreads();
-  uint64_t t = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < FAN_WAVES; k++) t += ws[k];
-  return t;
-}
-
 // (2a) the sum of every FAN_SCAN counts
 __global__ __launch_bounds__(FAN_SCAN) void fan_blocksum_kernel(const uint64_t *cnt, uint64_t m, uint64_t *bsum) {
-  __shared__ uint64_t ws[FAN_WAVES];
+  __shared__ uint64_t sw[FAN_SCAN / WAVE];
   const uint64_t g = (uint64_t)blockIdx.x * FAN_SCAN + threadIdx.x;
-  const uint64_t t = fan_block_sum(g < m ? cnt[g] : 0, ws);
+  uint64_t t;
+  (void)block_excl_scan<uint64_t>(g < m ? cnt[g] : 0, sw, t);
   if (threadIdx.x == 0) bsum[blockIdx.x] = t;
 }
 
@@ -115,18 +104,14 @@ __global__ __launch_bounds__(FAN_SCAN) void fan_blocksum_kernel(const uint64_t *
 // block sums before it (at most blockIdx.x / FAN_SCAN rounds), then a scan within the block. The
 // value at [f][0] is row_base[f]; the total past the last count (rows and blob rows) is *gtotal.
 __global__ __launch_bounds__(FAN_SCAN) void fan_scanbase_kernel(const FanParams P, uint64_t m) {
-  __shared__ uint64_t ws[FAN_WAVES], part[FAN_WAVES];
+  __shared__ uint64_t sw[FAN_SCAN / WAVE];
   uint64_t acc = 0;
   for (uint32_t k = threadIdx.x; k < blockIdx.x; k += FAN_SCAN) acc += P.bsum[k];
-  const uint64_t base = fan_block_sum(acc, ws);
+  uint64_t base, total;
+  (void)block_excl_scan(acc, sw, base);
   const uint64_t g = (uint64_t)blockIdx.x * FAN_SCAN + threadIdx.x;
   const uint64_t v = g < m ? P.block_cnt[g] : 0;
-  const uint64_t incl = wave_incl_scan64(v);
-  const uint32_t wv = threadIdx.x >> 6;
-  if (lane_id() == 63) part[wv] = incl;
-  __syncthreads();
-  uint64_t excl = base + incl - v;
-  for (uint32_t k = 0; k < wv; k++) excl += part[k];
+  const uint64_t excl = base + block_excl_scan(v, sw, total);
   if (g < m) {
     P.block_cnt[g] = excl;
     if (g % P.nwg == 0) {
@@ -222,7 +207,6 @@ __global__ __launch_bounds__(256) void fan_gather_kernel(const uint64_t *frame_o
 
 using namespace drp;
 
-static uint64_t fan_al(uint64_t x) { return (x + 255) & ~255ull; }
 static uint64_t fan_nwg(uint64_t n) { return (n + FAN_ROWS - 1) / FAN_ROWS; }
 
 namespace {
@@ -231,11 +215,11 @@ struct FanLayout {
   FanLayout(uint64_t n, uint32_t K) {
     const uint64_t nwg = fan_nwg(n), planes = (uint64_t)K + 1, m = planes * nwg;
     filt = 0;
-    fbytes = fan_al((uint64_t)K * sizeof(RowFilter));
+    fbytes = al((uint64_t)K * sizeof(RowFilter));
     mask = fbytes + (uint64_t)K * FAN_FBYTES;
-    cnt = mask + fan_al(planes * nwg * FAN_CHUNKS * 8);
-    bsum = cnt + fan_al(m * 8);
-    tot = bsum + fan_al(((m + FAN_SCAN - 1) / FAN_SCAN) * 8);
+    cnt = mask + al(planes * nwg * FAN_CHUNKS * 8);
+    bsum = cnt + al(m * 8);
+    tot = bsum + al(((m + FAN_SCAN - 1) / FAN_SCAN) * 8);
     end = tot + 256;
   }
 };

@@ -7,6 +7,9 @@
 
 namespace drp {
 
+// sizes of scratch regions and staged columns: up to the next multiple of 256 bytes
+inline uint64_t al(uint64_t x) { return (x + 255) & ~255ull; }
+
 struct DecodeParams {
   const uint8_t *bytes;
   uint64_t nbytes;

@@ -173,12 +173,8 @@ __global__ __launch_bounds__(SEL_BLK) void flat_scan_kernel(const FanLatestParam
   const uint64_t per = (m + SEL_BLK - 1) / SEL_BLK, a = umin64(m, threadIdx.x * per), b = umin64(m, a + per);
   uint64_t s = 0;
   for (uint64_t g = a; g < b; g++) s += (uint64_t)__popcll(L.lead[g]);
-  const uint64_t incl = wave_incl_scan64(s);
-  const uint32_t wv = threadIdx.x >> 6;
-  if (lane_id() == 63) part[wv] = incl;
-  __syncthreads();
-  uint64_t run = incl - s;
-  for (uint32_t k = 0; k < wv; k++) run += part[k];
+  uint64_t total;
+  uint64_t run = block_excl_scan(s, part, total);
   for (uint64_t g = a; g < b; g++) {
     L.lead_base[g] = run;
     run += (uint64_t)__popcll(L.lead[g]);
@@ -264,7 +260,6 @@ __global__ __launch_bounds__(FAN_BLK) void flat_keep_kernel(const FanLatestParam
 
 using namespace drp;
 
-static uint64_t lat_al(uint64_t x) { return (x + 255) & ~255ull; }
 // the power of two >= 2 n: the table is at most half full
 static uint64_t lat_nslots(uint64_t n) {
   uint64_t c = 2;
@@ -284,7 +279,7 @@ static LatTable lat_table(void *at, uint64_t n, uint64_t hash_mask) {
 }
 
 extern "C" uint64_t drp_latest_scratch_bytes(uint64_t n) {
-  return lat_al(drp_select_scratch_bytes(n)) + lat_al(n * 8) + lat_nslots(n) * 24;
+  return al(drp_select_scratch_bytes(n)) + al(n * 8) + lat_nslots(n) * 24;
 }
 
 extern "C" hipError_t drp_launch_latest(const SelectParams *Pp, const SelectBytes *fb, uint64_t hash_mask,
@@ -294,9 +289,9 @@ extern "C" hipError_t drp_launch_latest(const SelectParams *Pp, const SelectByte
   const uint64_t n = L.sel.src.n;
   if (n == 0) return hipMemsetAsync(L.sel.n_selected, 0, 8, st);
   if (const hipError_t e = drp_select_place(&L.sel, fb, scratch, st)) return e;
-  uint8_t *sc = static_cast<uint8_t *>(scratch) + lat_al(drp_select_scratch_bytes(n));
+  uint8_t *sc = static_cast<uint8_t *>(scratch) + al(drp_select_scratch_bytes(n));
   L.slot = reinterpret_cast<uint64_t *>(sc);
-  L.t = lat_table(sc + lat_al(n * 8), n, hash_mask);
+  L.t = lat_table(sc + al(n * 8), n, hash_mask);
   if (const hipError_t e = hipMemsetAsync(L.t.tab, 0, L.t.nslots * 24, st)) return e;
   const dim3 grid((uint32_t)((n + SEL_BLK - 1) / SEL_BLK)), blk(SEL_BLK);
   hipLaunchKernelGGL(lat_insert_kernel, grid, blk, 0, st, L);
@@ -310,8 +305,8 @@ extern "C" hipError_t drp_launch_latest(const SelectParams *Pp, const SelectByte
 static uint32_t flat_pass(uint32_t nfilters, uint32_t pass) { return pass == 0 || pass > nfilters ? nfilters : pass; }
 
 extern "C" uint64_t drp_fanout_latest_scratch_bytes(uint64_t n, uint32_t nfilters, uint32_t pass) {
-  const uint64_t words = lat_al((n + 63) / 64 * 8);
-  return lat_al(drp_fanout_scratch_bytes(n, nfilters)) + lat_al(n * 8) + lat_nslots(n) * 8 + 2 * words +
+  const uint64_t words = al((n + 63) / 64 * 8);
+  return al(drp_fanout_scratch_bytes(n, nfilters)) + al(n * 8) + lat_nslots(n) * 8 + 2 * words +
          n * 16 * (uint64_t)flat_pass(nfilters, pass);
 }
 
@@ -323,10 +318,10 @@ extern "C" hipError_t drp_launch_fanout_latest(const FanParams *Pp, uint64_t has
   if (n == 0) return hipSuccess;
   const uint32_t K = L.fan.nfilters;
   pass = flat_pass(K, pass);
-  const uint64_t m = (n + 63) / 64, words = lat_al(m * 8);
-  uint8_t *sc = static_cast<uint8_t *>(scratch) + lat_al(drp_fanout_scratch_bytes(n, K));
+  const uint64_t m = (n + 63) / 64, words = al(m * 8);
+  uint8_t *sc = static_cast<uint8_t *>(scratch) + al(drp_fanout_scratch_bytes(n, K));
   L.group = reinterpret_cast<uint64_t *>(sc);
-  L.t = lat_table(sc + lat_al(n * 8), n, hash_mask);
+  L.t = lat_table(sc + al(n * 8), n, hash_mask);
   L.lead = L.t.tab + L.t.nslots;
   L.lead_base = L.lead + words / 8;
   L.state = L.lead_base + words / 8;

@@ -218,37 +218,25 @@ __global__ __launch_bounds__(ORD_SCAN) void ord_blocksum_kernel(const OrderParam
   if (!c.act[p]) return;
   const uint64_t m = (uint64_t)ORD_BINS * c.nwg, g = (uint64_t)blockIdx.x * ORD_SCAN + threadIdx.x;
   if ((uint64_t)blockIdx.x * ORD_SCAN >= m) return;
-  const uint32_t s = wave_sum32(g < m ? P.hist[g] : 0);
-  if (lane_id() == 0) ws[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    uint32_t t = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < ORD_SCAN / 64; k++) t += ws[k];
-    P.bsum[blockIdx.x] = t;
-  }
+  uint32_t t;
+  (void)block_excl_scan<uint32_t>(g < m ? P.hist[g] : 0, ws, t);
+  if (threadIdx.x == 0) P.bsum[blockIdx.x] = t;
 }
 
 // (2c) exclusive scan of the table in place: a block's base is the sum of the block sums before it
 // (at most blockIdx.x / ORD_SCAN rounds), then a scan within the block. (All sums are <= n < 2^32.)
 __global__ __launch_bounds__(ORD_SCAN) void ord_scanbase_kernel(const OrderParams P, uint32_t p) {
-  __shared__ uint32_t ws[ORD_SCAN / 64], part[ORD_SCAN / 64];
+  __shared__ uint32_t ws[ORD_SCAN / 64];
   const OrdCtl &c = *P.ctl;
   if (!c.act[p]) return;
   const uint64_t m = (uint64_t)ORD_BINS * c.nwg, g = (uint64_t)blockIdx.x * ORD_SCAN + threadIdx.x;
   if ((uint64_t)blockIdx.x * ORD_SCAN >= m) return;
   uint32_t acc = 0;
   for (uint32_t k = threadIdx.x; k < blockIdx.x; k += ORD_SCAN) acc += P.bsum[k];
-  acc = wave_sum32(acc);
-  const uint32_t wv = threadIdx.x >> 6;
-  if (lane_id() == 0) ws[wv] = acc;
+  uint32_t base, total;
+  (void)block_excl_scan(acc, ws, base);
   const uint32_t v = g < m ? P.hist[g] : 0;
-  const uint32_t incl = wave_incl_scan32(v);
-  if (lane_id() == 63) part[wv] = incl;
-  __syncthreads();
-  uint32_t excl = incl - v;
-#pragma unroll
-  for (uint32_t k = 0; k < ORD_SCAN / 64; k++) excl += ws[k] + (k < wv ? part[k] : 0);
+  const uint32_t excl = base + block_excl_scan(v, ws, total);
   if (g < m) P.hist[g] = excl;
 }
 
@@ -378,7 +366,6 @@ __global__ __launch_bounds__(256) void ord_gather_kernel(const OrderParams P) {
 
 using namespace drp;
 
-static uint64_t ord_al(uint64_t x) { return (x + 255) & ~255ull; }
 
 namespace {
 struct OrdLayout {
@@ -388,14 +375,14 @@ struct OrdLayout {
     nscan = (ORD_BINS * nwg + ORD_SCAN - 1) / ORD_SCAN;
     ctl = 0;
     por = 256;
-    pand = por + ord_al(nwg * 8);
-    key[0] = pand + ord_al(nwg * 8);
-    key[1] = key[0] + ord_al(cap * 8);
-    idx[0] = key[1] + ord_al(cap * 8);
-    idx[1] = idx[0] + ord_al(cap * 4);
-    hist = idx[1] + ord_al(cap * 4);
-    bsum = hist + ord_al(ORD_BINS * nwg * 4);
-    end = bsum + ord_al(nscan * 4);
+    pand = por + al(nwg * 8);
+    key[0] = pand + al(nwg * 8);
+    key[1] = key[0] + al(cap * 8);
+    idx[0] = key[1] + al(cap * 8);
+    idx[1] = idx[0] + al(cap * 4);
+    hist = idx[1] + al(cap * 4);
+    bsum = hist + al(ORD_BINS * nwg * 4);
+    end = bsum + al(nscan * 4);
   }
 };
 static_assert(sizeof(OrdCtl) <= 256, "the control block's place in the scratch");

@@ -33,27 +33,10 @@ __global__ __launch_bounds__(SEL_BLK) void sel_count_kernel(const SelectParams P
 // (2) exclusive scan of the workgroup counts in place (any number of them: SEL_BLK per round with
 // a running carry); the total is the number of rows kept
 __global__ __launch_bounds__(SEL_BLK) void sel_scan_kernel(const SelectParams P, uint64_t nblk) {
-  __shared__ uint64_t part[SEL_BLK];
-  __shared__ uint64_t carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (uint64_t c0 = 0; c0 < nblk; c0 += SEL_BLK) {
-    const uint64_t b = c0 + threadIdx.x;
-    const uint64_t v0 = b < nblk ? P.block_cnt[b] : 0;
-    part[threadIdx.x] = v0;
-    __syncthreads();
-    for (uint32_t d = 1; d < SEL_BLK; d <<= 1) {
-      const uint64_t v = threadIdx.x >= d ? part[threadIdx.x - d] : 0;
-      __syncthreads();
-      part[threadIdx.x] += v;
-      __syncthreads();
-    }
-    if (b < nblk) P.block_cnt[b] = carry + part[threadIdx.x] - v0;
-    __syncthreads();
-    if (threadIdx.x == SEL_BLK - 1) carry += part[SEL_BLK - 1];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *P.n_selected = carry;
+  __shared__ uint64_t part[SEL_WAVES];
+  const uint64_t total = block_scan_rounds(
+      nblk, part, [&](uint64_t b) { return P.block_cnt[b]; }, [&](uint64_t b, uint64_t ex) { P.block_cnt[b] = ex; });
+  if (threadIdx.x == 0) *P.n_selected = total;
 }
 
 // (3) every kept row's columns to its slot
@@ -80,7 +63,7 @@ extern "C" uint32_t drp_select_known_flags(void) { return SEL_KNOWN; }
 // scratch: the filter's byte strings, the ballot words (one per 64 rows, for whole workgroups),
 // the workgroup counts
 static uint64_t sel_nblk(uint64_t n) { return (n + SEL_BLK - 1) / SEL_BLK; }
-static uint64_t sel_mask_bytes(uint64_t n) { return (sel_nblk(n) * SEL_WAVES * 8 + 255) & ~255ull; }
+static uint64_t sel_mask_bytes(uint64_t n) { return al(sel_nblk(n) * SEL_WAVES * 8); }
 extern "C" uint64_t drp_select_scratch_bytes(uint64_t n) {
   return 2 * DRP_SEL_MAX_BYTES + sel_mask_bytes(n) + sel_nblk(n) * 8 + 256;
 }

@@ -42,23 +42,6 @@ enum : uint32_t { ST_NONE = 0, ST_INSERT = 1, ST_REPLACE = 2, ST_UNCHANGED = 3, 
 
 __device__ __forceinline__ uint32_t st_r16(uint32_t len) { return (len + 15u) & ~15u; }  // (len <= 2^32 - 16)
 
-// v summed over the lanes of the workgroup before this one, and over all of them (ST_BLK lanes)
-__device__ __forceinline__ uint64_t st_block_prefix(uint64_t v, uint64_t &total) {
-  __shared__ uint64_t part[ST_WAVES];
-  const uint64_t incl = wave_incl_scan64(v);
-  const uint32_t wv = threadIdx.x >> 6;
-  if (lane_id() == 63) part[wv] = incl;
-  __syncthreads();
-  uint64_t before = incl - v, all = 0;
-#pragma unroll
-  for (uint32_t k = 0; k < ST_WAVES; k++) {
-    if (k < wv) before += part[k];
-    all += part[k];
-  }
-  total = all;
-  return before;
-}
-
 // store row r (named by a table word) has this identity; a row outside the store, or whose payload
 // leaves the arena (a table that no drp_store_init cleared), matches nothing and is never read
 __device__ __forceinline__ bool st_same(const StoreDev &S, uint64_t r, bool has, const uint8_t *key, uint32_t klen,
@@ -74,7 +57,7 @@ __device__ __forceinline__ bool st_same(const StoreDev &S, uint64_t r, bool has,
 
 __global__ __launch_bounds__(ST_BLK) void st_lookup_kernel(const StoreMerge M) {
   __shared__ uint32_t wcnt[ST_WAVES][ST_MISC];
-  __shared__ uint64_t wdead[ST_WAVES];
+  __shared__ uint64_t wdead[ST_WAVES], sw[ST_WAVES];
   const StoreDev &S = M.s;
   const uint64_t i = (uint64_t)blockIdx.x * ST_BLK + threadIdx.x;
   uint32_t code = ST_NONE, alloc = 0;
@@ -154,7 +137,7 @@ __global__ __launch_bounds__(ST_BLK) void st_lookup_kernel(const StoreMerge M) {
     wdead[wv] = dsum;
   }
   uint64_t btotal;
-  const uint64_t before = st_block_prefix(alloc, btotal);  // (its barrier publishes wcnt and wdead too)
+  const uint64_t before = block_excl_scan<uint64_t>(alloc, sw, btotal);  // (its barrier publishes wcnt and wdead too)
   uint32_t irank = (uint32_t)__popcll(bi & ((1ull << lane) - 1ull));
   for (uint32_t k = 0; k < wv; k++) irank += wcnt[k][0];
   M.where[i] = where;  // (i < nblk * ST_BLK: the state covers whole workgroups)
@@ -387,8 +370,9 @@ struct StoreCompact {
 __global__ __launch_bounds__(ST_BLK) void stc_size_kernel(const StoreCompact Q) {
   const uint64_t r = (uint64_t)blockIdx.x * ST_BLK + threadIdx.x;
   const uint64_t rows = umin64(Q.s.info->rows, Q.s.max_keys);
+  __shared__ uint64_t sw[ST_WAVES];
   uint64_t total;
-  const uint64_t before = st_block_prefix(r < rows ? st_r16(Q.s.payload_len[r]) : 0, total);
+  const uint64_t before = block_excl_scan<uint64_t>(r < rows ? st_r16(Q.s.payload_len[r]) : 0, sw, total);
   if (r < rows) Q.boff[r] = before;
   if (threadIdx.x == 0) Q.blk_bytes[blockIdx.x] = total;
 }
@@ -426,7 +410,6 @@ __global__ __launch_bounds__(ST_BLK) void stc_copy_kernel(const StoreCompact Q) 
 
 using namespace drp;
 
-static uint64_t st_al(uint64_t x) { return (x + 255) & ~255ull; }
 static uint64_t st_nblk(uint64_t n) { return n ? (n + ST_BLK - 1) / ST_BLK : 1; }
 
 extern "C" uint64_t drp_store_nslots(uint64_t max_keys) {
@@ -446,7 +429,7 @@ extern "C" hipError_t drp_launch_store_init(const StoreDev *S, hipStream_t st) {
 // for whole workgroups), 2 + ST_MISC words per workgroup, the control words
 extern "C" uint64_t drp_store_merge_scratch_bytes(uint64_t n) {
   const uint64_t nblk = st_nblk(n), m = nblk * ST_BLK;
-  return 3 * st_al(m * 8) + 2 * st_al(m * 4) + 2 * st_al(nblk * 8) + st_al(nblk * ST_MISC * 8) + 256;
+  return 3 * al(m * 8) + 2 * al(m * 4) + 2 * al(nblk * 8) + al(nblk * ST_MISC * 8) + 256;
 }
 
 extern "C" uint64_t drp_store_blocks(uint64_t n) { return st_nblk(n); }
@@ -457,7 +440,7 @@ extern "C" hipError_t drp_launch_store_merge(const StoreMerge *Mp, const StoreRe
   const uint64_t nblk = st_nblk(M.n), m = nblk * ST_BLK;
   if (nblk >= (1ull << 31) / ST_GRP) return hipErrorInvalidValue;
   uint8_t *sc = static_cast<uint8_t *>(scratch);
-  auto take = [&](uint64_t bytes) { void *p = sc; sc += st_al(bytes); return p; };
+  auto take = [&](uint64_t bytes) { void *p = sc; sc += al(bytes); return p; };
   M.where = static_cast<uint64_t *>(take(m * 8));
   M.hash = static_cast<uint64_t *>(take(m * 8));
   M.boff = static_cast<uint64_t *>(take(m * 8));
@@ -494,7 +477,7 @@ extern "C" hipError_t drp_launch_store_merge(const StoreMerge *Mp, const StoreRe
 }
 
 extern "C" uint64_t drp_store_compact_scratch_bytes(uint64_t max_keys) {
-  return st_al(max_keys * 8) + st_al(st_nblk(max_keys) * 8) + 256;
+  return al(max_keys * 8) + al(st_nblk(max_keys) * 8) + 256;
 }
 
 extern "C" hipError_t drp_launch_store_compact(const StoreDev *S, uint8_t *arena2, uint64_t arena2_bytes,
@@ -506,8 +489,8 @@ extern "C" hipError_t drp_launch_store_compact(const StoreDev *S, uint8_t *arena
   const uint64_t nblk = st_nblk(S->max_keys);
   uint8_t *sc = static_cast<uint8_t *>(scratch);
   Q.boff = reinterpret_cast<uint64_t *>(sc);
-  Q.blk_bytes = reinterpret_cast<uint64_t *>(sc + st_al(S->max_keys * 8));
-  Q.ctl = Q.blk_bytes + st_al(nblk * 8) / 8;
+  Q.blk_bytes = reinterpret_cast<uint64_t *>(sc + al(S->max_keys * 8));
+  Q.ctl = Q.blk_bytes + al(nblk * 8) / 8;
   const dim3 blk(ST_BLK);
   hipLaunchKernelGGL(stc_size_kernel, dim3((uint32_t)nblk), blk, 0, st, Q);
   if (const hipError_t e = drp_launch_count_scan(Q.blk_bytes, nblk, Q.ctl, st)) return e;
