@@ -192,6 +192,7 @@ void drp_close(drp_ctx *c) {
   c->keytext.release();
   c->fan_rows.release();
   c->news.release();
+  c->lack.release();
   c->fan_tab.release();
   if (c->fan_ev) (void)hipEventDestroy(c->fan_ev);
   if (c->dstats) (void)hipFree(c->dstats);

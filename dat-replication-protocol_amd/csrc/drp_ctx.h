@@ -170,6 +170,8 @@ struct drp_ctx {
   drp::DevBuf news;
   bool news_held = false;
   uint64_t news_seq = 0;
+  // drp_store_lookup_staged's lack_type column (one byte per store row) for its select
+  drp::DevBuf lack;
   // the staged host-batch decode: row 0 is a host-built blob continuation when nf0 == 1; GPU
   // rows follow, each piece's payload_off relative to the batch offset where that piece was
   // staged (pieces: {first GPU row, batch offset}; one piece unless blobs were skipped)

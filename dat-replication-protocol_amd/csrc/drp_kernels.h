@@ -273,6 +273,28 @@ struct StoreReport {
 };
 constexpr uint32_t ST_BLK = 256, ST_WAVES = ST_BLK / 64, ST_MISC = 5;
 constexpr uint32_t ST_GRP = 16;  // lanes that copy one payload, 16 bytes each per step
+// one lookup (include/drp.h "lookup"): the queries are the candidates among sel.src's rows under
+// sel's filter; the store is only read. Every output may be null; the state is placed by the launcher
+constexpr uint32_t LK_CODES = 5;  // DRP_LOOKUP_NONE .. DRP_LOOKUP_AHEAD
+struct StoreLookup {
+  StoreDev s;
+  SelectParams sel;    // the row source and the predicate (its scratch and outputs are not used)
+  uint32_t emit_mask;  // DRP_LOOKUP_BIT of the verdicts whose store rows are emitted
+  uint8_t *verdict;    // [n]
+  uint64_t *hit_row;   // [n]
+  uint64_t *counts;    // [LK_CODES]
+  uint8_t *lack_type;  // [max_keys]
+  RowOut out;          // the emitted queries' store rows (out.sel_idx: out_query), rows_cap entries
+  uint64_t *n_out, rows_cap;
+  // per query, only with n_out: its store row, and verdict | rank among its workgroup's emitted
+  // queries << 8
+  uint64_t *where;
+  uint32_t *meta;
+  // per workgroup of ST_BLK queries: its emitted queries (scanned in place) and its rows per verdict
+  uint64_t *blk_emit, *blk_cnt;
+  uint64_t nblk;
+  uint64_t *ctl;  // [0] the emitted queries
+};
 
 // drp_digest.hip: the bucket digest of the select's candidates whose ranges lie inside the wire
 // (dig_cells: cells, totals), and the count step of the select restricted to the buckets of a set
@@ -451,6 +473,11 @@ hipError_t drp_launch_store_init(const drp::StoreDev *S, hipStream_t st);
 uint64_t drp_store_merge_scratch_bytes(uint64_t n);
 hipError_t drp_launch_store_merge(const drp::StoreMerge *M, const drp::StoreReport *R, void *scratch, hipStream_t st);
 uint64_t drp_store_blocks(uint64_t n);  // the workgroups of ST_BLK winners a merge of n rows runs (>= 1)
+// the lookup Q (its state is placed in `scratch`, drp_store_lookup_scratch_bytes(n) bytes; fb: the
+// filter's byte strings, as drp_launch_select takes them): nothing of the store is written
+uint64_t drp_store_lookup_scratch_bytes(uint64_t n);
+hipError_t drp_launch_store_lookup(const drp::StoreLookup *Q, const drp::SelectBytes *fb, void *scratch,
+                                   hipStream_t st);
 uint64_t drp_store_compact_scratch_bytes(uint64_t max_keys);
 hipError_t drp_launch_store_compact(const drp::StoreDev *S, uint8_t *arena2, uint64_t arena2_bytes, void *scratch,
                                     hipStream_t st);

@@ -4,7 +4,8 @@
 // heap), drp_fanout_device / drp_fanout_staged (many filters over one pass) and
 // drp_fanout_latest_device / drp_fanout_latest_staged (latest per key under each), and the store
 // (drp_store_*: the latest-per-key step, then the merge into caller-owned device memory; with a
-// report, drp_store_merge_report_device, drp_store_merge_news_staged / drp_fanout_news_staged), and the
+// report, drp_store_merge_report_device, drp_store_merge_news_staged / drp_fanout_news_staged; the
+// read-only probe by key, drp_store_lookup_device / drp_store_lookup_staged), and the
 // digest calls (drp_digest_device, drp_digest_diff_device, drp_select_buckets_device, and their second
 // level drp_digest_refine_device, drp_digest_diff_cells_device, drp_select_refined_device), and the ordered
 // catch-up (drp_order_device). The kernels are in drp_select.hip, drp_latest.hip, drp_fanout.hip,
@@ -444,6 +445,38 @@ static bool report_ok(const drp_merge_report *rep, const uint8_t *type) {
   return !(rep->news_type && rep->news_type == type);
 }
 
+// ---- lookup -------------------------------------------------------------------------------------
+constexpr uint32_t LOOKUP_EMIT_BITS =
+    DRP_LOOKUP_BIT(DRP_LOOKUP_BEHIND) | DRP_LOOKUP_BIT(DRP_LOOKUP_LEVEL) | DRP_LOOKUP_BIT(DRP_LOOKUP_AHEAD);
+
+// the DRP_E_INVAL cases of a drp_lookup that need neither the ctx nor a device (type: the store's
+// type column)
+static bool lookup_ok(const drp_lookup *lk, const uint8_t *type) {
+  if (!lk || lk->flags || (lk->emit_mask & ~LOOKUP_EMIT_BITS)) return false;
+  if (lk->out_rows && (!lk->n_out || (lk->rows_cap && !src_cols_ok(lk->out_rows)))) return false;
+  return !(lk->lack_type && lk->lack_type == type);
+}
+
+// The lookup of the rows of `src` under the filter F / fb against D, its state `at` bytes into the
+// ctx's scratch (ensured by the caller: drp_store_lookup_scratch_bytes(src.n) bytes from there)
+static int store_lookup(drp_ctx *c, const StoreDev &D, const RowSrc &src, const RowFilter &F, const SelectBytes &fb,
+                        const drp_lookup *lk, size_t at) {
+  StoreLookup Q = {};
+  Q.s = D;
+  Q.sel.src = src;
+  Q.sel.f = F;
+  Q.emit_mask = lk->emit_mask;  // (n_out without out_rows: the count alone, as with rows_cap 0)
+  Q.verdict = lk->verdict;
+  Q.hit_row = lk->hit_row;
+  Q.counts = lk->counts;
+  Q.lack_type = lk->lack_type;
+  if (lk->out_rows && lk->rows_cap) Q.out = row_out(lk->out_rows, lk->out_query);
+  Q.n_out = lk->n_out;
+  Q.rows_cap = lk->out_rows ? lk->rows_cap : 0;
+  CHK(drp_launch_store_lookup(&Q, &fb, c->scratch.at<char>(at), c->st));
+  return DRP_OK;
+}
+
 static int store_query(drp_ctx *c, const drp_store_info *dev, drp_store_info *host) {
   CHK(hipMemcpyAsync(host, dev, sizeof(drp_store_info), hipMemcpyDeviceToHost, c->st));
   CHK(hipStreamSynchronize(c->st));
@@ -663,6 +696,78 @@ int drp_fanout_news_staged(drp_ctx *c, const drp_filter *filters, uint32_t nfilt
                            uint64_t blob_cap, uint64_t *n_blobs) {
   return fanout_staged(c, filters, nfilters, out, cap, out_off, n_selected, blob_row, blob_pos, blob_cap, n_blobs,
                        false, true);
+}
+
+int drp_store_lookup_device(drp_ctx *c, const drp_store *s, const uint8_t *bytes, uint64_t nbytes,
+                            const drp_frames *frames, const drp_changes *cols, uint64_t n, const drp_filter *filter,
+                            const drp_lookup *lk) {
+  StoreDev D = {};
+  if (!c || !s || !frames || !cols || (!bytes && nbytes) || !lookup_ok(lk, s->frames.type)) return DRP_E_INVAL;
+  if (!store_dev(c, s, D) || !cols_ok(frames, cols, n)) return DRP_E_INVAL;
+  RowFilter F;
+  SelectBytes fb = {};
+  if (const int rc = select_filter(filter, F, fb.b)) return rc;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  // (the decode scratch: free between decodes, and every user is ordered on the ctx's stream)
+  if (!c->scratch.ensure(drp_store_lookup_scratch_bytes(n))) return DRP_E_NOMEM;
+  return store_lookup(c, D, caller_src(bytes, nbytes, frames, cols, n), F, fb, lk, 0);
+}
+
+// Scratch (the decode's, free until the next decode): with DRP_LOOKUP_REPLY_LACK the select's words
+// for max_keys rows; the lookup's state; the counts (the reply's rows, then the five verdicts); the
+// piece table; the reply's rows (ten columns of n entries, or of max_keys)
+int drp_store_lookup_staged(drp_ctx *c, const drp_store *s, const drp_filter *filter, uint32_t reply, uint8_t *out,
+                            uint64_t cap, uint64_t *written, uint64_t *n_rows, uint64_t *counts_host) {
+  StoreDev D = {};
+  const bool lack = reply == DRP_LOOKUP_REPLY_LACK;
+  if (!c || !s || !written || !n_rows || (!out && cap) || (!lack && (reply & ~LOOKUP_EMIT_BITS))) return DRP_E_INVAL;
+  if (!store_dev(c, s, D)) return DRP_E_INVAL;
+  const auto &S = c->staged;
+  if (!S.valid) return DRP_E_INVAL;
+  RowFilter F;
+  SelectBytes fb = {};
+  if (const int rc = select_filter(filter, F, fb.b)) return rc;
+  *written = 0;
+  *n_rows = 0;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  const uint64_t n = S.good, cap_rows = lack ? D.max_keys : n;
+  const size_t o_lk = lack ? al(drp_select_scratch_bytes(D.max_keys)) : 0,
+               o_cnt = o_lk + al(drp_store_lookup_scratch_bytes(n)), o_piece = o_cnt + 256,
+               o_rows = o_piece + al(2 * S.pieces.size() * 8), col = al(cap_rows * 8);
+  if (!c->scratch.ensure(o_rows + 10 * col)) return DRP_E_NOMEM;
+  if (lack && !c->lack.ensure(D.max_keys + 16)) return DRP_E_NOMEM;
+  uint64_t *dcnt = c->scratch.at<uint64_t>(o_cnt);
+  const drp_change_src rows = carve_rows(c->scratch, o_rows, col);
+  RowSrc src;
+  if (const int rc = staged_src(c, src, c->scratch.at<uint64_t>(o_piece))) return rc;
+  drp_lookup lk = {};
+  lk.counts = dcnt + 1;
+  if (lack) {
+    lk.lack_type = c->lack.at<uint8_t>(0);
+  } else {
+    lk.emit_mask = reply;
+    lk.out_rows = &rows;
+    lk.n_out = dcnt;
+    lk.rows_cap = n;
+  }
+  if (const int rc = store_lookup(c, D, src, F, fb, &lk, o_lk)) return rc;
+  if (lack) {  // the store's rows under lack_type, in store-row order
+    SelectParams P = {};
+    SelectBytes none = {};
+    select_filter(nullptr, P.f, none.b);
+    drp_frames fr = s->frames;
+    fr.type = lk.lack_type;
+    P.src = caller_src(D.arena, D.arena_bytes, &fr, &D.cols, D.max_keys);
+    P.out = row_out(&rows, nullptr);
+    P.n_selected = dcnt;
+    CHK(drp_launch_select(&P, &none, c->scratch.p, c->st));
+  }
+  uint64_t h[1 + LK_CODES];
+  CHK(hipMemcpyAsync(h, dcnt, sizeof h, hipMemcpyDeviceToHost, c->st));
+  CHK(hipStreamSynchronize(c->st));  // (the one readback that sizes the encode)
+  *n_rows = h[0];
+  if (counts_host) memcpy(counts_host, h + 1, LK_CODES * 8);
+  return drp_encode_batch(c, &rows, D.arena, D.arena_bytes, h[0], out, cap, written);
 }
 
 int drp_store_compact(drp_ctx *c, const drp_store *s, uint8_t *arena2, uint64_t arena2_bytes) {

@@ -32,6 +32,8 @@
 //               wave), the allocation's tail zeroed; the group's first lane writes the columns.
 //   st_commit   rows, arena_used, arena_dead, merges.
 // With a report (include/drp.h "merge report") the rep_* steps follow: see "report" below.
+// The lookup (include/drp.h "lookup") probes the table as st_lookup does (st_probe, one copy) and
+// writes nothing into the store: see "lookup" below.
 // The compact is the same shape: the live allocations' sizes and their prefix, the scan, the verdict
 // with the commit (nothing later reads the old totals), the copy.
 #include "drp_select.h"  // (wire_has, bytes_eq; drp_device.h: xxh, ld_agent, the wave scans)
@@ -55,6 +57,43 @@ __device__ __forceinline__ bool st_same(const StoreDev &S, uint64_t r, bool has,
   return bytes_eq(a, key, klen) && bytes_eq(a + klen, sub, slen);
 }
 
+// the identity's hash: lat_group's (XXH64 of the key, the subset's merged in: an empty subset still
+// changes it), under the ctx's hash mask
+__device__ __forceinline__ uint64_t st_hash(const StoreDev &S, bool has, const uint8_t *key, uint32_t klen,
+                                            const uint8_t *sub, uint32_t slen) {
+  uint64_t h = xxh::xxh64(key, klen);
+  if (has) h = xxh::merge(h, xxh::xxh64(sub, slen));
+  return h & S.hash_mask;
+}
+
+// The probe of the table for an identity of hash h, one copy for the merge (st_lookup) and the
+// read-only lookup (lk_probe): a linear walk with atomic loads to the next free slot or tag match,
+// then (outside that loop) the byte compare of st_same. Nothing is written. Returns the store row
+// that holds the identity, or ~0 with `free_slot` = the first free slot of the probe (~0 as well for
+// a table without one: not reached, it is at most half full).
+__device__ __forceinline__ uint64_t st_probe(const StoreDev &S, uint64_t h, bool has, const uint8_t *key,
+                                             uint32_t klen, const uint8_t *sub, uint32_t slen, uint64_t &free_slot) {
+  const uint64_t smask = S.nslots - 1;
+  uint64_t s = h & smask, step = 0;
+  free_slot = ~0ull;
+  while (step < S.nslots) {
+    uint64_t seen = 0;
+    for (; step < S.nslots; step++, s = (s + 1) & smask) {
+      seen = ld_agent(S.table + s);
+      if (seen == 0 || ((seen ^ h) & ST_TAG) == 0) break;
+    }
+    if (step == S.nslots) break;
+    if (seen == 0) {
+      free_slot = s;
+      break;
+    }
+    if (st_same(S, (seen & ~ST_TAG) - 1, has, key, klen, sub, slen)) return (seen & ~ST_TAG) - 1;
+    step++;
+    s = (s + 1) & smask;
+  }
+  return ~0ull;
+}
+
 __global__ __launch_bounds__(ST_BLK) void st_lookup_kernel(const StoreMerge M) {
   __shared__ uint32_t wcnt[ST_WAVES][ST_MISC];
   __shared__ uint64_t wdead[ST_WAVES], sw[ST_WAVES];
@@ -76,32 +115,13 @@ __global__ __launch_bounds__(ST_BLK) void st_lookup_kernel(const StoreMerge M) {
       code = ST_SKIPPED;
     } else {
       const uint8_t *key = M.bytes + koff, *sub = M.bytes + soff, *val = M.bytes + voff;
-      h = xxh::xxh64(key, klen);
-      if (has) h = xxh::merge(h, xxh::xxh64(sub, slen));
-      h &= S.hash_mask;
-      const uint64_t smask = S.nslots - 1;
-      uint64_t s = h & smask, r = ~0ull;
+      h = st_hash(S, has, key, klen, sub, slen);
+      uint64_t free_slot;
+      const uint64_t r = st_probe(S, h, has, key, klen, sub, slen, free_slot);
       code = ST_SKIPPED;  // (a table without a free slot: not reached, it is at most half full)
-      uint64_t step = 0;
-      while (step < S.nslots) {
-        // to the next free slot or tag match, then (outside that loop) the byte compare
-        uint64_t seen = 0;
-        for (; step < S.nslots; step++, s = (s + 1) & smask) {
-          seen = ld_agent(S.table + s);
-          if (seen == 0 || ((seen ^ h) & ST_TAG) == 0) break;
-        }
-        if (step == S.nslots) break;
-        if (seen == 0) {
-          code = ST_INSERT;
-          where = s;
-          break;
-        }
-        if (st_same(S, (seen & ~ST_TAG) - 1, has, key, klen, sub, slen)) {
-          r = (seen & ~ST_TAG) - 1;
-          break;
-        }
-        step++;
-        s = (s + 1) & smask;
+      if (r == ~0ull && free_slot != ~0ull) {
+        code = ST_INSERT;
+        where = free_slot;
       }
       if (r != ~0ull) {
         const drp_changes &c = S.cols;
@@ -357,6 +377,116 @@ __global__ __launch_bounds__(ST_BLK) void rep_reply_kernel(const StoreMerge M, c
   row_store(R.reply, j, row_load(V, r), r);
 }
 
+// ---- lookup -----------------------------------------------------------------------------------
+// The read-only probe (include/drp.h "lookup"): the batch's candidates are queries, each looked up by
+// identity and compared by `change`; no byte of the store is written. Everything read here (the
+// table, the columns, the arena) was written by earlier launches, nothing is handed between
+// workgroups inside a kernel, and every store is a plain vector store.
+//   (copy)     frames.type -> lack_type, max_keys bytes, on the stream before lk_probe.
+//   lk_probe   one query per lane: sel_pred and the candidate's wire-range test, st_hash and st_probe
+//              (the merge's), the verdict from the two changes; verdict / hit_row; a zero byte into
+//              lack_type[row] for a hit whose change is not below the stored one (the only writes
+//              behind the copy are zeros: the order of the queries decides nothing); the query's
+//              rank among the workgroup's emitted queries (ballots and the waves' counts, as
+//              st_lookup ranks the inserted); per workgroup the emitted count and the five verdict
+//              counts.
+//   scan       drp_select.hip's, over the workgroups' emitted counts.
+//   lk_totals  one workgroup: the verdict counts summed over the workgroups, and *n_out.
+//   lk_emit    the emitted queries, if their total fits rows_cap: place = the scanned count + the
+//              rank; the store row's ten columns as row_load / row_store write them, as rep_reply.
+__global__ __launch_bounds__(ST_BLK) void lk_probe_kernel(const StoreLookup Q) {
+  __shared__ uint32_t wcnt[ST_WAVES][LK_CODES + 1];
+  const StoreDev &S = Q.s;
+  const RowSrc &P = Q.sel.src;
+  const uint64_t i = (uint64_t)blockIdx.x * ST_BLK + threadIdx.x;
+  uint32_t code = DRP_LOOKUP_NONE;
+  uint64_t row = ~0ull;
+  if (i < P.n && sel_pred(Q.sel, i)) {
+    const drp_changes &c = P.cols;
+    const bool has = (c.flags[i] & DRP_F_SUBSET) != 0;
+    const uint64_t base = P.payload_off[i] + row_shift(P, i);
+    const uint64_t koff = base + c.key_off[i], soff = base + c.subset_off[i];
+    const uint32_t klen = c.key_len[i], slen = has ? c.subset_len[i] : 0;
+    // (lat_group's test: a row whose key or subset range leaves the wire is no candidate, never read)
+    if (wire_has(P, koff, klen) && (!has || wire_has(P, soff, slen))) {
+      const uint8_t *key = P.bytes + koff, *sub = P.bytes + soff;
+      uint64_t free_slot;
+      row = st_probe(S, st_hash(S, has, key, klen, sub, slen), has, key, klen, sub, slen, free_slot);
+      if (row == ~0ull) {
+        code = DRP_LOOKUP_ABSENT;
+      } else {  // (row < max_keys: st_same)
+        const uint64_t sch = S.cols.change[row], qch = c.change[i];
+        code = sch > qch ? DRP_LOOKUP_AHEAD : sch == qch ? DRP_LOOKUP_LEVEL : DRP_LOOKUP_BEHIND;
+        if (Q.lack_type && qch >= sch) Q.lack_type[row] = 0;
+      }
+    }
+  }
+  const bool in = i < P.n;
+  if (in && Q.verdict) Q.verdict[i] = (uint8_t)code;
+  if (in && Q.hit_row) Q.hit_row[i] = row;
+  // the workgroup's sums, and this query's place among its emitted queries
+  const uint32_t wv = threadIdx.x >> 6, lane = lane_id();
+  const uint64_t be = __ballot(((Q.emit_mask >> code) & 1u) != 0);  // (bit 0 is never set: NONE is not emitted)
+  uint32_t mine = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < LK_CODES; k++) {
+    const uint32_t cnt = (uint32_t)__popcll(__ballot(in && code == k));
+    if (lane == k + 1) mine = cnt;
+  }
+  if (lane == 0) mine = (uint32_t)__popcll(be);
+  if (lane <= LK_CODES) wcnt[wv][lane] = mine;
+  __syncthreads();
+  if (Q.meta) {
+    uint32_t rank = (uint32_t)__popcll(be & ((1ull << lane) - 1ull));
+    for (uint32_t k = 0; k < wv; k++) rank += wcnt[k][0];
+    Q.where[i] = row;  // (i < nblk * ST_BLK: the state covers whole workgroups)
+    Q.meta[i] = code | (rank << 8);
+  }
+  if (threadIdx.x <= LK_CODES) {
+    uint64_t t = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < ST_WAVES; k++) t += wcnt[k][threadIdx.x];
+    if (threadIdx.x == 0) Q.blk_emit[blockIdx.x] = t;
+    else Q.blk_cnt[(uint64_t)blockIdx.x * LK_CODES + threadIdx.x - 1] = t;
+  }
+}
+
+// one workgroup: the verdict counts over all workgroups, and the emitted total the scan left
+__global__ __launch_bounds__(ST_BLK) void lk_totals_kernel(const StoreLookup Q) {
+  __shared__ uint64_t part[ST_WAVES][LK_CODES];
+  uint64_t s[LK_CODES] = {};
+  for (uint64_t b = threadIdx.x; b < Q.nblk; b += ST_BLK)
+#pragma unroll
+    for (uint32_t k = 0; k < LK_CODES; k++) s[k] += Q.blk_cnt[b * LK_CODES + k];
+#pragma unroll
+  for (uint32_t k = 0; k < LK_CODES; k++) {
+    s[k] = wave_sum64(s[k]);
+    if (lane_id() == 0) part[threadIdx.x >> 6][k] = s[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < LK_CODES && Q.counts) {
+    uint64_t t = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < ST_WAVES; w++) t += part[w][threadIdx.x];
+    Q.counts[threadIdx.x] = t;
+  }
+  if (threadIdx.x == 0 && Q.n_out) *Q.n_out = Q.ctl[0];
+}
+
+__global__ __launch_bounds__(ST_BLK) void lk_emit_kernel(const StoreLookup Q) {
+  const StoreDev &S = Q.s;
+  const uint64_t i = (uint64_t)blockIdx.x * ST_BLK + threadIdx.x;
+  if (i >= Q.sel.src.n || Q.ctl[0] > Q.rows_cap) return;
+  const uint32_t meta = Q.meta[i];
+  if (!((Q.emit_mask >> (meta & 0xFF)) & 1u)) return;
+  const uint64_t j = Q.blk_emit[blockIdx.x] + (meta >> 8), r = Q.where[i];
+  if (j >= Q.rows_cap || r >= S.max_keys) return;  // (not reached: j < the total, and an emitted query was found in a row)
+  RowSrc V = {};  // the store's view (offsets absolute into the arena: no piece shift)
+  V.payload_off = S.payload_off;
+  V.cols = S.cols;
+  row_store(Q.out, j, row_load(V, r), i);
+}
+
 // ---- compact ----------------------------------------------------------------------------------
 struct StoreCompact {
   StoreDev s;
@@ -473,6 +603,42 @@ extern "C" hipError_t drp_launch_store_merge(const StoreMerge *Mp, const StoreRe
     }
     drp_dbg_mark("store_report", st);
   }
+  return hipGetLastError();
+}
+
+// the lookup's state: the filter's byte strings, per query (for whole workgroups) an 8-byte and a
+// 4-byte word, per workgroup 1 + LK_CODES words, the control words
+extern "C" uint64_t drp_store_lookup_scratch_bytes(uint64_t n) {
+  const uint64_t nblk = st_nblk(n), m = nblk * ST_BLK;
+  return 2 * DRP_SEL_MAX_BYTES + al(m * 8) + al(m * 4) + al(nblk * 8) + al(nblk * LK_CODES * 8) + 256;
+}
+
+extern "C" hipError_t drp_launch_store_lookup(const StoreLookup *Qp, const SelectBytes *fb, void *scratch,
+                                              hipStream_t st) {
+  StoreLookup Q = *Qp;
+  const uint64_t n = Q.sel.src.n, nblk = st_nblk(n), m = nblk * ST_BLK;
+  if (nblk >= (1ull << 31)) return hipErrorInvalidValue;
+  // (only the filter's byte strings are placed: the lookup reads neither ballot words nor counts)
+  if (const hipError_t e = drp_select_place(&Q.sel, fb, scratch, st)) return e;
+  uint8_t *sc = static_cast<uint8_t *>(scratch) + 2 * DRP_SEL_MAX_BYTES;
+  auto take = [&](uint64_t bytes) { void *p = sc; sc += al(bytes); return p; };
+  const bool emit = Q.n_out != nullptr;  // (the entry point passes out arrays only with n_out)
+  Q.where = static_cast<uint64_t *>(take(m * 8));
+  Q.meta = static_cast<uint32_t *>(take(m * 4));
+  if (!emit) Q.where = nullptr, Q.meta = nullptr;
+  Q.blk_emit = static_cast<uint64_t *>(take(nblk * 8));
+  Q.blk_cnt = static_cast<uint64_t *>(take(nblk * LK_CODES * 8));
+  Q.ctl = static_cast<uint64_t *>(take(256));
+  Q.nblk = nblk;
+  if (Q.lack_type)
+    if (const hipError_t e = hipMemcpyAsync(Q.lack_type, Q.s.type, Q.s.max_keys, hipMemcpyDeviceToDevice, st)) return e;
+  const dim3 grid((uint32_t)nblk), blk(ST_BLK);
+  hipLaunchKernelGGL(lk_probe_kernel, grid, blk, 0, st, Q);
+  if (emit)
+    if (const hipError_t e = drp_launch_count_scan(Q.blk_emit, nblk, Q.ctl, st)) return e;
+  if (emit || Q.counts) hipLaunchKernelGGL(lk_totals_kernel, dim3(1), blk, 0, st, Q);
+  if (emit && Q.rows_cap) hipLaunchKernelGGL(lk_emit_kernel, grid, blk, 0, st, Q);
+  drp_dbg_mark("store_lookup", st);
   return hipGetLastError();
 }
 

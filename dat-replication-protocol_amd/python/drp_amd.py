@@ -35,6 +35,7 @@ EXPORTS = [
     "drp_store_table_bytes", "drp_store_init", "drp_store_merge_device", "drp_store_merge_staged",
     "drp_store_compact", "drp_store_query", "drp_order_device",
     "drp_store_merge_report_device", "drp_store_merge_news_staged", "drp_fanout_news_staged",
+    "drp_store_lookup_device", "drp_store_lookup_staged",
     "drp_digest_device", "drp_digest_diff_device", "drp_select_buckets_device",
     "drp_digest_refine_device", "drp_digest_diff_cells_device", "drp_select_refined_device",
     "drp_comm_id", "drp_comm_init_rank", "drp_comm_init_all", "drp_comm_destroy",
@@ -52,6 +53,9 @@ DIGEST_MAX_SUB_BITS = 8
 ORDER_KEEP_TIES = 1
 MERGE_NONE, MERGE_INSERTED, MERGE_REPLACED, MERGE_UNCHANGED, MERGE_STALE, MERGE_SKIPPED = 0, 1, 2, 3, 4, 5
 REPORT_KEEP_BLOBS = 1
+LOOKUP_NONE, LOOKUP_ABSENT, LOOKUP_BEHIND, LOOKUP_LEVEL, LOOKUP_AHEAD = 0, 1, 2, 3, 4
+LOOKUP_FOUND = (1 << LOOKUP_BEHIND) | (1 << LOOKUP_LEVEL) | (1 << LOOKUP_AHEAD)  # the emit_mask of a multi-get
+LOOKUP_REPLY_LACK = 0x100
 ORDER_TILE, ORDER_SCAN = 4096, 1024  # csrc/drp_kernels.h ORD_TILE, ORD_SCAN: pairs per sort workgroup, counts per scan block
 DIGEST_LDS_BITS = 10  # csrc/drp_kernels.h DIG_LDS_BITS: up to here dig_cells sums in LDS, above in global memory
 COMM_ID_BYTES = 128
@@ -163,6 +167,18 @@ class MergeReport(C.Structure):
                 ("reply_idx", P), ("n_reply", P), ("reply_cap", U64), ("reserved2", U64)]
 
 
+class Lookup(C.Structure):
+    """drp_lookup: a host struct of device pointers (out_rows: a host pointer to a ChangeSrc)."""
+    _fields_ = [("flags", U32), ("emit_mask", U32), ("verdict", P), ("hit_row", P), ("counts", P), ("lack_type", P),
+                ("out_rows", C.POINTER(ChangeSrc)), ("out_query", P), ("n_out", P), ("rows_cap", U64), ("reserved", U64),
+                ("reserved2", U64)]
+
+
+def lookup_bit(code):
+    """DRP_LOOKUP_BIT: the emit_mask bit of a verdict code."""
+    return 1 << code
+
+
 class DigestCell(C.Structure):
     """drp_digest_cell: the rows of one bucket and the sum of their fingerprints (mod 2^64)."""
     _fields_ = [("count", U64), ("sum", U64)]
@@ -238,6 +254,9 @@ def lib():
         L.drp_store_merge_report_device.argtypes = L.drp_store_merge_device.argtypes + [C.POINTER(MergeReport)]
         L.drp_store_merge_news_staged.argtypes = L.drp_store_merge_staged.argtypes
         L.drp_fanout_news_staged.argtypes = L.drp_fanout_staged.argtypes
+        L.drp_store_lookup_device.argtypes = L.drp_store_merge_device.argtypes + [C.POINTER(Lookup)]
+        L.drp_store_lookup_staged.argtypes = [P, C.POINTER(StoreDesc), C.POINTER(Filter), U32, P, U64, C.POINTER(U64),
+                                              C.POINTER(U64), C.POINTER(U64)]
         L.drp_store_compact.argtypes = [P, C.POINTER(StoreDesc), P, U64]
         L.drp_store_query.argtypes = [P, C.POINTER(StoreDesc), C.POINTER(StoreInfo)]
         L.drp_order_device.argtypes = [P, C.POINTER(ChangeSrc), P, U32, U64, P, U32, C.POINTER(ChangeSrc), P, P, P]
@@ -274,6 +293,7 @@ def lib():
                   "drp_set_fanout_latest_pass", "drp_store_init", "drp_store_merge_device", "drp_store_merge_staged",
                   "drp_store_compact", "drp_store_query", "drp_order_device", "drp_digest_device", "drp_digest_diff_device",
                   "drp_store_merge_report_device", "drp_store_merge_news_staged", "drp_fanout_news_staged",
+                  "drp_store_lookup_device", "drp_store_lookup_staged",
                   "drp_select_buckets_device", "drp_digest_refine_device", "drp_digest_diff_cells_device",
                   "drp_select_refined_device", "drp_stream_stats_from_results", "drp_device", "drp_comm_id", "drp_comm_init_rank",
                   "drp_comm_init_all", "drp_index_allgather", "drp_index_allgather_multi",
@@ -764,6 +784,59 @@ class Ctx:
         the staged batch that the last store_merge_news_staged found to be news (and its blobs)."""
         return self.fanout_staged(filters, cap, splice, out, blob_cap, _fn="drp_fanout_news_staged")
 
+    # ---- lookup: a read-only probe of the store by key --------------------------------------------
+    def store_lookup_device(self, store, wire_t, cols, n, filter=None, emit_mask=0, verdict_t=None, hit_row_t=None,
+                            counts_t=None, lack_type_t=None, out_rows=None, out_query_t=None, n_out_t=None, rows_cap=0,
+                            flags=0, lookup=True):
+        """drp_store_lookup_device: the candidates among the rows [0, n) of (wire_t, cols), as
+        latest_device takes them, looked up in the store by identity; nothing of the store is
+        written. Outputs (all optional CUDA tensors): verdict_t (uint8) and hit_row_t (int64) of n
+        entries, counts_t (int64, 5), lack_type_t (uint8, max_keys), out_rows a dict of
+        drp_change_src columns and out_query_t (int64) of rows_cap entries, n_out_t (int64, 1).
+        emit_mask: lookup_bit of LOOKUP_BEHIND / LEVEL / AHEAD. lookup=False passes a NULL drp_lookup.
+        Asynchronous."""
+        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
+        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
+                     tp(cols["flags"]), None)
+        lk = None
+        if lookup:
+            dst = ChangeSrc(*[tp(out_rows.get(k)) for k in SRC_COLS]) if out_rows is not None else None
+            lk = Lookup(flags, emit_mask, tp(verdict_t), tp(hit_row_t), tp(counts_t), tp(lack_type_t),
+                        C.pointer(dst) if dst is not None else None, tp(out_query_t), tp(n_out_t), rows_cap, 0, 0)
+        self.order_after_torch(wire_t)
+        rc = self.L.drp_store_lookup_device(self.h, C.byref(store.desc()), tp(wire_t), wire_t.numel(), C.byref(fr),
+                                            C.byref(co), n, C.byref(filter) if filter is not None else None,
+                                            C.byref(lk) if lk is not None else None)
+        _chk("drp_store_lookup_device", rc)
+        self.order_torch_after(wire_t)
+
+    def store_lookup_staged(self, store, filter=None, reply=LOOKUP_FOUND, cap=None, out=None):
+        """drp_store_lookup_staged over the batch last staged (decode_staged): returns (wire bytes,
+        rows in them, [the five verdict counts]). reply: an emit_mask (the store's rows of the queries
+        with those verdicts, in batch-row order) or LOOKUP_REPLY_LACK (every store row the sender of
+        the staged have-list lacks, in store order). cap=None: first a call that only sizes the
+        reply, then one with that capacity. A given cap that is too small raises
+        DrpError(DRP_E_CAPACITY) with .written = the size needed. out: a host uint8 array to write
+        into (at least cap bytes)."""
+        fp = C.byref(filter) if filter is not None else None
+        written, nrows, counts = U64(), U64(), (U64 * 5)()
+        self.order_after_torch(store.arena)
+        if cap is None:
+            rc = self.L.drp_store_lookup_staged(self.h, C.byref(store.desc()), fp, reply, None, 0, C.byref(written),
+                                                C.byref(nrows), counts)
+            if rc not in (DRP_OK, DRP_E_CAPACITY):
+                raise DrpError("drp_store_lookup_staged", rc)
+            cap = int(written.value)
+        buf = out if out is not None else np.zeros(max(16, cap), np.uint8)
+        rc = self.L.drp_store_lookup_staged(self.h, C.byref(store.desc()), fp, reply, _p(buf), cap, C.byref(written),
+                                            C.byref(nrows), counts)
+        if rc != DRP_OK:
+            e = DrpError("drp_store_lookup_staged", rc)
+            e.written = int(written.value)
+            raise e
+        return buf[:int(written.value)].tobytes(), int(nrows.value), [int(v) for v in counts]
+
     def store_compact(self, store, arena2_t):
         """drp_store_compact into arena2_t (a uint8 CUDA tensor). Asynchronous; the caller checks
         store_query(...).refused and, if 0, sets store.arena = arena2_t."""
@@ -1019,11 +1092,80 @@ class Store:
             self.arena, self.arena_bytes = a2, int(arena2_bytes)
         return i
 
-    def fanout_rows(self, filters, n=None, rows_cap=None):
+    def lookup(self, wire_t, cols, n, filter=None, emit=(LOOKUP_BEHIND, LOOKUP_LEVEL, LOOKUP_AHEAD), lack=False):
+        """store_lookup_device with the full set of outputs: {"verdict" (uint8, n entries: LOOKUP_*
+        per batch row), "hit_row" (int64, n: the store row, -1 for NONE and ABSENT), "counts" (int64,
+        5: rows per verdict)}; with emit (verdict codes; None or empty: no emission, the entries are
+        None) {"out_rows", "out_query", "n_out"}: the store's rows of the queries with those verdicts
+        as drp_change_src columns over the arena, their batch rows, and the count as an int64 tensor
+        of one element (rows_cap = n); with lack=True (else None) "lack_type": the uint8 column of
+        max_keys entries under which the store's view holds the rows the batch's sender lacks.
+        Nothing of the store is written. Asynchronous."""
+        import torch
+        dev = self.arena.device
+        z = lambda k, dt: torch.zeros(max(int(k), 1), dtype=dt, device=dev)
+        r = {"verdict": z(n, torch.uint8), "hit_row": z(n, torch.int64), "counts": z(5, torch.int64),
+             "lack_type": z(self.max_keys, torch.uint8) if lack else None, "out_rows": None, "out_query": None,
+             "n_out": None}
+        mask = 0
+        for code in emit or ():
+            mask |= lookup_bit(code)
+        if mask:
+            r["out_rows"] = {k: z(n, torch.int32 if k.endswith("_len") else torch.uint8 if k == "flags" else
+                                  torch.int64) for k in SRC_COLS}
+            r["out_query"], r["n_out"] = z(n, torch.int64), z(1, torch.int64)
+        self.ctx.store_lookup_device(self, wire_t, cols, n, filter, mask, r["verdict"], r["hit_row"], r["counts"],
+                                     r["lack_type"], r["out_rows"], r["out_query"], r["n_out"], n if mask else 0)
+        r["verdict"], r["hit_row"] = r["verdict"][:n], r["hit_row"][:n]
+        if lack:
+            r["lack_type"] = r["lack_type"][:self.max_keys]
+        return r
+
+    def get(self, keys):
+        """The multi-get: the store's current Change of each key. keys: a list of `key` or
+        `(subset, key)` byte strings (a key occurring twice is answered twice). The queries are built
+        here (key | subset end to end in one heap, type 1, change 0, no value: no wire, no decode);
+        one lookup that emits every found row and one encode_device with the arena as the heap.
+        Returns (hit_row, wire bytes): an int64 numpy array, the store row of each key or -1 where the
+        store does not hold it, and the found rows in query order as change frames."""
+        import torch
+        n = len(keys)
+        dev = self.arena.device
+        q = alloc_host_outputs(max(n, 1))
+        heap = bytearray()
+        for i, k in enumerate(keys):
+            sub, key = k if isinstance(k, tuple) else (None, k)
+            q["payload_off"][i], q["type"][i] = len(heap), TYPE_CHANGE
+            q["key_len"][i], q["subset_off"][i] = len(key), len(key)
+            heap += key
+            if sub is not None:
+                q["subset_len"][i], q["flags"][i] = len(sub), F_SUBSET
+                heap += sub
+            q["payload_len"][i] = len(heap) - int(q["payload_off"][i])
+            q["value_off"][i] = q["payload_len"][i]
+        signed = {np.dtype(np.uint64): np.int64, np.dtype(np.uint32): np.int32, np.dtype(np.uint8): np.uint8}
+        cols = {k: torch.from_numpy(v.view(signed[v.dtype])).to(dev) for k, v in q.items()}
+        heap_t = torch.from_numpy(np.frombuffer(bytes(heap) or b"\0", np.uint8).copy()).to(dev)[:len(heap)]
+        r = self.lookup(heap_t, cols, n)
+        base = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), r["n_out"][:1]])
+        wire = self._encode_outputs(r["out_rows"], base, self._view(), 1)[0]
+        return r["hit_row"].cpu().numpy().copy(), wire
+
+    def sync_reply(self, wire_t, cols, n, filter=None):
+        """The answer to a have-list (wire_t, cols, n: a batch of Changes whose values do not matter,
+        the sender's keys and versions): one lookup with lack_type, then the existing fan-out
+        (fanout_rows) and encoder over the store's view with that column in the type column's place.
+        Returns the bytes of the store's rows the sender lacks (those it did not name, and those it
+        named with a smaller change), under `filter`, in store order."""
+        r = self.lookup(wire_t, cols, n, emit=None, lack=True)
+        rows, base = self.fanout_rows([filter], type_t=r["lack_type"])
+        return self._encode_outputs(rows, base, self._view(), 1)[0]
+
+    def fanout_rows(self, filters, n=None, rows_cap=None, type_t=None):
         """The existing fanout_device over the store's view, rows [0, n) (default max_keys: the rows
         past info.rows are no Changes). Returns (out_rows, row_base_t): drp_change_src columns of
         rows_cap entries (default len(filters) * n) and the int64 tensor of len(filters) + 1 bounds.
-        Asynchronous."""
+        type_t: a column to take the type column's place (lookup's lack_type). Asynchronous."""
         import torch
         n = self.max_keys if n is None else int(n)
         K = len(filters)
@@ -1033,7 +1175,8 @@ class Store:
                                                    torch.uint8 if k == "flags" else torch.int64), device=dev)
                 for k in SRC_COLS}
         base = torch.zeros(K + 1, dtype=torch.int64, device=dev)
-        self.ctx.fanout_device(self.arena[:self.arena_bytes] if self.arena_bytes else self.arena[:0], self.cols, n,
+        view = self.cols if type_t is None else dict(self.cols, type=type_t)
+        self.ctx.fanout_device(self.arena[:self.arena_bytes] if self.arena_bytes else self.arena[:0], view, n,
                                filters, rows, cap, None, base)
         return rows, base
 

@@ -37,6 +37,11 @@
  *       -> no reference counterpart: that merge saying per batch row what became of it, as a type
  *          column under which the batch holds exactly the Changes that changed the store (a relay
  *          forwarding only what was news to it), and the store's rows a stale sender lacks.
+ *   drp_store_lookup_device / drp_store_lookup_staged
+ *       -> no reference counterpart: a read-only probe of that store by identity, a verdict per
+ *          queried key from its `change` against the stored one, the found rows for the encoder (a
+ *          multi-get), and a type column under which the store holds exactly the rows the sender of
+ *          a have-list lacks (a peer with a plain list of keys and versions catching up).
  *   drp_order_device
  *       -> no reference counterpart: the rows of every fan-out output in ascending `change` (schema
  *          messages/schema.proto:1-8), cut to a per-peer limit (a catch-up a peer can resume or page).
@@ -685,6 +690,97 @@ int drp_store_merge_news_staged(drp_ctx *ctx, const drp_store *s, const drp_filt
 int drp_fanout_news_staged(drp_ctx *ctx, const drp_filter *filters, uint32_t nfilters, uint8_t *out, uint64_t cap,
                            uint64_t *out_off, uint64_t *n_selected, uint64_t *blob_row, uint64_t *blob_pos,
                            uint64_t blob_cap, uint64_t *n_blobs);
+
+/* ---- lookup: a read-only probe of the store by key (multi-get, have-list sync) --------------- */
+/* Every call above either writes the store or scans all max_keys rows of it. Two questions a hub is
+ * asked all the time need neither: "give me the current Change of these keys" (a multi-get: equality
+ * on the identity, not a key prefix, and any number of keys per call), and "here is what I hold, send
+ * what I lack" (a peer's have-list: Changes without values, that is identities and versions, which a
+ * merge would write into the store in the values' place). The lookup probes the identity table as a
+ * merge does and writes nothing into the store. No reference counterpart (the reference has no relay);
+ * the fields read are subset, key and change of messages/schema.proto:1-8.
+ *   Queries: exactly the candidates of drp_latest_device for (bytes, nbytes, frames, cols, n, filter):
+ * the rows drp_select_device selects whose key range, and with DRP_F_SUBSET whose subset range, lies
+ * inside [0, nbytes). Every other row is DRP_LOOKUP_NONE and nothing of it is read; the value is
+ * never read for any row. frames / cols need not come from a decode: any columns of that layout over
+ * any device bytes do (a list of keys laid end to end, type = DRP_TYPE_CHANGE, is a batch of queries).
+ *   The identity is the store section's. verdict[r] compares the query's `change` with the store
+ * row's, unsigned 64-bit: ABSENT (no row of this identity), BEHIND (the stored change is smaller: the
+ * hub lacks the query's), LEVEL (equal), AHEAD (the stored change is greater: the sender lacks the
+ * store's row). hit_row[r] is the store row, UINT64_MAX for NONE and ABSENT. counts[code] is the
+ * number of rows in [0, n) with that verdict. Queries are independent: the same identity may be
+ * queried many times, with different `change`, and each row gets its own verdict; nothing is
+ * de-duplicated.
+ *   Read-only: no byte of the store changes (the arena, the columns, the table and the info record
+ * stay as they were). info is not read: rows are bounded by max_keys, and the table names only rows
+ * in use.
+ *   Emission, with out_rows: the queries whose verdict's bit is set in emit_mask, in batch-row order
+ * (a stable compaction); for each the store's row of that identity, written as drp_select_device
+ * writes that row over the store's view: offsets absolute into s->arena, flags masked to DRP_F_SUBSET
+ * | DRP_F_VALUE; out_query[j] is the batch row of emitted row j. *n_out always carries the true
+ * count; if it exceeds rows_cap nothing is written to the arrays (drp_fanout_device's rows_cap
+ * convention), otherwise entries at or beyond it are left untouched. drp_encode_device(ctx, out_rows,
+ * s->arena, s->arena_bytes, *n_out, ...) gives the bytes; the offsets hold until the next
+ * drp_store_compact. A multi-get is emit_mask = BEHIND | LEVEL | AHEAD; "only if newer than mine" is
+ * emit_mask = AHEAD.
+ *   lack_type, a replacement for s->frames.type (max_keys entries): lack_type[j] = s->frames.type[j],
+ * except 0 where at least one query hit row j with a `change` greater than or equal to the stored
+ * one. Rows no query names stay Changes; rows at or beyond info.rows are 0 as in frames.type. So
+ * (s->arena, s->arena_bytes, {payload_off, payload_len, lack_type}, &s->cols, max_keys) is a decoded
+ * batch holding exactly the store's rows the sender of the have-list lacks: drp_select_device,
+ * drp_fanout_device, drp_order_device behind them, drp_digest_device and the encoder run over it
+ * unchanged, and no other column is copied. The outcome does not depend on the order of the queries
+ * (the only writes after the copy of the type column are zeros). lack_type == s->frames.type
+ * (aliasing) is DRP_E_INVAL.
+ *   Entries of verdict / hit_row at or beyond n and of lack_type at or beyond max_keys are left
+ * untouched.
+ *   Device pointers only; asynchronous on drp_stream(ctx), no host synchronisation inside; the result
+ * is a function of the input alone. drp_set_latest_hash_mask applies: a lookup must see the mask the
+ * store has seen.
+ *   DRP_E_INVAL: drp_store_merge_device's cases; a NULL lk; unknown flags; an emit_mask bit other than
+ * those of BEHIND, LEVEL and AHEAD; out_rows without n_out; with rows_cap > 0 a NULL array in
+ * out_rows; the aliasing above. (Those of lk are checked before the ctx is used.) Scratch from the
+ * ctx's (DRP_E_NOMEM if it cannot be had): 512 bytes of filter strings, 12 bytes per batch row (only
+ * with n_out: the emitted queries' store rows and ranks) and 48 bytes per 256 rows (the workgroups'
+ * counts). */
+#define DRP_LOOKUP_NONE   0 /* the row is no query */
+#define DRP_LOOKUP_ABSENT 1 /* the store holds no row of this identity */
+#define DRP_LOOKUP_BEHIND 2 /* it does, with a smaller `change` than the query's (the hub lacks the query's) */
+#define DRP_LOOKUP_LEVEL  3 /* equal `change` */
+#define DRP_LOOKUP_AHEAD  4 /* the store's `change` is greater (the sender lacks the store's row) */
+#define DRP_LOOKUP_BIT(code) (1u << (code))
+
+typedef struct drp_lookup { /* HOST struct of DEVICE pointers, read before the call returns; 88 bytes */
+  uint32_t flags;     /* 0 (unknown bits: DRP_E_INVAL) */
+  uint32_t emit_mask; /* DRP_LOOKUP_BIT of BEHIND / LEVEL / AHEAD; any other bit: DRP_E_INVAL */
+  uint8_t *verdict;   /* n entries, may be NULL */
+  uint64_t *hit_row;  /* n entries, may be NULL: the store row, UINT64_MAX for NONE and ABSENT */
+  uint64_t *counts;   /* 5 entries, may be NULL: rows [0, n) per verdict code */
+  uint8_t *lack_type; /* max_keys entries, may be NULL */
+  const drp_change_src *out_rows; /* HOST pointer to a struct of writable device arrays, rows_cap entries each; NULL: no emission */
+  uint64_t *out_query; /* rows_cap entries, may be NULL: the batch row of each emitted row */
+  uint64_t *n_out;     /* one entry; required with out_rows */
+  uint64_t rows_cap;
+  uint64_t reserved;
+  uint64_t reserved2; /* neither is read */
+} drp_lookup;
+
+int drp_store_lookup_device(drp_ctx *ctx, const drp_store *s, const uint8_t *bytes, uint64_t nbytes,
+                            const drp_frames *frames, const drp_changes *cols, uint64_t n,
+                            const drp_filter *filter, const drp_lookup *lk);
+/* That lookup over the delivered rows of the batch last staged (the rows, validity rules and
+ * DRP_E_INVAL cases of drp_latest_staged; `filter` says which of them are queries; the same bytes in
+ * every drp_set_blob_skip mode), and its reply, encoded with the arena as the heap. reply is an emit_mask: the emitted rows, in batch-row
+ * order; or DRP_LOOKUP_REPLY_LACK alone: every store row under lack_type, in store-row order
+ * (drp_select_device with a NULL filter over that view; the column lives in a buffer of the ctx).
+ * Any other value is DRP_E_INVAL. Synchronous; out is a host or device pointer; *n_rows is the
+ * reply's rows, counts_host (HOST, 5 entries, may be NULL) receives the verdict counts. DRP_E_CAPACITY
+ * as drp_relay_staged: *written is the size needed and nothing is written to out. The staged batch
+ * stays valid. */
+#define DRP_LOOKUP_REPLY_LACK 0x100u
+int drp_store_lookup_staged(drp_ctx *ctx, const drp_store *s, const drp_filter *filter, uint32_t reply,
+                            uint8_t *out, uint64_t cap, uint64_t *written, uint64_t *n_rows,
+                            uint64_t *counts_host /* 5, may be NULL */);
 
 /* ---- ordered catch-up: a fan-out's outputs in `change` order, with a per-peer limit ---------- */
 /* Every output of the select, fan-out and latest calls above is in row order; over a store that is

@@ -103,6 +103,21 @@ probe, and the host relay through drp_relay_staged against the host round trip i
               library and binding (DRP_LIB, DRP_PY); --news-baseline reads such a file, and the result
               says per batch whether this build's medians lie inside the parent's own min-max spread.
 
+  lookup      (--lookup-out, default profiles/relay/lookup_bench.json; no other leg runs) The store leg's
+              merge sequences (timed again: the merge shares its probe with the lookup) and its final
+              store. HIP events, three warm-up rounds and --iters timed ones: drp_store_lookup_device
+              over 64, 65,536 and 1.25M keys laid end to end (columns built here, no wire), half of
+              them held: the verdicts alone, the multi-get (every found row emitted) and the
+              drp_encode_device of its rows, every hit row checked to hold the queried key; then a
+              have-list of every key at change 50 with lack_type, and the drp_select_device and
+              drp_encode_device over the store's view under that column (what Store.sync_reply
+              composes). --lookup-baseline-out: the merge sequences and what the parent commit can do
+              for a point read (one drp_fanout_device over the store with the 64 keys as 64
+              DRP_SEL_KEY_PREFIX filters, and the encode), to be taken with the parent commit's
+              library and binding (DRP_LIB, DRP_PY); --lookup-baseline reads such a file, and the
+              result says per batch whether this build's merge medians lie inside the parent's own
+              min-max spread.
+
 Prints one JSON line (and writes it to --out). Needs an MI355X: there is no CPU path.
 
   hipcc -O3 --offload-arch=gfx950 scripts/probe_bw.hip -o exp/probe_bw
@@ -1557,6 +1572,156 @@ def digest_refine_leg(ctx, drp_amd, torch, frames, iters, parent=None):
     return res
 
 
+# ---- lookup: point reads and the have-list against the store -----------------------------------------
+
+LOOKUP_SIZES = (64, 65_536, 1_250_000)
+LOOKUP_ABSENT_ID = 2_000_000_000  # (ten digits, above every key id of the stream)
+HAVE_CHANGE = 50                  # the have-list's version: about half of the store lies above it
+
+
+def _lookup_store(ctx, drp_amd, torch, frames, seqs):
+    """The store leg's merge sequences, timed ([seq][batch] ms, one warm-up sequence), and its final
+    store: the last sequence's, compacted. Through calls every commit with the store has."""
+    dev = torch.device("cuda", 0)
+    key_ids, wire_t, cols, n, m = _store_input(ctx, drp_amd, torch, frames)
+    ids = np.unique(key_ids)
+    keys = int(len(ids))
+    timed = _news_timed(ctx, torch, dev)
+    merges, store = [], None
+    for it in range(seqs + 1):
+        store = None
+        torch.cuda.empty_cache()
+        store = drp_amd.Store(ctx, keys, 80 * (keys + STORE_BATCHES * m) // 2)
+        tm = [timed(lambda: ctx.store_merge_device(store, wire_t, {k: v[b * m:] for k, v in cols.items()}, m))
+              for b in range(STORE_BATCHES)]
+        if it:
+            merges.append(tm)
+    before = store.query()
+    assert before.rows == keys and before.refused == 0, (before.rows, keys)
+    a2 = torch.zeros(before.arena_used, dtype=torch.uint8, device=dev)
+    ctx.store_compact(store, a2)
+    assert store.query().refused == 0
+    store.arena, store.arena_bytes = a2, a2.numel()
+    del wire_t, cols
+    torch.cuda.empty_cache()
+    return store, ids, n, m, _per_batch(merges)
+
+
+def _point_keys(ids, nq, seed=11):
+    """nq key ids, half of them held (a seeded sample of the store's) and half not, shuffled."""
+    rng = np.random.default_rng(seed)
+    held = rng.choice(ids, nq // 2, replace=False)
+    q = np.concatenate([held, LOOKUP_ABSENT_ID + np.arange(nq - nq // 2, dtype=np.int64)])
+    rng.shuffle(q)
+    return q, nq // 2
+
+
+def _key_digits(q):
+    a = np.zeros((len(q), 10), np.uint8)
+    for k in range(10):
+        a[:, k] = 48 + (q // 10 ** (9 - k)) % 10
+    return a
+
+
+def lookup_baseline(ctx, drp_amd, torch, frames, seqs, iters):
+    """What the parent commit can do for a point read: one drp_fanout_device over the store with 64
+    DRP_SEL_KEY_PREFIX filters (the 64-key lookup's keys, whole: a prefix of ten digits is the key) and
+    the encode of the rows found; and the merge sequences. No call of this commit."""
+    dev = torch.device("cuda", 0)
+    store, ids, n, m, merge_ms = _lookup_store(ctx, drp_amd, torch, frames, seqs)
+    q, held = _point_keys(ids, 64)
+    flt = [drp_amd.make_filter(key_prefix=bytes(d)) for d in _key_digits(q)]
+    stat = _timers(ctx, torch, dev, iters)
+    rows = _row_tensors(torch, dev, 64)
+    rb_t = torch.zeros(65, dtype=torch.int64, device=dev)
+    foff = torch.zeros(65, dtype=torch.int64, device=dev)
+    out = torch.zeros(64 * 86, dtype=torch.uint8, device=dev)
+    tf = stat(lambda: ctx.fanout_device(store.arena, store.cols, store.max_keys, flt, rows, 64, None, rb_t))
+    te = stat(lambda: ctx.encode_device(rows, store.arena, held, foff, out, out.numel()))
+    assert int(rb_t.cpu()[64]) == held and int(foff[held].cpu()) == held * 86, "point read rows"
+    return {"bench": "relay_lookup_baseline", "frames": n, "batch_rows": m, "keys": int(len(ids)), "seqs": seqs,
+            "iters": iters, "merge_ms": merge_ms,
+            "point_read_64": {"filters": 64, "rows_out": held, "fanout_ms": tf, "encode_ms": te,
+                              "total_ms_median": tf["median"] + te["median"]}}
+
+
+def _query_cols(torch, dev, nq, change):
+    """Host-built query columns over a heap of ten-digit keys laid end to end: no wire, no decode."""
+    i64 = lambda v: torch.full((nq,), v, dtype=torch.int64, device=dev)
+    i32 = lambda v: torch.full((nq,), v, dtype=torch.int32, device=dev)
+    return {"payload_off": torch.arange(nq, dtype=torch.int64, device=dev) * 10, "payload_len": i32(10),
+            "type": torch.ones(nq, dtype=torch.uint8, device=dev), "flags": torch.zeros(nq, dtype=torch.uint8, device=dev),
+            "key_off": i32(0), "key_len": i32(10), "subset_off": i32(10), "subset_len": i32(0), "value_off": i32(10),
+            "value_len": i32(0), "change": i64(change), "from": i64(0), "to": i64(0)}
+
+
+def lookup_leg(ctx, drp_amd, torch, frames, seqs, iters, parent=None):
+    dev = torch.device("cuda", 0)
+    store, ids, n, m, merge_ms = _lookup_store(ctx, drp_amd, torch, frames, seqs)
+    keys = int(len(ids))
+    stat = _timers(ctx, torch, dev, iters)
+    ch = store.cols["change"][:keys].cpu().numpy()
+    res = {"frames": n, "batch_rows": m, "keys": keys, "seqs": seqs, "iters": iters, "merge_ms": merge_ms,
+           "sum_merge_ms": sum(x["median"] for x in merge_ms), "point": {}}
+    z = lambda k, dt: torch.zeros(k, dtype=dt, device=dev)
+    for nq in LOOKUP_SIZES:
+        q, held = _point_keys(ids, nq)
+        heap_t = torch.from_numpy(_key_digits(q).reshape(-1)).to(dev)
+        qc = _query_cols(torch, dev, nq, HAVE_CHANGE)
+        verdict, hit, counts, oq, n_out = z(nq, torch.uint8), z(nq, torch.int64), z(5, torch.int64), z(nq, torch.int64), z(1, torch.int64)
+        rows = _row_tensors(torch, dev, nq)
+        foff, out = z(held + 1, torch.int64), z(held * 86, torch.uint8)
+        t_verdict = stat(lambda: ctx.store_lookup_device(store, heap_t, qc, nq, None, 0, verdict, hit, counts))
+        t_get = stat(lambda: ctx.store_lookup_device(store, heap_t, qc, nq, None, drp_amd.LOOKUP_FOUND, verdict, hit, counts,
+                                                     None, rows, oq, n_out, nq))
+        t_enc = stat(lambda: ctx.encode_device(rows, store.arena, held, foff, out, out.numel()))
+        cnt = [int(v) for v in counts.cpu()]
+        assert cnt[0] == 0 and cnt[1] == nq - held and sum(cnt) == nq and int(n_out.cpu()[0]) == held, (cnt, held)
+        found = hit.cpu().numpy()
+        assert int((found >= 0).sum()) == held and int(foff[held].cpu()) == held * 86, "multi-get rows"
+        # every hit row holds the queried key
+        at = store.cols["payload_off"].cpu().numpy()[found[found >= 0]]
+        got = store.arena.cpu().numpy()[at[:, None] + np.arange(10)[None, :]]
+        assert np.array_equal(got, _key_digits(q)[found >= 0]), "hit rows"
+        res["point"][f"n{nq}"] = {"queries": nq, "held": held, "verdict_ms": t_verdict, "multi_get_ms": t_get,
+                                  "encode_ms": t_enc, "out_bytes": held * 86,
+                                  "total_ms_median": t_get["median"] + t_enc["median"]}
+        print("lookup", nq, res["point"][f"n{nq}"], file=sys.stderr, flush=True)
+        heap_t = qc = rows = foff = out = None
+        torch.cuda.empty_cache()
+    # the have-list: every key of the store at change HAVE_CHANGE, then the select and encode of what the sender lacks
+    nq = keys
+    heap_t = torch.from_numpy(_key_digits(ids).reshape(-1)).to(dev)
+    qc = _query_cols(torch, dev, nq, HAVE_CHANGE)
+    counts, lack = z(5, torch.int64), z(keys, torch.uint8)
+    t_have = stat(lambda: ctx.store_lookup_device(store, heap_t, qc, nq, None, 0, None, None, counts, lack))
+    lacking = int((ch > HAVE_CHANGE).sum())
+    cnt = [int(v) for v in counts.cpu()]
+    assert cnt == [0, 0, int((ch < HAVE_CHANGE).sum()), int((ch == HAVE_CHANGE).sum()), lacking], cnt
+    assert int(lack.count_nonzero().cpu()) == lacking, "lack_type"
+    rows = _row_tensors(torch, dev, lacking)
+    nsel = z(1, torch.int64)
+    foff, out = z(lacking + 1, torch.int64), z(lacking * 86, torch.uint8)
+    view = dict(store.cols, type=lack)
+    t_sel = stat(lambda: ctx.select_device(store.arena, view, keys, None, rows, None, nsel))
+    t_enc = stat(lambda: ctx.encode_device(rows, store.arena, lacking, foff, out, out.numel()))
+    assert int(nsel.cpu()[0]) == lacking and int(foff[lacking].cpu()) == lacking * 86, "sync reply rows"
+    res["have_list"] = {"queries": nq, "change": HAVE_CHANGE, "lacking_rows": lacking, "lookup_ms": t_have,
+                        "select_ms": t_sel, "encode_ms": t_enc, "out_bytes": lacking * 86,
+                        "total_ms_median": t_have["median"] + t_sel["median"] + t_enc["median"]}
+    print("have-list", res["have_list"], file=sys.stderr, flush=True)
+    if parent is not None:
+        assert parent["frames"] == n and parent["keys"] == keys
+        res["parent_merge_ms"] = parent["merge_ms"]
+        res["sum_parent_merge_ms"] = sum(x["median"] for x in parent["merge_ms"])
+        res["merge_inside_parent_spread"] = [p["min"] <= x["median"] <= p["max"]
+                                             for x, p in zip(merge_ms, parent["merge_ms"])]
+        res["parent_point_read_64"] = parent["point_read_64"]
+        res["parent_point_read_over_multi_get_64"] = (parent["point_read_64"]["total_ms_median"] /
+                                                      res["point"]["n64"]["total_ms_median"])
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20_000_000)
@@ -1607,6 +1772,11 @@ def main():
     ap.add_argument("--order-baseline-out", default=None,
                     help="only the order leg's yardstick (fan-out and encode over the final store) to this file")
     ap.add_argument("--order-baseline", default=None, help="such a file of the parent commit, read into the order leg's result")
+    ap.add_argument("--lookup-out", nargs="?", default=None, const=os.path.join(ROOT, "profiles", "relay", "lookup_bench.json"),
+                    help="run the lookup leg alone and write its JSON line here")
+    ap.add_argument("--lookup-baseline-out", default=None,
+                    help="only the point read by fan-out and the merge sequences (no call of this commit), written here")
+    ap.add_argument("--lookup-baseline", default=None, help="such a file of the parent commit, read into the lookup leg's result")
     a = ap.parse_args()
     if a.digest_only and not a.digest_out:
         ap.error("--digest-only needs --digest-out")
@@ -1625,6 +1795,21 @@ def main():
     torch.cuda.init()
     import _streams as S
     import drp_amd
+    if a.lookup_baseline_out:
+        with drp_amd.Ctx(0) as ctx:
+            base = lookup_baseline(ctx, drp_amd, torch, a.frames, a.store_seqs, a.iters)
+        with open(a.lookup_baseline_out, "w") as f:
+            f.write(json.dumps(base) + "\n")
+        print(json.dumps(base))
+        return
+    if a.lookup_out:
+        parent = json.loads(open(a.lookup_baseline).read()) if a.lookup_baseline else None
+        with drp_amd.Ctx(0) as ctx:
+            lk = {"bench": "relay_lookup", "device": lookup_leg(ctx, drp_amd, torch, a.frames, a.store_seqs, a.iters, parent)}
+        with open(a.lookup_out, "w") as f:
+            f.write(json.dumps(lk) + "\n")
+        print(json.dumps(lk))
+        return
     if a.news_baseline_out:
         with drp_amd.Ctx(0) as ctx:
             base = news_baseline(ctx, drp_amd, torch, a.frames, a.store_seqs, a.iters)
