@@ -473,6 +473,13 @@ hipError_t drp_launch_store_init(const drp::StoreDev *S, hipStream_t st);
 uint64_t drp_store_merge_scratch_bytes(uint64_t n);
 hipError_t drp_launch_store_merge(const drp::StoreMerge *M, const drp::StoreReport *R, void *scratch, hipStream_t st);
 uint64_t drp_store_blocks(uint64_t n);  // the workgroups of ST_BLK winners a merge of n rows runs (>= 1)
+// the load (include/drp.h "store lifecycle") of the rows in M, a select's and taken to be new: the
+// merge's steps with stl_plan in st_lookup's place (the same state in `scratch`), then, with `clash`
+// (device, null: none), the self-check of the rows it added. The rehash: the table rebuilt from the
+// rows in use under S->hash_mask, with `report` (device, two words, null: none) the invalid rows and
+// the self-check of all of them; no scratch
+hipError_t drp_launch_store_load(const drp::StoreMerge *M, uint64_t *clash, void *scratch, hipStream_t st);
+hipError_t drp_launch_store_rehash(const drp::StoreDev *S, uint64_t *report, hipStream_t st);
 // the lookup Q (its state is placed in `scratch`, drp_store_lookup_scratch_bytes(n) bytes; fb: the
 // filter's byte strings, as drp_launch_select takes them): nothing of the store is written
 uint64_t drp_store_lookup_scratch_bytes(uint64_t n);

@@ -5,7 +5,8 @@
 // drp_fanout_latest_device / drp_fanout_latest_staged (latest per key under each), and the store
 // (drp_store_*: the latest-per-key step, then the merge into caller-owned device memory; with a
 // report, drp_store_merge_report_device, drp_store_merge_news_staged / drp_fanout_news_staged; the
-// read-only probe by key, drp_store_lookup_device / drp_store_lookup_staged), and the
+// read-only probe by key, drp_store_lookup_device / drp_store_lookup_staged; the load of rows known
+// to be new and the table's rebuild, drp_store_load_device / drp_store_rehash_device), and the
 // digest calls (drp_digest_device, drp_digest_diff_device, drp_select_buckets_device, and their second
 // level drp_digest_refine_device, drp_digest_diff_cells_device, drp_select_refined_device), and the ordered
 // catch-up (drp_order_device). The kernels are in drp_select.hip, drp_latest.hip, drp_fanout.hip,
@@ -394,9 +395,11 @@ static bool store_dev(const drp_ctx *c, const drp_store *s, StoreDev &D) {
 // latest-per-key step into winner rows in the ctx's scratch, then drp_store.hip's steps over them.
 // Scratch: drp_launch_latest's words, the winners' count, the staged piece table, the winner rows
 // (ten columns of n entries), the merge's state; behind it, only when the report `rep` (NULL: none)
-// asks for them, the winners' source rows and the workgroups' stale counts
+// asks for them, the winners' source rows and the workgroups' stale counts.
+// With `load` the load of include/drp.h "store lifecycle" (no report): the plain select in the
+// latest's place, with its smaller scratch, and drp_launch_store_load over its rows
 static int store_merge(drp_ctx *c, const StoreDev &D, const RowSrc *caller, const drp_filter *filter,
-                       const drp_merge_report *rep = nullptr) {
+                       const drp_merge_report *rep = nullptr, bool load = false, uint64_t *clash = nullptr) {
   SelectParams P = {};
   SelectBytes fb = {};
   if (const int rc = select_filter(filter, P.f, fb.b)) return rc;
@@ -404,7 +407,7 @@ static int store_merge(drp_ctx *c, const StoreDev &D, const RowSrc *caller, cons
   const auto &S = c->staged;
   const uint64_t n = caller ? caller->n : S.good, np = caller ? 0 : S.pieces.size();
   const bool by_row = rep && (rep->outcome || rep->news_type), reply = rep && rep->n_reply;
-  const size_t o_cnt = al(drp_latest_scratch_bytes(n)), o_piece = o_cnt + 256, o_rows = o_piece + al(2 * np * 8),
+  const size_t o_cnt = al(select_scratch(n, !load)), o_piece = o_cnt + 256, o_rows = o_piece + al(2 * np * 8),
                col = al(n * 8), o_state = o_rows + 10 * col, o_src = o_state + drp_store_merge_scratch_bytes(n),
                o_stale = o_src + (by_row ? col : 0), o_end = o_stale + (reply ? al(drp_store_blocks(n) * 8) : 0);
   if (!c->scratch.ensure(o_end)) return DRP_E_NOMEM;
@@ -413,7 +416,7 @@ static int store_merge(drp_ctx *c, const StoreDev &D, const RowSrc *caller, cons
   const drp_change_src rows = carve_rows(c->scratch, o_rows, col);
   P.out = row_out(&rows, by_row ? c->scratch.at<uint64_t>(o_src) : nullptr);
   P.n_selected = c->scratch.at<uint64_t>(o_cnt);
-  CHK(drp_launch_latest(&P, &fb, c->latest_hash_mask, c->scratch.p, c->st));
+  CHK(launch_select(c, P, fb, !load));
   StoreMerge M = {};
   M.s = D;
   M.bytes = P.src.bytes;
@@ -421,6 +424,10 @@ static int store_merge(drp_ctx *c, const StoreDev &D, const RowSrc *caller, cons
   M.w = rows;
   M.nw = P.n_selected;
   M.n = n;
+  if (load) {
+    CHK(drp_launch_store_load(&M, clash, c->scratch.at<char>(o_state), c->st));
+    return DRP_OK;
+  }
   StoreReport R = {};
   if (by_row || reply) {
     R.flags = rep->flags;
@@ -655,6 +662,24 @@ int drp_store_merge_report_device(drp_ctx *c, const drp_store *s, const uint8_t 
   if (!cols_ok(frames, cols, n) || !report_ok(report, frames->type)) return DRP_E_INVAL;
   const RowSrc R = caller_src(bytes, nbytes, frames, cols, n);
   return store_merge(c, D, &R, filter, report);
+}
+
+int drp_store_load_device(drp_ctx *c, const drp_store *s, const uint8_t *bytes, uint64_t nbytes,
+                          const drp_frames *frames, const drp_changes *cols, uint64_t n, const drp_filter *filter,
+                          uint64_t *clash) {
+  StoreDev D = {};
+  if (!c || !s || !frames || !cols || (!bytes && nbytes) || !store_dev(c, s, D)) return DRP_E_INVAL;
+  if (!cols_ok(frames, cols, n)) return DRP_E_INVAL;
+  const RowSrc R = caller_src(bytes, nbytes, frames, cols, n);
+  return store_merge(c, D, &R, filter, nullptr, true, clash);
+}
+
+int drp_store_rehash_device(drp_ctx *c, const drp_store *s, uint64_t *report) {
+  StoreDev D = {};
+  if (!c || !s || !store_dev(c, s, D)) return DRP_E_INVAL;
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  CHK(drp_launch_store_rehash(&D, report, c->st));
+  return DRP_OK;
 }
 
 // drp_store_merge_staged, or with `news` drp_store_merge_news_staged: the merge's news column, blobs

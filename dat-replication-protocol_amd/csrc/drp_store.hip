@@ -36,6 +36,8 @@
 // writes nothing into the store: see "lookup" below.
 // The compact is the same shape: the live allocations' sizes and their prefix, the scan, the verdict
 // with the commit (nothing later reads the old totals), the copy.
+// The load and the rehash (include/drp.h "store lifecycle") are the merge's steps around two plans of
+// their own, stl_plan and strh_enter, and one check, st_selfcheck: see "lifecycle" below.
 #include "drp_select.h"  // (wire_has, bytes_eq; drp_device.h: xxh, ld_agent, the wave scans)
 
 namespace drp {
@@ -44,6 +46,15 @@ enum : uint32_t { ST_NONE = 0, ST_INSERT = 1, ST_REPLACE = 2, ST_UNCHANGED = 3, 
 
 __device__ __forceinline__ uint32_t st_r16(uint32_t len) { return (len + 15u) & ~15u; }  // (len <= 2^32 - 16)
 
+// store row r's payload lies inside the arena, at `at`, and holds an identity of `ident` bytes (key |
+// subset)
+__device__ __forceinline__ bool st_payload_ok(const StoreDev &S, uint64_t r, uint64_t ident, uint64_t &at) {
+  at = S.payload_off[r];
+  const uint64_t len = S.payload_len[r];
+  if (len > S.arena_bytes || at > S.arena_bytes - len || ident > len) return false;
+  return true;
+}
+
 // store row r (named by a table word) has this identity; a row outside the store, or whose payload
 // leaves the arena (a table that no drp_store_init cleared), matches nothing and is never read
 __device__ __forceinline__ bool st_same(const StoreDev &S, uint64_t r, bool has, const uint8_t *key, uint32_t klen,
@@ -51,8 +62,8 @@ __device__ __forceinline__ bool st_same(const StoreDev &S, uint64_t r, bool has,
   if (r >= S.max_keys) return false;
   const drp_changes &c = S.cols;
   if (((c.flags[r] & DRP_F_SUBSET) != 0) != has || c.key_len[r] != klen || c.subset_len[r] != slen) return false;
-  const uint64_t at = S.payload_off[r], len = S.payload_len[r];
-  if (len > S.arena_bytes || at > S.arena_bytes - len || (uint64_t)klen + slen > len) return false;
+  uint64_t at;
+  if (!st_payload_ok(S, r, (uint64_t)klen + slen, at)) return false;
   const uint8_t *a = S.arena + at;
   return bytes_eq(a, key, klen) && bytes_eq(a + klen, sub, slen);
 }
@@ -94,55 +105,36 @@ __device__ __forceinline__ uint64_t st_probe(const StoreDev &S, uint64_t h, bool
   return ~0ull;
 }
 
-__global__ __launch_bounds__(ST_BLK) void st_lookup_kernel(const StoreMerge M) {
+// winner i of M as the plans read it (an absent field has length 0), and whether it can be stored:
+// its three ranges inside the wire, its payload within an allocation's 2^32 - 16 bytes. One that
+// cannot is never read (a latest's winner was a candidate, so its key and subset are inside; a
+// select's row, and any winner's value, need not be)
+struct StWinner {
+  uint64_t koff, soff, voff, plen;
+  uint32_t fl, klen, slen, vlen;
+  bool has, ok;
+};
+__device__ __forceinline__ StWinner st_winner(const StoreMerge &M, uint64_t i) {
+  StWinner w;
+  w.fl = M.w.flags[i];
+  w.has = (w.fl & DRP_F_SUBSET) != 0;
+  const bool hv = (w.fl & DRP_F_VALUE) != 0;
+  w.koff = M.w.key_off[i], w.soff = M.w.subset_off[i], w.voff = M.w.value_off[i];
+  w.klen = M.w.key_len[i], w.slen = w.has ? M.w.subset_len[i] : 0, w.vlen = hv ? M.w.value_len[i] : 0;
+  w.plen = (uint64_t)w.klen + w.slen + w.vlen;
+  RowSrc W = {};
+  W.nbytes = M.nbytes;
+  w.ok = wire_has(W, w.koff, w.klen) && (!w.has || wire_has(W, w.soff, w.slen)) &&
+         (!hv || wire_has(W, w.voff, w.vlen)) && w.plen <= 0xFFFFFFF0ull;
+  return w;
+}
+
+// The plans' epilogue (st_lookup, stl_plan; every lane of the workgroup): winner i's state, within the
+// workgroup its rank among the inserted and the bytes needed before it, per workgroup the sums
+__device__ __forceinline__ void st_publish(const StoreMerge &M, uint64_t i, uint32_t code, uint32_t alloc,
+                                           uint64_t where, uint64_t h, uint64_t dead) {
   __shared__ uint32_t wcnt[ST_WAVES][ST_MISC];
   __shared__ uint64_t wdead[ST_WAVES], sw[ST_WAVES];
-  const StoreDev &S = M.s;
-  const uint64_t i = (uint64_t)blockIdx.x * ST_BLK + threadIdx.x;
-  uint32_t code = ST_NONE, alloc = 0;
-  uint64_t where = 0, h = 0, dead = 0;
-  if (i < *M.nw && i < M.n) {
-    const uint32_t fl = M.w.flags[i];
-    const bool has = (fl & DRP_F_SUBSET) != 0, hv = (fl & DRP_F_VALUE) != 0;
-    const uint64_t koff = M.w.key_off[i], soff = M.w.subset_off[i], voff = M.w.value_off[i];
-    const uint32_t klen = M.w.key_len[i], slen = has ? M.w.subset_len[i] : 0, vlen = hv ? M.w.value_len[i] : 0;
-    const uint64_t plen = (uint64_t)klen + slen + vlen;
-    RowSrc W = {};
-    W.nbytes = M.nbytes;
-    // (a winner's key and subset lie inside the wire: it was a candidate; its value need not)
-    if (!wire_has(W, koff, klen) || (has && !wire_has(W, soff, slen)) || (hv && !wire_has(W, voff, vlen)) ||
-        plen > 0xFFFFFFF0ull) {
-      code = ST_SKIPPED;
-    } else {
-      const uint8_t *key = M.bytes + koff, *sub = M.bytes + soff, *val = M.bytes + voff;
-      h = st_hash(S, has, key, klen, sub, slen);
-      uint64_t free_slot;
-      const uint64_t r = st_probe(S, h, has, key, klen, sub, slen, free_slot);
-      code = ST_SKIPPED;  // (a table without a free slot: not reached, it is at most half full)
-      if (r == ~0ull && free_slot != ~0ull) {
-        code = ST_INSERT;
-        where = free_slot;
-      }
-      if (r != ~0ull) {
-        const drp_changes &c = S.cols;
-        const uint64_t sch = c.change[r], wch = M.w.change[i];
-        where = r;
-        if (sch > wch) {
-          code = ST_STALE;
-        } else if (sch == wch && c.from[r] == M.w.from[i] && c.to[r] == M.w.to[i] &&
-                   (c.flags[r] & (DRP_F_SUBSET | DRP_F_VALUE)) == fl && c.value_len[r] == vlen &&
-                   (uint64_t)S.payload_len[r] == plen &&
-                   bytes_eq(S.arena + S.payload_off[r] + klen + slen, val, vlen)) {
-          code = ST_UNCHANGED;
-        } else {
-          code = ST_REPLACE;
-          dead = st_r16(S.payload_len[r]);
-        }
-      }
-      if (code == ST_INSERT || code == ST_REPLACE) alloc = st_r16((uint32_t)plen);
-    }
-  }
-  // the workgroup's sums, and this winner's place among its inserted winners and in its bytes
   const uint32_t wv = threadIdx.x >> 6, lane = lane_id();
   const uint64_t bi = __ballot(code == ST_INSERT), br = __ballot(code == ST_REPLACE),
                  bu = __ballot(code == ST_UNCHANGED), bs = __ballot(code == ST_STALE),
@@ -176,6 +168,50 @@ __global__ __launch_bounds__(ST_BLK) void st_lookup_kernel(const StoreMerge M) {
       M.blk_misc[(uint64_t)blockIdx.x * ST_MISC + threadIdx.x - 1] = t;  // [4]: the dead bytes
     }
   }
+}
+
+__global__ __launch_bounds__(ST_BLK) void st_lookup_kernel(const StoreMerge M) {
+  const StoreDev &S = M.s;
+  const uint64_t i = (uint64_t)blockIdx.x * ST_BLK + threadIdx.x;
+  uint32_t code = ST_NONE, alloc = 0;
+  uint64_t where = 0, h = 0, dead = 0;
+  if (i < *M.nw && i < M.n) {
+    const StWinner w = st_winner(M, i);
+    const bool has = w.has;
+    const uint32_t fl = w.fl, klen = w.klen, slen = w.slen, vlen = w.vlen;
+    const uint64_t plen = w.plen;
+    if (!w.ok) {
+      code = ST_SKIPPED;
+    } else {
+      const uint8_t *key = M.bytes + w.koff, *sub = M.bytes + w.soff, *val = M.bytes + w.voff;
+      h = st_hash(S, has, key, klen, sub, slen);
+      uint64_t free_slot;
+      const uint64_t r = st_probe(S, h, has, key, klen, sub, slen, free_slot);
+      code = ST_SKIPPED;  // (a table without a free slot: not reached, it is at most half full)
+      if (r == ~0ull && free_slot != ~0ull) {
+        code = ST_INSERT;
+        where = free_slot;
+      }
+      if (r != ~0ull) {
+        const drp_changes &c = S.cols;
+        const uint64_t sch = c.change[r], wch = M.w.change[i];
+        where = r;
+        if (sch > wch) {
+          code = ST_STALE;
+        } else if (sch == wch && c.from[r] == M.w.from[i] && c.to[r] == M.w.to[i] &&
+                   (c.flags[r] & (DRP_F_SUBSET | DRP_F_VALUE)) == fl && c.value_len[r] == vlen &&
+                   (uint64_t)S.payload_len[r] == plen &&
+                   bytes_eq(S.arena + S.payload_off[r] + klen + slen, val, vlen)) {
+          code = ST_UNCHANGED;
+        } else {
+          code = ST_REPLACE;
+          dead = st_r16(S.payload_len[r]);
+        }
+      }
+      if (code == ST_INSERT || code == ST_REPLACE) alloc = st_r16((uint32_t)plen);
+    }
+  }
+  st_publish(M, i, code, alloc, where, h, dead);
 }
 
 // one workgroup: the sums the scans did not take, the verdict, the record's last-merge group
@@ -212,6 +248,19 @@ __global__ __launch_bounds__(ST_BLK) void st_verdict_kernel(const StoreMerge M) 
   M.ctl[2] = s[4];
 }
 
+// row `row` of hash h into the first free slot from s on (st_claim, strh_enter): a compare-and-swap
+// of 0 -> tag | row + 1 per slot until one takes place, nslots steps at the latest
+__device__ __forceinline__ void st_enter(const StoreDev &S, uint64_t s, uint64_t h, uint64_t row) {
+  const uint64_t word = (h & ST_TAG) | (row + 1), smask = S.nslots - 1;
+  s &= smask;
+  for (uint64_t step = 0; step < S.nslots; step++, s = (s + 1) & smask) {
+    uint64_t seen = 0;
+    if (__hip_atomic_compare_exchange_strong(S.table + s, &seen, word, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_AGENT))
+      break;
+  }
+}
+
 __global__ __launch_bounds__(ST_BLK) void st_claim_kernel(const StoreMerge M) {
   const StoreDev &S = M.s;
   const uint64_t i = (uint64_t)blockIdx.x * ST_BLK + threadIdx.x;
@@ -219,14 +268,7 @@ __global__ __launch_bounds__(ST_BLK) void st_claim_kernel(const StoreMerge M) {
   const uint32_t meta = M.meta[i];
   if ((meta & 0xFF) != ST_INSERT) return;
   const uint64_t row = S.info->rows + M.blk_ins[blockIdx.x] + (meta >> 8);  // (< max_keys: the verdict)
-  const uint64_t word = (M.hash[i] & ST_TAG) | (row + 1), smask = S.nslots - 1;
-  uint64_t s = M.where[i];
-  for (uint64_t step = 0; step < S.nslots; step++, s = (s + 1) & smask) {
-    uint64_t seen = 0;
-    if (__hip_atomic_compare_exchange_strong(S.table + s, &seen, word, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT))
-      break;
-  }
+  st_enter(S, M.where[i], M.hash[i], row);
   M.where[i] = row;  // (read by this winner's lanes of st_write only)
 }
 
@@ -536,6 +578,108 @@ __global__ __launch_bounds__(ST_BLK) void stc_copy_kernel(const StoreCompact Q) 
   if (g == 0) S.payload_off[r] = to;
 }
 
+// ---- lifecycle --------------------------------------------------------------------------------
+// The load and the rehash (include/drp.h "store lifecycle"). Both enter rows whose identities the
+// caller promises to be distinct, so nothing is looked up: a row goes to the first free slot from its
+// home slot on (st_enter, st_claim's loop). The table words are still all that crosses workgroups
+// inside a kernel; the counts below are only added to, and read after the kernel's end.
+//   stl_plan     st_lookup's place in a load, one selected row per lane: skipped if a range leaves the
+//                wire, else inserted; the hash, the home slot, the allocation; st_publish as st_lookup.
+//                The scans, st_verdict, st_claim, st_write and st_commit follow unchanged.
+//   strh_enter   one store row per lane over the zeroed table: a row st_same would not read is counted
+//                and left out, every other enters under its hash from its arena bytes.
+//   st_selfcheck one store row per lane (a load's new rows behind st_commit, or all rows): st_probe for
+//                the row's own identity, counted if it names another row. A kernel of its own behind
+//                the one that entered the rows: by then the table is final, and of two rows of one
+//                identity every probe meets the one in the earlier slot first, so exactly the other is
+//                counted, whichever won the race for it.
+//   strh_finish  the record's last-merge group.
+
+// the lanes of the workgroup with `flag`, added to *dst (null: not counted): the waves' ballots, their
+// counts in LDS, one agent-scope add per workgroup that has any. Once per kernel, by every lane
+__device__ __forceinline__ void st_count(bool flag, uint64_t *dst) {
+  __shared__ uint32_t wcnt[ST_WAVES];
+  const uint64_t b = __ballot(flag);
+  if (lane_id() == 0) wcnt[threadIdx.x >> 6] = (uint32_t)__popcll(b);
+  __syncthreads();
+  if (threadIdx.x != 0 || !dst) return;
+  uint64_t t = 0;
+#pragma unroll
+  for (uint32_t k = 0; k < ST_WAVES; k++) t += wcnt[k];
+  if (t) __hip_atomic_fetch_add(dst, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// store row r's own identity out of its columns and arena bytes, and its hash; false (nothing of the
+// arena is read): a row that fails st_same's validity test
+struct StOwn {
+  const uint8_t *key, *sub;
+  uint32_t klen, slen;
+  bool has;
+  uint64_t h;
+};
+__device__ __forceinline__ bool st_own(const StoreDev &S, uint64_t r, StOwn &d) {
+  const drp_changes &c = S.cols;
+  d.klen = c.key_len[r];
+  d.slen = c.subset_len[r];
+  d.has = (c.flags[r] & DRP_F_SUBSET) != 0;
+  uint64_t at;
+  if (!st_payload_ok(S, r, (uint64_t)d.klen + d.slen, at)) return false;
+  d.key = S.arena + at;
+  d.sub = d.key + d.klen;
+  d.h = st_hash(S, d.has, d.key, d.klen, d.sub, d.slen);
+  return true;
+}
+
+__global__ __launch_bounds__(ST_BLK) void stl_plan_kernel(const StoreMerge M) {
+  const uint64_t i = (uint64_t)blockIdx.x * ST_BLK + threadIdx.x;
+  uint32_t code = ST_NONE, alloc = 0;
+  uint64_t h = 0;
+  if (i < *M.nw && i < M.n) {
+    const StWinner w = st_winner(M, i);
+    code = ST_SKIPPED;
+    if (w.ok) {
+      code = ST_INSERT;
+      h = st_hash(M.s, w.has, M.bytes + w.koff, w.klen, M.bytes + w.soff, w.slen);
+      alloc = st_r16((uint32_t)w.plen);
+    }
+  }
+  st_publish(M, i, code, alloc, h & (M.s.nslots - 1), h, 0);
+}
+
+__global__ __launch_bounds__(ST_BLK) void strh_enter_kernel(const StoreDev S, uint64_t *invalid) {
+  const uint64_t r = (uint64_t)blockIdx.x * ST_BLK + threadIdx.x;
+  bool bad = false;
+  if (r < umin64(S.info->rows, S.max_keys)) {
+    StOwn d;
+    bad = !st_own(S, r, d);
+    if (!bad) st_enter(S, d.h, d.h, r);
+  }
+  st_count(bad, invalid);
+}
+
+// rows [first, rows): first = 0, or with `loaded` the rows before the load st_commit has just applied
+// (a refused load added none)
+__global__ __launch_bounds__(ST_BLK) void st_selfcheck_kernel(const StoreDev S, uint64_t *count, uint32_t loaded) {
+  const drp_store_info *I = S.info;
+  const uint64_t rows = umin64(I->rows, S.max_keys);
+  const uint64_t first = !loaded ? 0 : I->refused ? rows : rows - umin64(I->inserted, rows);
+  const uint64_t r = first + (uint64_t)blockIdx.x * ST_BLK + threadIdx.x;
+  bool other = false;
+  StOwn d;
+  if (r < rows && st_own(S, r, d)) {
+    uint64_t free_slot;
+    other = st_probe(S, d.h, d.has, d.key, d.klen, d.sub, d.slen, free_slot) != r;
+  }
+  st_count(other, count);
+}
+
+__global__ void strh_finish_kernel(const StoreDev S, const uint64_t *report) {
+  drp_store_info *I = S.info;
+  I->winners = I->inserted = I->replaced = I->unchanged = I->stale = I->skipped = 0;
+  I->need_rows = I->need_bytes = 0;
+  I->refused = (report && (report[0] | report[1])) ? 1 : 0;
+}
+
 }  // namespace drp
 
 using namespace drp;
@@ -564,11 +708,10 @@ extern "C" uint64_t drp_store_merge_scratch_bytes(uint64_t n) {
 
 extern "C" uint64_t drp_store_blocks(uint64_t n) { return st_nblk(n); }
 
-extern "C" hipError_t drp_launch_store_merge(const StoreMerge *Mp, const StoreReport *R, void *scratch,
-                                             hipStream_t st) {
-  StoreMerge M = *Mp;
+// M's state into `scratch`; false: more workgroups than a grid of st_write holds
+static bool st_place(StoreMerge &M, void *scratch) {
   const uint64_t nblk = st_nblk(M.n), m = nblk * ST_BLK;
-  if (nblk >= (1ull << 31) / ST_GRP) return hipErrorInvalidValue;
+  if (nblk >= (1ull << 31) / ST_GRP) return false;
   uint8_t *sc = static_cast<uint8_t *>(scratch);
   auto take = [&](uint64_t bytes) { void *p = sc; sc += al(bytes); return p; };
   M.where = static_cast<uint64_t *>(take(m * 8));
@@ -581,14 +724,55 @@ extern "C" hipError_t drp_launch_store_merge(const StoreMerge *Mp, const StoreRe
   M.blk_misc = static_cast<uint64_t *>(take(nblk * ST_MISC * 8));
   M.ctl = static_cast<uint64_t *>(take(256));
   M.nblk = nblk;
-  const dim3 grid((uint32_t)nblk), blk(ST_BLK);
-  hipLaunchKernelGGL(st_lookup_kernel, grid, blk, 0, st, M);
-  if (const hipError_t e = drp_launch_count_scan(M.blk_ins, nblk, M.ctl + 0, st)) return e;
-  if (const hipError_t e = drp_launch_count_scan(M.blk_bytes, nblk, M.ctl + 1, st)) return e;
+  return true;
+}
+
+// what follows a plan (st_lookup, stl_plan): the scans, the verdict, the claims, the writes, the commit
+static hipError_t st_apply(const StoreMerge &M, hipStream_t st) {
+  const dim3 grid((uint32_t)M.nblk), blk(ST_BLK);
+  if (const hipError_t e = drp_launch_count_scan(M.blk_ins, M.nblk, M.ctl + 0, st)) return e;
+  if (const hipError_t e = drp_launch_count_scan(M.blk_bytes, M.nblk, M.ctl + 1, st)) return e;
   hipLaunchKernelGGL(st_verdict_kernel, dim3(1), blk, 0, st, M);
   hipLaunchKernelGGL(st_claim_kernel, grid, blk, 0, st, M);
-  hipLaunchKernelGGL(st_write_kernel, dim3((uint32_t)(nblk * ST_GRP)), blk, 0, st, M);
+  hipLaunchKernelGGL(st_write_kernel, dim3((uint32_t)(M.nblk * ST_GRP)), blk, 0, st, M);
   hipLaunchKernelGGL(st_commit_kernel, dim3(1), dim3(1), 0, st, M);
+  return hipSuccess;
+}
+
+extern "C" hipError_t drp_launch_store_load(const StoreMerge *Mp, uint64_t *clash, void *scratch, hipStream_t st) {
+  StoreMerge M = *Mp;
+  if (!st_place(M, scratch)) return hipErrorInvalidValue;
+  const dim3 grid((uint32_t)M.nblk), blk(ST_BLK);
+  hipLaunchKernelGGL(stl_plan_kernel, grid, blk, 0, st, M);
+  if (const hipError_t e = st_apply(M, st)) return e;
+  if (clash) {
+    if (const hipError_t e = hipMemsetAsync(clash, 0, 8, st)) return e;
+    hipLaunchKernelGGL(st_selfcheck_kernel, grid, blk, 0, st, M.s, clash, 1u);
+  }
+  drp_dbg_mark("store_load", st);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t drp_launch_store_rehash(const StoreDev *S, uint64_t *report, hipStream_t st) {
+  if (const hipError_t e = hipMemsetAsync(S->table, 0, S->nslots * 8, st)) return e;
+  if (report)
+    if (const hipError_t e = hipMemsetAsync(report, 0, 16, st)) return e;
+  const dim3 grid((uint32_t)st_nblk(S->max_keys)), blk(ST_BLK);
+  hipLaunchKernelGGL(strh_enter_kernel, grid, blk, 0, st, *S, report);
+  if (report) hipLaunchKernelGGL(st_selfcheck_kernel, grid, blk, 0, st, *S, report + 1, 0u);
+  hipLaunchKernelGGL(strh_finish_kernel, dim3(1), dim3(1), 0, st, *S, (const uint64_t *)report);
+  drp_dbg_mark("store_rehash", st);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t drp_launch_store_merge(const StoreMerge *Mp, const StoreReport *R, void *scratch,
+                                             hipStream_t st) {
+  StoreMerge M = *Mp;
+  if (!st_place(M, scratch)) return hipErrorInvalidValue;
+  const uint64_t nblk = M.nblk;
+  const dim3 grid((uint32_t)nblk), blk(ST_BLK);
+  hipLaunchKernelGGL(st_lookup_kernel, grid, blk, 0, st, M);
+  if (const hipError_t e = st_apply(M, st)) return e;
   drp_dbg_mark("store_merge", st);
   if (R) {
     const bool rows = R->src_row && (R->outcome || R->news_type), reply = R->n_reply && R->blk_stale;

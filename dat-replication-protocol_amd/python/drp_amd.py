@@ -36,6 +36,7 @@ EXPORTS = [
     "drp_store_compact", "drp_store_query", "drp_order_device",
     "drp_store_merge_report_device", "drp_store_merge_news_staged", "drp_fanout_news_staged",
     "drp_store_lookup_device", "drp_store_lookup_staged",
+    "drp_store_load_device", "drp_store_rehash_device",
     "drp_digest_device", "drp_digest_diff_device", "drp_select_buckets_device",
     "drp_digest_refine_device", "drp_digest_diff_cells_device", "drp_select_refined_device",
     "drp_comm_id", "drp_comm_init_rank", "drp_comm_init_all", "drp_comm_destroy",
@@ -257,6 +258,8 @@ def lib():
         L.drp_store_lookup_device.argtypes = L.drp_store_merge_device.argtypes + [C.POINTER(Lookup)]
         L.drp_store_lookup_staged.argtypes = [P, C.POINTER(StoreDesc), C.POINTER(Filter), U32, P, U64, C.POINTER(U64),
                                               C.POINTER(U64), C.POINTER(U64)]
+        L.drp_store_load_device.argtypes = L.drp_store_merge_device.argtypes + [P]
+        L.drp_store_rehash_device.argtypes = [P, C.POINTER(StoreDesc), P]
         L.drp_store_compact.argtypes = [P, C.POINTER(StoreDesc), P, U64]
         L.drp_store_query.argtypes = [P, C.POINTER(StoreDesc), C.POINTER(StoreInfo)]
         L.drp_order_device.argtypes = [P, C.POINTER(ChangeSrc), P, U32, U64, P, U32, C.POINTER(ChangeSrc), P, P, P]
@@ -294,6 +297,7 @@ def lib():
                   "drp_store_compact", "drp_store_query", "drp_order_device", "drp_digest_device", "drp_digest_diff_device",
                   "drp_store_merge_report_device", "drp_store_merge_news_staged", "drp_fanout_news_staged",
                   "drp_store_lookup_device", "drp_store_lookup_staged",
+                  "drp_store_load_device", "drp_store_rehash_device",
                   "drp_select_buckets_device", "drp_digest_refine_device", "drp_digest_diff_cells_device",
                   "drp_select_refined_device", "drp_stream_stats_from_results", "drp_device", "drp_comm_id", "drp_comm_init_rank",
                   "drp_comm_init_all", "drp_index_allgather", "drp_index_allgather_multi",
@@ -851,6 +855,34 @@ class Ctx:
         _chk("drp_store_query", self.L.drp_store_query(self.h, C.byref(store.desc()), C.byref(info)))
         return info
 
+    # ---- store lifecycle: load distinct rows, rehash ----------------------------------------------
+    def store_load_device(self, store, wire_t, cols, n, filter=None, clash_t=None):
+        """drp_store_load_device: the rows select_device selects from [0, n) of (wire_t, cols) enter
+        the store as new rows, ungrouped and not looked up: the caller promises that their identities
+        are distinct and not in the store. clash_t (int64, 1, optional) receives the rows that broke
+        the promise; a store with clash > 0 must be dropped. Asynchronous; refused on the device as a
+        merge is (store_query(...).refused)."""
+        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
+        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
+                     tp(cols["flags"]), None)
+        self.order_after_torch(wire_t)
+        rc = self.L.drp_store_load_device(self.h, C.byref(store.desc()), tp(wire_t), wire_t.numel(), C.byref(fr),
+                                          C.byref(co), n, C.byref(filter) if filter is not None else None, tp(clash_t))
+        _chk("drp_store_load_device", rc)
+        self.order_torch_after(wire_t)
+
+    def store_rehash_device(self, store, report_t=None):
+        """drp_store_rehash_device: the store's table rebuilt from its rows in use under the ctx's
+        current hash mask. report_t (int64, 2, optional): the rows left out as invalid, and the rows
+        that share their identity with an earlier one; store_query(...).refused is 1 if either is
+        nonzero. Asynchronous."""
+        self.order_after_torch(store.arena)
+        rc = self.L.drp_store_rehash_device(self.h, C.byref(store.desc()),
+                                            C.c_void_p(report_t.data_ptr()) if report_t is not None else None)
+        _chk("drp_store_rehash_device", rc)
+        self.order_torch_after(store.arena)
+
     # ---- ordered catch-up: a fan-out's outputs in change order, with a per-peer limit -------------
     def order_device(self, rows, row_base_t, nseg, rows_cap, out_rows, out_base_t, limit=None, keep_ties=False,
                      sel_idx_t=None, out_sel_idx_t=None, flags=None):
@@ -1091,6 +1123,110 @@ class Store:
         if not i.refused:
             self.arena, self.arena_bytes = a2, int(arena2_bytes)
         return i
+
+    # ---- lifecycle: grow, prune, save and restore -------------------------------------------------
+    def _take(self, other):
+        """This store becomes `other` (its tensors and sizes)."""
+        for k in ["max_keys", "arena", "arena_bytes", "cols", "table", "info"]:
+            setattr(self, k, getattr(other, k))
+
+    def grow(self, max_keys=None, arena_bytes=None):
+        """Resize the store in place: new column tensors and a new table for max_keys (the rows in use
+        copied with torch, then one rehash), a new arena for arena_bytes (the bytes in use copied).
+        No payload moves within the arena and the rows keep their index. ValueError for a size below
+        what is in use; DrpError if the rehash reports an invalid or duplicate row (the store is left
+        as it was). Returns the record."""
+        import copy
+        import torch
+        i = self.query()
+        mk = self.max_keys if max_keys is None else int(max_keys)
+        ab = self.arena_bytes if arena_bytes is None else int(arena_bytes)
+        if mk < max(int(i.rows), 1) or ab < int(i.arena_used):
+            raise ValueError(f"grow({mk}, {ab}) below what is in use ({i.rows} rows, {i.arena_used} bytes)")
+        dev = self.arena.device
+        new = copy.copy(self)
+        if ab != self.arena_bytes:
+            new.arena = torch.zeros(max(ab, 1), dtype=torch.uint8, device=dev)
+            new.arena[:i.arena_used] = self.arena[:i.arena_used]
+            new.arena_bytes = ab
+        if mk != self.max_keys:
+            new.cols = {k: torch.zeros(mk, dtype=v.dtype, device=dev) for k, v in self.cols.items()}
+            for k, v in self.cols.items():
+                new.cols[k][:i.rows] = v[:i.rows]
+            new.table = torch.zeros(lib().drp_store_table_bytes(mk) // 8, dtype=torch.int64, device=dev)
+            new.max_keys = mk
+            report = torch.zeros(2, dtype=torch.int64, device=dev)
+            self.ctx.store_rehash_device(new, report)
+            bad = [int(v) for v in report.cpu()]
+            if any(bad):
+                self.ctx.store_rehash_device(self)  # (the shared record's last-merge group, and this table)
+                raise DrpError(f"drp_store_rehash_device (report {bad})", DRP_E_INVAL)
+        self._take(new)
+        return self.query()
+
+    def retain(self, filter=None, type_t=None, max_keys=None, arena_bytes=None):
+        """Keep only the rows that select_device selects from the store's view under `filter`, with
+        type_t (uint8, max_keys entries: a lookup's lack_type, the store's own type column with entries
+        zeroed) in the type column's place: a fresh store (max_keys / arena_bytes, default the same
+        sizes) and one store_load_device of the view into it, with the clash check. Returns the fresh
+        store's record, with .clash = the check's count; this store takes the new tensors unless the
+        load was refused or clashed. The kept rows are renumbered in their old order, the arena is
+        compacted and arena_dead is 0."""
+        import torch
+        dev = self.arena.device
+        new = Store(self.ctx, self.max_keys if max_keys is None else max_keys,
+                    self.arena_bytes if arena_bytes is None else arena_bytes, device=dev)
+        view = dict(self.cols)
+        if type_t is not None:
+            view["type"] = type_t
+        clash = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.ctx.store_load_device(new, self._view(), view, self.max_keys, filter, clash)
+        i = new.query()
+        i.clash = int(clash.cpu()[0])
+        if not i.refused and not i.clash:
+            self._take(new)
+        return i
+
+    def state(self):
+        """The store as host numpy arrays: {"cols": {name: the column's rows [0, rows)}, "arena": the
+        bytes [0, arena_used), "rows", "arena_used", "arena_dead", "merges"}. Store.from_state brings
+        it back; the table is not saved (it is rebuilt from the rows)."""
+        i = self.query()
+        return {"cols": {k: v[:i.rows].cpu().numpy().copy() for k, v in self.cols.items()},
+                "arena": self.arena[:i.arena_used].cpu().numpy().copy(),
+                "rows": int(i.rows), "arena_used": int(i.arena_used), "arena_dead": int(i.arena_dead),
+                "merges": int(i.merges)}
+
+    @classmethod
+    def from_state(cls, ctx, state, max_keys=None, arena_bytes=None, device="cuda:0"):
+        """A store restored from Store.state(): allocate (default sizes: what the state uses), upload
+        the columns, the arena and the record, and rehash with a report. ValueError for a state that
+        does not fit the sizes or its own counts; DrpError if the rehash reports an invalid or
+        duplicate row."""
+        import torch
+        rows, used = int(state["rows"]), int(state["arena_used"])
+        mk = max(rows, 1) if max_keys is None else int(max_keys)
+        ab = used if arena_bytes is None else int(arena_bytes)
+        if mk < rows or ab < used or len(state["arena"]) != used or used % 16 or int(state["arena_dead"]) > used:
+            raise ValueError(f"the state ({rows} rows, {used} bytes) does not fit ({mk}, {ab})")
+        s = cls(ctx, mk, ab, device=device)
+        if set(state["cols"]) != set(s.cols) or any(len(v) != rows for v in state["cols"].values()):
+            raise ValueError("the state's columns are not a store's, or not `rows` long")
+        dev = s.arena.device
+        signed = {8: np.int64, 4: np.int32, 1: np.uint8}  # (torch's dtypes for the 64-, 32- and 8-bit columns)
+        for k, v in state["cols"].items():
+            v = np.ascontiguousarray(v)
+            s.cols[k][:rows] = torch.from_numpy(v.view(signed[v.dtype.itemsize])).to(dev)
+        s.arena[:used] = torch.from_numpy(np.ascontiguousarray(state["arena"], np.uint8)).to(dev)
+        rec = np.zeros(C.sizeof(StoreInfo) // 8, np.int64)
+        rec[:4] = [rows, used, int(state["arena_dead"]), int(state["merges"])]
+        s.info.copy_(torch.from_numpy(rec).to(dev))
+        report = torch.zeros(2, dtype=torch.int64, device=dev)
+        ctx.store_rehash_device(s, report)
+        bad = [int(v) for v in report.cpu()]
+        if any(bad):
+            raise DrpError(f"drp_store_rehash_device (report {bad})", DRP_E_INVAL)
+        return s
 
     def lookup(self, wire_t, cols, n, filter=None, emit=(LOOKUP_BEHIND, LOOKUP_LEVEL, LOOKUP_AHEAD), lack=False):
         """store_lookup_device with the full set of outputs: {"verdict" (uint8, n entries: LOOKUP_*

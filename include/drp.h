@@ -42,6 +42,10 @@
  *          queried key from its `change` against the stored one, the found rows for the encoder (a
  *          multi-get), and a type column under which the store holds exactly the rows the sender of
  *          a have-list lacks (a peer with a plain list of keys and versions catching up).
+ *   drp_store_load_device / drp_store_rehash_device
+ *       -> no reference counterpart: rows known to be new entered into that store without grouping
+ *          or lookup, and its table rebuilt from its rows (a hub growing its store, dropping rows
+ *          from it, or restoring it from saved columns after a restart).
  *   drp_order_device
  *       -> no reference counterpart: the rows of every fan-out output in ascending `change` (schema
  *          messages/schema.proto:1-8), cut to a per-peer limit (a catch-up a peer can resume or page).
@@ -781,6 +785,58 @@ int drp_store_lookup_device(drp_ctx *ctx, const drp_store *s, const uint8_t *byt
 int drp_store_lookup_staged(drp_ctx *ctx, const drp_store *s, const drp_filter *filter, uint32_t reply,
                             uint8_t *out, uint64_t cap, uint64_t *written, uint64_t *n_rows,
                             uint64_t *counts_host /* 5, may be NULL */);
+
+/* ---- store lifecycle: load distinct rows, rehash (grow, prune, restore) ----------------------- */
+/* A store's max_keys and table are fixed at drp_store_init, its rows keep their index, and its table
+ * is a product of the merges that filled it. Growing it, dropping rows from it and bringing it back
+ * from saved columns all come down to two calls: enter rows that are known to be new, without the
+ * grouping and the lookup a merge pays for, and rebuild the table from the rows. No reference
+ * counterpart (the reference has no relay).
+ *   drp_store_load_device. The arguments and DRP_E_INVAL cases are drp_store_merge_device's. Loaded
+ * rows: exactly the rows drp_select_device selects for (bytes, nbytes, frames, cols, n, filter), in row
+ * order; with the store's view as the batch, a type column of the caller's in frames->type's place
+ * (a lookup's lack_type, a report's news_type, the store's own with entries zeroed) says which rows.
+ *   Precondition, the caller's promise: the loaded rows' identities are pairwise distinct and none is
+ * in the store. Nothing is grouped, looked up or compared.
+ *   A loaded row is `skipped`, counted and never read, if its key range, its subset range (with
+ * DRP_F_SUBSET) or its value range (with DRP_F_VALUE) leaves [0, nbytes), or its three lengths sum
+ * past 2^32 - 16. Every other row is `inserted` exactly as a merge inserts: as row info.rows + its rank
+ * among the inserted in row order, in the stored form above, its payload at arena_used + the
+ * 16-rounded sizes of the inserted before it.
+ *   All or nothing, by the merge's verdict: refused, need_rows, need_bytes. The record's last-merge
+ * group: winners = the selected rows, inserted, skipped, and replaced = unchanged = stale = 0. merges
+ * is counted unless the load is refused.
+ *   clash (DEVICE, one entry, may be NULL: then the check does not run): after the rows are written,
+ * every loaded row probes the table for its own identity; *clash is the number of rows for which the
+ * probe names another row. That is the loaded rows minus the new distinct identities among them: a
+ * function of the input alone, and 0 exactly when the precondition held (0 after a refused load).
+ * With *clash > 0 the store holds two rows of one identity and every later merge or lookup of it may
+ * meet either: the store must be dropped. The call is meant for a store the caller is building
+ * (Store.retain in drp_amd.py loads into a fresh one and keeps the old one on a clash).
+ *   Device pointers only; asynchronous on drp_stream(ctx), no host synchronisation inside. Scratch from
+ * the ctx's (DRP_E_NOMEM if it cannot be had): drp_select_device's, and per row of the batch 80 bytes
+ * of selected rows and 32 bytes of merge state. There is no grouping table; a caller bounds the
+ * scratch by loading in pieces (a load into a store that holds rows appends). */
+int drp_store_load_device(drp_ctx *ctx, const drp_store *s, const uint8_t *bytes, uint64_t nbytes,
+                          const drp_frames *frames, const drp_changes *cols, uint64_t n,
+                          const drp_filter *filter, uint64_t *clash /* device, 1 entry, may be NULL */);
+/* Rebuild the table from the rows: s->table (drp_store_table_bytes(max_keys) bytes) is zeroed and the
+ * rows [0, min(info.rows, max_keys)) (info.rows is read on the device) are entered under the ctx's
+ * current hash mask, each from its home slot forward as a merge's inserted winner is. The arena, the
+ * columns and rows / arena_used / arena_dead / merges of the record are not written; the last-merge
+ * group is zeroed. A row whose payload range [payload_off, payload_off + payload_len) leaves
+ * [0, arena_bytes), or whose key_len + subset_len exceeds payload_len, is never read and not entered:
+ * no lookup or merge finds it.
+ *   report (DEVICE, two entries, may be NULL: then the check does not run): report[0] = the rows not
+ * entered; report[1] = the entered rows whose probe for their own identity names another row (the
+ * load's check over all rows: the rows minus the distinct identities). refused = 1 if either is
+ * nonzero, else 0.
+ *   After a rehash the store's hash mask is the ctx's current one: the "one mask for its whole life"
+ * rule above starts again there.
+ *   Restore: upload the columns, the arena and the record, then rehash. Grow without a payload copy:
+ * larger columns and a larger table, the old columns copied, frames.type zero beyond them, then
+ * rehash. DRP_E_INVAL: drp_store_init's cases. Asynchronous on drp_stream(ctx); no scratch. */
+int drp_store_rehash_device(drp_ctx *ctx, const drp_store *s, uint64_t *report /* device, 2 entries, may be NULL */);
 
 /* ---- ordered catch-up: a fan-out's outputs in `change` order, with a per-peer limit ---------- */
 /* Every output of the select, fan-out and latest calls above is in row order; over a store that is

@@ -118,6 +118,15 @@ probe, and the host relay through drp_relay_staged against the host round trip i
               result says per batch whether this build's merge medians lie inside the parent's own
               min-max spread.
 
+  lifecycle   (--lifecycle-out, default profiles/relay/lifecycle_bench.json; no other leg runs) The
+              store leg's final store (its key count, compacted) and its view as the batch. HIP events,
+              three warm-up rounds and --runs timed ones, medians: (a) drp_store_init and
+              drp_store_merge_device of the view into a fresh store, the only way to move a store
+              without the lifecycle calls; (b) drp_store_init and drp_store_load_device of the same
+              view, without and with clash, the loaded store checked to equal the merged one byte for
+              byte; (c) drp_store_rehash_device of the final store, without and with report; (d)
+              drp_store_compact and drp_store_init alone, for scale. All in one run, one library.
+
 Prints one JSON line (and writes it to --out). Needs an MI355X: there is no CPU path.
 
   hipcc -O3 --offload-arch=gfx950 scripts/probe_bw.hip -o exp/probe_bw
@@ -1722,6 +1731,57 @@ def lookup_leg(ctx, drp_amd, torch, frames, seqs, iters, parent=None):
     return res
 
 
+# ---- store lifecycle ---------------------------------------------------------------------------------
+
+def lifecycle_leg(ctx, drp_amd, torch, frames, runs):
+    """Moving a store: merge against load of its view into a fresh store, the rehash, and the compact
+    and the init for scale (include/drp.h "store lifecycle")."""
+    dev = torch.device("cuda", 0)
+    store, keys, n = _final_store(ctx, drp_amd, torch, frames)
+    stat = _timers(ctx, torch, dev, runs)
+    used = int(store.query().arena_used)  # (the live bytes: _final_store's arena has room to spare)
+    view = (store._view(), store.cols, store.max_keys)
+    fresh = drp_amd.Store(ctx, keys, store.arena_bytes)
+    clash_t = torch.zeros(1, dtype=torch.int64, device=dev)
+    report_t = torch.zeros(2, dtype=torch.int64, device=dev)
+
+    def merge():
+        ctx.store_init(fresh)
+        ctx.store_merge_device(fresh, *view)
+
+    def load(clash):
+        ctx.store_init(fresh)
+        ctx.store_load_device(fresh, *view, None, clash)
+
+    def filled():
+        i = fresh.query()
+        assert (i.rows, i.inserted, i.refused, i.arena_used) == (keys, keys, 0, used), i.as_dict()
+        return {k: v.clone() for k, v in fresh.cols.items()}, fresh.arena.clone()
+
+    res = {"keys": keys, "frames": n, "arena_used": used, "runs": runs}
+    res["init_ms"] = stat(lambda: ctx.store_init(fresh))
+    res["init_merge_ms"] = stat(merge)
+    want_cols, want_arena = filled()
+    for name, clash in [("init_load_ms", None), ("init_load_clash_ms", clash_t)]:
+        res[name] = stat(lambda: load(clash))
+        cols, arena = filled()
+        assert torch.equal(arena, want_arena) and all(torch.equal(cols[k], want_cols[k]) for k in cols), name
+    assert int(clash_t.cpu()[0]) == 0
+    del want_cols, want_arena, cols, arena, fresh
+    res["rehash_ms"] = stat(lambda: ctx.store_rehash_device(store))
+    res["rehash_report_ms"] = stat(lambda: ctx.store_rehash_device(store, report_t))
+    assert [int(v) for v in report_t.cpu()] == [0, 0] and int(torch.count_nonzero(store.table)) == keys
+    assert store.query().refused == 0
+    a2 = torch.zeros(store.arena_bytes, dtype=torch.uint8, device=dev)
+    # (the store is compact already: every round copies each payload to the offset it has)
+    res["compact_ms"] = stat(lambda: ctx.store_compact(store, a2))
+    assert store.query().refused == 0
+    res["load_over_merge"] = res["init_load_ms"]["median"] / res["init_merge_ms"]["median"]
+    res["load_clash_over_merge"] = res["init_load_clash_ms"]["median"] / res["init_merge_ms"]["median"]
+    res["load_not_slower_than_merge"] = bool(res["load_clash_over_merge"] <= 1.0 and res["load_over_merge"] <= 1.0)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=20_000_000)
@@ -1777,6 +1837,9 @@ def main():
     ap.add_argument("--lookup-baseline-out", default=None,
                     help="only the point read by fan-out and the merge sequences (no call of this commit), written here")
     ap.add_argument("--lookup-baseline", default=None, help="such a file of the parent commit, read into the lookup leg's result")
+    ap.add_argument("--lifecycle-out", nargs="?", default=None,
+                    const=os.path.join(ROOT, "profiles", "relay", "lifecycle_bench.json"),
+                    help="run the store lifecycle leg alone (load against merge, rehash, compact) and write its JSON line here")
     a = ap.parse_args()
     if a.digest_only and not a.digest_out:
         ap.error("--digest-only needs --digest-out")
@@ -1795,6 +1858,13 @@ def main():
     torch.cuda.init()
     import _streams as S
     import drp_amd
+    if a.lifecycle_out:
+        with drp_amd.Ctx(0) as ctx:
+            lc = {"bench": "relay_lifecycle", "device": lifecycle_leg(ctx, drp_amd, torch, a.frames, a.runs)}
+        with open(a.lifecycle_out, "w") as f:
+            f.write(json.dumps(lc) + "\n")
+        print(json.dumps(lc))
+        return
     if a.lookup_baseline_out:
         with drp_amd.Ctx(0) as ctx:
             base = lookup_baseline(ctx, drp_amd, torch, a.frames, a.store_seqs, a.iters)
