@@ -357,10 +357,44 @@ struct OrderParams {
   OrdCtl *ctl;
   uint64_t *part_or, *part_and, *key[2];
   uint32_t *idx[2], *hist, *bsum;
+  // set by drp_keyorder.hip only (null in drp_order_device): per row, 1 if it takes no part (the
+  // segment pass then sorts by 2 * segment + bad, so such rows fall behind their segment's others),
+  // and per segment the sorted position, counted from the segment's start, of its first kept row
+  const uint8_t *bad;
+  const uint64_t *seg_start;
 };
 // the per-segment limits as a launch argument (UINT64_MAX: none)
 struct OrdLimits {
   uint64_t v[DRP_FANOUT_MAX];
+};
+
+// drp_keyorder.hip: the segmented order-by-key. The sort is drp_order.hip's digit passes run once per
+// field of the tuple (key words, key length, subset presence, subset words, subset length), least
+// significant field first; before each run ordk_fetch loads that field of every row, in the order
+// reached so far, into the pair buffer's key column.
+constexpr uint32_t ORDK_KEY_WORD = 0, ORDK_KEY_LEN = 1, ORDK_SUB_HAS = 2, ORDK_SUB_WORD = 3, ORDK_SUB_LEN = 4;
+// written by ordk_prefin; its first 32 bytes are what the host reads to size the launch chain
+struct OrdkCtl {
+  uint64_t took, left;                 // rows that take part, rows left out
+  uint32_t max_key, max_sub, any_sub;  // over the rows that take part: longest key, longest subset, a subset present
+  uint32_t shared_words;               // leading 8-byte key words that are whole and equal in all of them
+  uint64_t start[DRP_FANOUT_MAX];      // ordk_cut: OrderParams::seg_start
+};
+// the pages as a launch argument: lo / hi are (offset, length) into the staged bound bytes
+struct OrdkPages {
+  uint64_t limit[DRP_FANOUT_MAX];
+  uint32_t flags[DRP_FANOUT_MAX], lo_off[DRP_FANOUT_MAX], lo_len[DRP_FANOUT_MAX], hi_off[DRP_FANOUT_MAX],
+      hi_len[DRP_FANOUT_MAX];
+};
+struct KeyOrderParams {
+  OrderParams o;  // (o.flags: DRP_KEYORDER_KEEP_TIES)
+  const uint8_t *heap;
+  uint64_t heap_bytes;
+  OrdkCtl *kctl;
+  uint8_t *bad;           // o.bad, writable (ordk_pre)
+  const uint8_t *bounds;  // the staged bound bytes
+  uint64_t bounds_bytes;
+  uint64_t *totals;       // may be null
 };
 
 }  // namespace drp
@@ -513,6 +547,13 @@ hipError_t drp_launch_select_refined(const drp::RefineParams *R, const drp::Sele
 uint64_t drp_order_scratch_bytes(uint64_t rows_cap);
 hipError_t drp_launch_order(const drp::OrderParams *P, const drp::OrdLimits *lim, uint64_t out_max, void *scratch,
                             hipStream_t st);
+// drp_keyorder.hip. Scratch: drp_order_scratch_bytes(rows_cap), then one byte per entry of rows_cap,
+// the OrdkCtl and bounds_bytes of staged bounds. bounds_host (bounds_bytes, may be null when 0) is
+// copied to the device and may be freed when the call returns. Waits for the stream once (the longest
+// key and subset size the launch chain).
+uint64_t drp_keyorder_scratch_bytes(uint64_t rows_cap, uint64_t bounds_bytes);
+hipError_t drp_launch_keyorder(const drp::KeyOrderParams *K, const drp::OrdkPages *pages, const uint8_t *bounds_host,
+                               uint64_t out_max, void *scratch, hipStream_t st);
 hipError_t drp_launch_fanout_scatter(const drp::FanParams *P, hipStream_t st);
 hipError_t drp_launch_fanout_splice(const drp::FanParams *P, hipStream_t st);
 // out_off[f] = frame_off[row_base[f]] (f <= nfilters); blob_pos[f * nb + j] = frame_off[row_base[f] +

@@ -32,36 +32,15 @@
 //  (4) ord_gather: output row j finds its segment in out_base and its source row in the permutation,
 //      and copies the ten columns (and sel_idx).
 // No global atomics; every loop is bounded; the result is a function of the input alone.
-#include "drp_device.h"
-#include "drp_kernels.h"
+// The digit pass (2) and the gather (4) also serve drp_keyorder.hip, which runs the pass once per
+// 8-byte word of a key: drp_launch_order_init / _pass / _gather below are the pieces both chains use,
+// and OrderParams::bad / seg_start (null here) are what that chain adds to them.
+#include "drp_order.h"
 
 namespace drp {
 
-constexpr uint32_t ORD_BLK = 1024, ORD_WAVES = ORD_BLK / 64, ORD_RPL = 4;
-constexpr uint32_t ORD_CHUNKS = ORD_TILE / 64, ORD_BINS = 256;
-static_assert(ORD_BLK * ORD_RPL == ORD_TILE, "four pairs per lane");
 static_assert(ORD_TILE < 65536, "a chunk base fits the 16-bit counts of ord_scatter");
-static_assert(DRP_FANOUT_MAX <= 64, "ord_cut: one lane per segment; the segment digit fits a pass");
-
-__device__ __forceinline__ uint64_t wave_or64(uint64_t v) {
-#pragma unroll
-  for (uint32_t m = 1; m < WAVE; m <<= 1) {
-    const uint32_t lo = shfl_xor32((uint32_t)v, m), hi = shfl_xor32((uint32_t)(v >> 32), m);
-    v |= ((uint64_t)hi << 32) | lo;
-  }
-  return v;
-}
-
-// the segment of row i (b[0] <= i): the greatest f < nseg with b[f] <= i (b non-decreasing)
-__device__ __forceinline__ uint32_t ord_seg(const uint64_t *b, uint32_t nseg, uint64_t i) {
-  uint32_t lo = 0, hi = nseg;
-  for (uint32_t k = 0; k < 7 && hi - lo > 1; k++) {  // (nseg <= 64: six halvings)
-    const uint32_t mid = (lo + hi) >> 1;
-    if (b[mid] <= i) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
+static_assert(2 * DRP_FANOUT_MAX <= ORD_BINS, "ord_cut: one lane per segment; the segment digit fits a pass");
 
 // (0) the input's validity and its row count
 __global__ __launch_bounds__(128) void ord_init_kernel(const OrderParams P) {
@@ -96,19 +75,8 @@ __global__ __launch_bounds__(ORD_BLK) void ord_reduce_kernel(const OrderParams P
       a &= k;
     }
   }
-  o = wave_or64(o);
-  a = ~wave_or64(~a);
-  if (lane_id() == 0) {
-    wo[threadIdx.x >> 6] = o;
-    wa[threadIdx.x >> 6] = a;
-  }
-  __syncthreads();
+  ord_block_or_and(o, a, wo, wa);
   if (threadIdx.x == 0) {
-#pragma unroll
-    for (uint32_t k = 1; k < ORD_WAVES; k++) {
-      o |= wo[k];
-      a &= wa[k];
-    }
     P.part_or[blockIdx.x] = o;
     P.part_and[blockIdx.x] = a;
   }
@@ -125,19 +93,8 @@ __global__ __launch_bounds__(ORD_BLK) void ord_plan_kernel(const OrderParams P) 
     o |= P.part_or[k];
     a &= P.part_and[k];
   }
-  o = wave_or64(o);
-  a = ~wave_or64(~a);
-  if (lane_id() == 0) {
-    wo[threadIdx.x >> 6] = o;
-    wa[threadIdx.x >> 6] = a;
-  }
-  __syncthreads();
+  ord_block_or_and(o, a, wo, wa);
   if (threadIdx.x != 0) return;
-#pragma unroll
-  for (uint32_t k = 1; k < ORD_WAVES; k++) {
-    o |= wo[k];
-    a &= wa[k];
-  }
   const uint64_t diff = n ? o ^ a : 0;  // the bits in which some two keys differ
   uint32_t cur = 0, any = 0;
   for (uint32_t p = 0; p < ORD_PASSES; p++) {
@@ -169,7 +126,9 @@ __device__ __forceinline__ OrdPair ord_fetch(const OrderParams &P, uint32_t p, u
   return x;
 }
 __device__ __forceinline__ uint32_t ord_digit(const OrderParams &P, uint32_t p, const OrdPair &x, const uint64_t *sb) {
-  return p == ORD_SEG_PASS ? ord_seg(sb, P.nseg, x.row) : (uint32_t)(x.key >> (8 * p)) & 0xFFu;
+  if (p != ORD_SEG_PASS) return (uint32_t)(x.key >> (8 * p)) & 0xFFu;
+  const uint32_t f = ord_seg(sb, P.nseg, x.row);
+  return P.bad ? 2 * f + P.bad[x.row] : f;  // (drp_keyorder.hip: the rows left out, behind their segment)
 }
 
 // the lanes of the wave that are valid and hold digit d (meaningless for a lane that is not valid)
@@ -301,11 +260,6 @@ __global__ __launch_bounds__(ORD_BLK) void ord_scatter_kernel(const OrderParams 
   }
 }
 
-// the source row at sorted position s, and its key
-__device__ __forceinline__ uint64_t ord_row_at(const OrderParams &P, uint32_t fs, uint64_t b0, uint64_t s) {
-  return fs ? (uint64_t)P.idx[fs - 1][s] : b0 + s;
-}
-
 // (3) the rows every segment keeps, and where the outputs start
 __global__ __launch_bounds__(64) void ord_cut_kernel(const OrderParams P, const OrdLimits L) {
   const OrdCtl &c = *P.ctl;
@@ -345,7 +299,8 @@ __global__ __launch_bounds__(256) void ord_gather_kernel(const OrderParams P) {
   if (j >= total) return;
   const OrdCtl &c = *P.ctl;
   const uint32_t f = ord_seg(ob, K, j);
-  const uint64_t s = rb[f] - c.b0 + (j - ob[f]);  // (< n: j - ob[f] < kept_f <= the segment's rows)
+  // (< n: start + j - ob[f] < start + kept_f <= the segment's rows)
+  const uint64_t s = rb[f] - c.b0 + (P.seg_start ? P.seg_start[f] : 0) + (j - ob[f]);
   const uint64_t i = ord_row_at(P, c.final_src, c.b0, s);
   const drp_change_src &R = P.rows;
   const RowOut &O = P.out;
@@ -367,59 +322,42 @@ __global__ __launch_bounds__(256) void ord_gather_kernel(const OrderParams P) {
 using namespace drp;
 
 
-namespace {
-struct OrdLayout {
-  uint64_t nwg, nscan, ctl, por, pand, key[2], idx[2], hist, bsum, end;
-  explicit OrdLayout(uint64_t cap) {
-    nwg = cap ? (cap + ORD_TILE - 1) / ORD_TILE : 1;
-    nscan = (ORD_BINS * nwg + ORD_SCAN - 1) / ORD_SCAN;
-    ctl = 0;
-    por = 256;
-    pand = por + al(nwg * 8);
-    key[0] = pand + al(nwg * 8);
-    key[1] = key[0] + al(cap * 8);
-    idx[0] = key[1] + al(cap * 8);
-    idx[1] = idx[0] + al(cap * 4);
-    hist = idx[1] + al(cap * 4);
-    bsum = hist + al(ORD_BINS * nwg * 4);
-    end = bsum + al(nscan * 4);
-  }
-};
-static_assert(sizeof(OrdCtl) <= 256, "the control block's place in the scratch");
-}  // namespace
-
 extern "C" uint64_t drp_order_scratch_bytes(uint64_t rows_cap) { return OrdLayout(rows_cap).end; }
+
+extern "C" void drp_launch_order_init(const OrderParams *P, hipStream_t st) {
+  hipLaunchKernelGGL(ord_init_kernel, dim3(1), dim3(128), 0, st, *P);
+}
+
+extern "C" void drp_launch_order_pass(const OrderParams *P, uint32_t p, hipStream_t st) {
+  const OrdLayout L(P->rows_cap);
+  const dim3 tiles((uint32_t)L.nwg), scans((uint32_t)L.nscan);
+  hipLaunchKernelGGL(ord_hist_kernel, tiles, dim3(ORD_BLK), 0, st, *P, p);
+  hipLaunchKernelGGL(ord_blocksum_kernel, scans, dim3(ORD_SCAN), 0, st, *P, p);
+  hipLaunchKernelGGL(ord_scanbase_kernel, scans, dim3(ORD_SCAN), 0, st, *P, p);
+  hipLaunchKernelGGL(ord_scatter_kernel, tiles, dim3(ORD_BLK), 0, st, *P, p);
+}
+
+// (no output holds more rows than rows_cap, nor more than the limits add up to: out_max)
+extern "C" void drp_launch_order_gather(const OrderParams *P, uint64_t out_max, hipStream_t st) {
+  const uint64_t most = out_max < P->rows_cap ? out_max : P->rows_cap;
+  if (most) hipLaunchKernelGGL(ord_gather_kernel, dim3((uint32_t)((most + 255) / 256)), dim3(256), 0, st, *P);
+}
 
 extern "C" hipError_t drp_launch_order(const OrderParams *Pp, const OrdLimits *lim, uint64_t out_max, void *scratch,
                                        hipStream_t st) {
   OrderParams P = *Pp;
   const OrdLayout L(P.rows_cap);
-  uint8_t *sc = static_cast<uint8_t *>(scratch);
-  P.ctl = reinterpret_cast<OrdCtl *>(sc + L.ctl);
-  P.part_or = reinterpret_cast<uint64_t *>(sc + L.por);
-  P.part_and = reinterpret_cast<uint64_t *>(sc + L.pand);
-  for (int k = 0; k < 2; k++) {
-    P.key[k] = reinterpret_cast<uint64_t *>(sc + L.key[k]);
-    P.idx[k] = reinterpret_cast<uint32_t *>(sc + L.idx[k]);
-  }
-  P.hist = reinterpret_cast<uint32_t *>(sc + L.hist);
-  P.bsum = reinterpret_cast<uint32_t *>(sc + L.bsum);
-  const dim3 tiles((uint32_t)L.nwg), scans((uint32_t)L.nscan);
-  hipLaunchKernelGGL(ord_init_kernel, dim3(1), dim3(128), 0, st, P);
-  hipLaunchKernelGGL(ord_reduce_kernel, tiles, dim3(ORD_BLK), 0, st, P);
+  L.place(P, scratch);
+  drp_launch_order_init(&P, st);
+  hipLaunchKernelGGL(ord_reduce_kernel, dim3((uint32_t)L.nwg), dim3(ORD_BLK), 0, st, P);
   hipLaunchKernelGGL(ord_plan_kernel, dim3(1), dim3(ORD_BLK), 0, st, P);
   for (uint32_t p = 0; p < ORD_PASSES; p++) {
     if (p == ORD_SEG_PASS && P.nseg == 1) break;
-    hipLaunchKernelGGL(ord_hist_kernel, tiles, dim3(ORD_BLK), 0, st, P, p);
-    hipLaunchKernelGGL(ord_blocksum_kernel, scans, dim3(ORD_SCAN), 0, st, P, p);
-    hipLaunchKernelGGL(ord_scanbase_kernel, scans, dim3(ORD_SCAN), 0, st, P, p);
-    hipLaunchKernelGGL(ord_scatter_kernel, tiles, dim3(ORD_BLK), 0, st, P, p);
+    drp_launch_order_pass(&P, p, st);
   }
   drp_dbg_mark("order_sort", st);
   hipLaunchKernelGGL(ord_cut_kernel, dim3(1), dim3(64), 0, st, P, *lim);
-  // (no output holds more rows than rows_cap, nor more than the limits add up to: out_max)
-  const uint64_t most = out_max < P.rows_cap ? out_max : P.rows_cap;
-  if (most) hipLaunchKernelGGL(ord_gather_kernel, dim3((uint32_t)((most + 255) / 256)), dim3(256), 0, st, P);
+  drp_launch_order_gather(&P, out_max, st);
   drp_dbg_mark("order_gather", st);
   return hipGetLastError();
 }

@@ -635,6 +635,69 @@ int drp_order_device(drp_ctx *c, const drp_change_src *rows, const uint64_t *row
   return DRP_OK;
 }
 
+// ---- key-ordered listing ------------------------------------------------------------------------
+int drp_order_keys_device(drp_ctx *c, const uint8_t *heap, uint64_t heap_bytes, const drp_change_src *rows,
+                          const uint64_t *row_base, uint32_t nseg, uint64_t rows_cap, const drp_key_page *pages,
+                          uint32_t flags, const drp_change_src *out_rows, const uint64_t *sel_idx,
+                          uint64_t *out_sel_idx, uint64_t *out_base, uint64_t *totals) {
+  if (!c || !rows || !row_base || !out_rows || !out_base || nseg == 0 || nseg > DRP_FANOUT_MAX) return DRP_E_INVAL;
+  if ((flags & ~(uint32_t)DRP_KEYORDER_KEEP_TIES) || (out_sel_idx && !sel_idx) || rows_cap > 0xFFFFFFFFull)
+    return DRP_E_INVAL;
+  if (rows_cap && (!src_cols_ok(rows) || !src_cols_ok(out_rows))) return DRP_E_INVAL;
+  if (out_rows->change && out_rows->change == rows->change) return DRP_E_INVAL;  // (no in-place sort)
+  if (!heap && heap_bytes) return DRP_E_INVAL;
+  const uint32_t page_bits = DRP_KEYPAGE_FROM | DRP_KEYPAGE_AFTER | DRP_KEYPAGE_UNTIL;
+  OrdkPages G = {};
+  uint64_t out_max = 0, nbound = 0;
+  for (uint32_t f = 0; f < DRP_FANOUT_MAX; f++) {
+    G.limit[f] = ~0ull;
+    if (!pages || f >= nseg) continue;
+    const drp_key_page &pg = pages[f];
+    if ((pg.flags & ~page_bits) || ((pg.flags & DRP_KEYPAGE_FROM) && (pg.flags & DRP_KEYPAGE_AFTER))) return DRP_E_INVAL;
+    if (pg.lo_len > DRP_KEYORDER_MAX_BYTES || pg.hi_len > DRP_KEYORDER_MAX_BYTES) return DRP_E_INVAL;
+    if ((pg.lo_len && !pg.lo) || (pg.hi_len && !pg.hi)) return DRP_E_INVAL;
+    G.limit[f] = pg.limit;
+    G.flags[f] = pg.flags;
+    if (pg.flags & (DRP_KEYPAGE_FROM | DRP_KEYPAGE_AFTER)) {
+      G.lo_off[f] = (uint32_t)nbound;
+      G.lo_len[f] = pg.lo_len;
+      nbound += pg.lo_len;
+    }
+    if (pg.flags & DRP_KEYPAGE_UNTIL) {
+      G.hi_off[f] = (uint32_t)nbound;
+      G.hi_len[f] = pg.hi_len;
+      nbound += pg.hi_len;
+    }
+  }
+  for (uint32_t f = 0; f < nseg; f++) out_max = out_max + G.limit[f] < out_max ? ~0ull : out_max + G.limit[f];
+  if (flags & DRP_KEYORDER_KEEP_TIES) out_max = ~0ull;  // (a cut that moves to its run's end passes the limit)
+  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+  std::vector<uint8_t> bounds(nbound);  // (the bounds in use, end to end; copied before the call's one wait ends)
+  for (uint32_t f = 0; pages && f < nseg; f++) {
+    if (G.lo_len[f]) memcpy(bounds.data() + G.lo_off[f], pages[f].lo, G.lo_len[f]);
+    if (G.hi_len[f]) memcpy(bounds.data() + G.hi_off[f], pages[f].hi, G.hi_len[f]);
+  }
+  // (the decode scratch: free between decodes, and every user is ordered on the ctx's stream)
+  if (!c->scratch.ensure(drp_keyorder_scratch_bytes(rows_cap, nbound))) return DRP_E_NOMEM;
+  KeyOrderParams K = {};
+  OrderParams &P = K.o;
+  P.rows = *rows;
+  P.row_base = row_base;
+  P.nseg = nseg;
+  P.flags = flags;
+  P.rows_cap = rows_cap;
+  P.out = row_out(out_rows, out_sel_idx);
+  P.sel_idx = sel_idx;
+  P.out_base = out_base;
+  P.skip = c->order_skip ? 1 : 0;
+  K.heap = heap;
+  K.heap_bytes = heap_bytes;
+  K.bounds_bytes = nbound;
+  K.totals = totals;
+  CHK(drp_launch_keyorder(&K, &G, bounds.data(), out_max, c->scratch.p, c->st));
+  return DRP_OK;
+}
+
 uint64_t drp_store_table_bytes(uint64_t max_keys) { return 8 * drp_store_nslots(max_keys); }
 
 int drp_store_init(drp_ctx *c, const drp_store *s) {

@@ -33,7 +33,7 @@ EXPORTS = [
     "drp_latest_device", "drp_latest_staged", "drp_set_latest_hash_mask",
     "drp_fanout_latest_device", "drp_fanout_latest_staged", "drp_set_fanout_latest_pass",
     "drp_store_table_bytes", "drp_store_init", "drp_store_merge_device", "drp_store_merge_staged",
-    "drp_store_compact", "drp_store_query", "drp_order_device",
+    "drp_store_compact", "drp_store_query", "drp_order_device", "drp_order_keys_device",
     "drp_store_merge_report_device", "drp_store_merge_news_staged", "drp_fanout_news_staged",
     "drp_store_lookup_device", "drp_store_lookup_staged",
     "drp_store_load_device", "drp_store_rehash_device",
@@ -52,6 +52,8 @@ FANOUT_MAX = 64
 DIGEST_MAX_BITS = 16
 DIGEST_MAX_SUB_BITS = 8
 ORDER_KEEP_TIES = 1
+KEYORDER_KEEP_TIES, KEYORDER_MAX_BYTES = 1, 4096
+KEYPAGE_FROM, KEYPAGE_AFTER, KEYPAGE_UNTIL = 1, 2, 4
 MERGE_NONE, MERGE_INSERTED, MERGE_REPLACED, MERGE_UNCHANGED, MERGE_STALE, MERGE_SKIPPED = 0, 1, 2, 3, 4, 5
 REPORT_KEEP_BLOBS = 1
 LOOKUP_NONE, LOOKUP_ABSENT, LOOKUP_BEHIND, LOOKUP_LEVEL, LOOKUP_AHEAD = 0, 1, 2, 3, 4
@@ -128,6 +130,52 @@ def make_filter(change_range=None, subset=None, subset_none=False, key_prefix=No
         f.key_prefix, f.key_prefix_len = C.cast(b, P), len(key_prefix)
     f.flags = fl if flags is None else flags
     return f
+
+
+class KeyPage(C.Structure):
+    """drp_key_page; make one with make_key_page (it keeps the bound bytes alive)."""
+    _fields_ = [("flags", U32), ("lo_len", U32), ("hi_len", U32), ("reserved", U32), ("lo", P), ("hi", P),
+                ("limit", U64)]
+
+
+def make_key_page(from_=None, after=None, until=None, limit=None, flags=None):
+    """A drp_key_page: from_=bytes keeps key >= from_, after=bytes keeps key > after (a resume
+    cursor; not together with from_), until=bytes keeps key < until, limit=rows (None: no limit). An
+    empty bound is a bound. flags overrides the flag word (tests of the error returns)."""
+    g = KeyPage()
+    g._keep = []
+    fl = 0
+
+    def put(b):
+        buf = C.create_string_buffer(bytes(b), max(1, len(b)))
+        g._keep.append(buf)
+        return C.cast(buf, P), len(b)
+
+    if from_ is not None:
+        fl |= KEYPAGE_FROM
+        g.lo, g.lo_len = put(from_)
+    if after is not None:
+        fl |= KEYPAGE_AFTER
+        g.lo, g.lo_len = put(after)
+    if until is not None:
+        fl |= KEYPAGE_UNTIL
+        g.hi, g.hi_len = put(until)
+    g.limit = 0xFFFFFFFFFFFFFFFF if limit is None else int(limit)
+    g.flags = fl if flags is None else flags
+    return g
+
+
+def key_page_array(pages):
+    """A C array of drp_key_page from make_key_page results (None: the page that keeps everything).
+    Keeps the pages, and with them their bound bytes, alive."""
+    arr = (KeyPage * max(1, len(pages)))()
+    arr._keep = list(pages)
+    for k, g in enumerate(pages):
+        if g is not None:
+            C.memmove(C.byref(arr, k * C.sizeof(KeyPage)), C.byref(g), C.sizeof(KeyPage))
+        else:
+            arr[k].limit = 0xFFFFFFFFFFFFFFFF
+    return arr
 
 
 class Splice(C.Structure):
@@ -263,6 +311,8 @@ def lib():
         L.drp_store_compact.argtypes = [P, C.POINTER(StoreDesc), P, U64]
         L.drp_store_query.argtypes = [P, C.POINTER(StoreDesc), C.POINTER(StoreInfo)]
         L.drp_order_device.argtypes = [P, C.POINTER(ChangeSrc), P, U32, U64, P, U32, C.POINTER(ChangeSrc), P, P, P]
+        L.drp_order_keys_device.argtypes = [P, P, U64, C.POINTER(ChangeSrc), P, U32, U64, C.POINTER(KeyPage), U32,
+                                            C.POINTER(ChangeSrc), P, P, P, P]
         L.drp_digest_device.argtypes = [P, P, U64, C.POINTER(Frames), C.POINTER(Changes), U64, C.POINTER(Filter), U32,
                                         P, P]
         L.drp_digest_diff_device.argtypes = [P, P, P, U32, P, P]
@@ -294,7 +344,8 @@ def lib():
                   "drp_fanout_device", "drp_fanout_staged", "drp_latest_device", "drp_latest_staged",
                   "drp_set_latest_hash_mask", "drp_fanout_latest_device", "drp_fanout_latest_staged",
                   "drp_set_fanout_latest_pass", "drp_store_init", "drp_store_merge_device", "drp_store_merge_staged",
-                  "drp_store_compact", "drp_store_query", "drp_order_device", "drp_digest_device", "drp_digest_diff_device",
+                  "drp_store_compact", "drp_store_query", "drp_order_device", "drp_order_keys_device",
+                  "drp_digest_device", "drp_digest_diff_device",
                   "drp_store_merge_report_device", "drp_store_merge_news_staged", "drp_fanout_news_staged",
                   "drp_store_lookup_device", "drp_store_lookup_staged",
                   "drp_store_load_device", "drp_store_rehash_device",
@@ -910,6 +961,32 @@ class Ctx:
         if ref is not None:
             self.order_torch_after(ref)
 
+    # ---- key-ordered listing: a fan-out's outputs in key order, with a key range and a page --------
+    def order_keys_device(self, heap_t, rows, row_base_t, nseg, rows_cap, out_rows, out_base_t, pages=None,
+                          keep_ties=False, sel_idx_t=None, out_sel_idx_t=None, totals_t=None, flags=None):
+        """drp_order_keys_device over torch CUDA tensors (on this ctx's stream; the call waits for the
+        stream once inside): heap_t the uint8 tensor the rows' offsets point into (None: no heap),
+        rows, row_base_t, out_rows, out_base_t, sel_idx_t and out_sel_idx_t as order_device takes them.
+        Output f holds the rows of segment f in ascending (key bytes, subset absent first, subset
+        bytes, input position), restricted to pages[f]'s key range and cut to its limit (pages: None,
+        or a list of make_key_page results / None per segment); keep_ties: a cut inside a run of equal
+        key moves to the run's end. totals_t (int64, 2, optional): the rows that took part, and the
+        rows left out (a range outside the heap, or a key or subset above KEYORDER_MAX_BYTES). flags
+        overrides the flag word (tests of the error returns)."""
+        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        mk = lambda r: C.byref(ChangeSrc(*[tp(r.get(k)) for k in SRC_COLS])) if r is not None else None
+        pg = key_page_array(list(pages)) if pages is not None else None
+        fl = (KEYORDER_KEEP_TIES if keep_ties else 0) if flags is None else flags
+        ref = next((t for t in (row_base_t, out_base_t, heap_t) if t is not None), None)
+        if ref is not None:
+            self.order_after_torch(ref)
+        rc = self.L.drp_order_keys_device(self.h, tp(heap_t), heap_t.numel() if heap_t is not None else 0, mk(rows),
+                                          tp(row_base_t), nseg, rows_cap, pg, fl, mk(out_rows), tp(sel_idx_t),
+                                          tp(out_sel_idx_t), tp(out_base_t), tp(totals_t))
+        _chk("drp_order_keys_device", rc)
+        if ref is not None:
+            self.order_torch_after(ref)
+
     # ---- digest / reconcile: what differs between two stores ------------------------------------
     def digest_device(self, wire_t, cols, n, filter, bits, cells_t, totals_t=None):
         """drp_digest_device over torch CUDA tensors (asynchronous, on this ctx's stream): wire_t and
@@ -1370,6 +1447,57 @@ class Store:
         last = dict(zip(ends, (int(v) for v in last)))
         return [(o[int(fo[ob[f]]):int(fo[ob[f + 1]])].tobytes(), ob[f + 1] - ob[f], last.get(ob[f + 1] - 1)
                  if ob[f + 1] > ob[f] else None) for f in range(K)]
+
+    def list_keys(self, filters, pages=None, keep_ties=True, n=None):
+        """The key-ordered listing: fanout_rows over the store, one order_keys_device and one
+        encode_device with the arena as the heap. filters as fanout takes them (the listing's subset,
+        key prefix and version bound: subset=, subset_none=, key_prefix=, change_range=); pages: None,
+        or per filter a make_key_page result or None (from_ / after / until bound the key, limit the
+        rows of a page); keep_ties: a page never ends inside a run of equal key (the rows of one key
+        under different subsets). Returns, per filter, (wire bytes, rows sent, last_key): the rows in
+        ascending (key, subset) as change frames, their number, and the key of the last one (None for
+        an empty page). Raises ValueError naming the count if rows were left out (a key or subset
+        above KEYORDER_MAX_BYTES). The paging loop:
+
+            after = None
+            while True:
+                wire, sent, last_key = store.list_keys(
+                    [make_filter(key_prefix=b"users/")], [make_key_page(after=after, limit=500)])[0]
+                if not sent:
+                    break
+                send(wire)
+                after = last_key"""
+        import torch
+        K = len(filters)
+        rows, base = self.fanout_rows(filters, n)
+        total = int(base.cpu()[K])  # (torch's stream was ordered after the ctx's)
+        if total == 0:
+            return [(b"", 0, None)] * K
+        dev = self.arena.device
+        out_rows = {k: torch.zeros(total, dtype=v.dtype, device=dev) for k, v in rows.items()}
+        out_base = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+        totals = torch.zeros(2, dtype=torch.int64, device=dev)
+        self.ctx.order_keys_device(self._view(), rows, base, K, total, out_rows, out_base, pages=pages,
+                                   keep_ties=keep_ties, totals_t=totals)
+        ob = [int(v) for v in out_base.cpu()]
+        left = int(totals.cpu()[1])
+        if left:
+            raise ValueError(f"list_keys: {left} rows left out of the order (key or subset too long, or outside the arena)")
+        sent = ob[K]
+        if sent == 0:
+            return [(b"", 0, None)] * K
+        src = ChangeSrc(*[C.c_void_p(out_rows[k].data_ptr()) for k in SRC_COLS])
+        need = U64()
+        _chk("drp_encode_size", self.ctx.L.drp_encode_size(self.ctx.h, C.byref(src), sent, C.byref(need)))
+        foff = torch.zeros(sent + 1, dtype=torch.int64, device=dev)
+        out = torch.zeros(max(int(need.value), 1), dtype=torch.uint8, device=dev)
+        self.ctx.encode_device(out_rows, self._view(), sent, foff, out, int(need.value))
+        fo, o = foff.cpu().numpy(), out.cpu().numpy()
+        ends = torch.tensor([ob[f + 1] - 1 for f in range(K) if ob[f + 1] > ob[f]], dtype=torch.int64, device=dev)
+        koff, klen = out_rows["key_off"][ends].cpu().tolist(), out_rows["key_len"][ends].cpu().tolist()
+        last = {int(e): bytes(self.arena[o_:o_ + l_].cpu().numpy()) for e, o_, l_ in zip(ends.cpu().tolist(), koff, klen)}
+        return [(o[int(fo[ob[f]]):int(fo[ob[f + 1]])].tobytes(), ob[f + 1] - ob[f],
+                 last[ob[f + 1] - 1] if ob[f + 1] > ob[f] else None) for f in range(K)]
 
     def _view(self):
         return self.arena[:self.arena_bytes] if self.arena_bytes else self.arena[:0]

@@ -49,6 +49,9 @@
  *   drp_order_device
  *       -> no reference counterpart: the rows of every fan-out output in ascending `change` (schema
  *          messages/schema.proto:1-8), cut to a per-peer limit (a catch-up a peer can resume or page).
+ *   drp_order_keys_device
+ *       -> no reference counterpart: those rows in ascending (key, subset) byte order, cut to a key
+ *          range and a page per peer (a listing in key order that a peer can resume after a key).
  *   drp_digest_device / drp_digest_diff_device / drp_select_buckets_device
  *       -> no reference counterpart: a digest of the rows per bucket of identities, the buckets in
  *          which two digests differ, and the select of those buckets' rows (two hubs without a shared
@@ -873,6 +876,68 @@ int drp_store_rehash_device(drp_ctx *ctx, const drp_store *s, uint64_t *report /
 int drp_order_device(drp_ctx *ctx, const drp_change_src *rows, const uint64_t *row_base, uint32_t nseg,
                      uint64_t rows_cap, const uint64_t *limit, uint32_t flags, const drp_change_src *out_rows,
                      const uint64_t *sel_idx, uint64_t *out_sel_idx, uint64_t *out_base);
+
+/* ---- key-ordered listing: a fan-out's outputs in key order, with a key range and a page -------- */
+/* Row order and `change` order mean nothing to a client that iterates a key/value store: "list what
+ * is under users/, 500 at a time, resuming after the last key I saw", "give me the range [a, m)",
+ * "export this subset in a stable order" need the rows in key order. The call below sits where
+ * drp_order_device does, between a fan-out and the encode, and takes the same rows; the listing's
+ * subset, key prefix and version bound are the fan-out's ordinary filters. No reference counterpart
+ * (the reference has no relay); the fields read are `key` and `subset` of messages/schema.proto:1-8.
+ *   Input and output shape: rows, row_base, nseg, rows_cap, out_rows, sel_idx, out_sel_idx and out_base
+ * are exactly drp_order_device's, with its rule for an input that is not valid (out_base all 0,
+ * nothing else written; totals, if given, {0, 0}) and its rule that entries of out_rows and
+ * out_sel_idx at or beyond out_base[nseg] are left untouched. heap / heap_bytes (device) is what the
+ * rows' offsets are absolute into: the wire of a decoded batch, or a store's arena.
+ *   Order: within a segment ascending by the tuple (key bytes; subset presence, absent first; subset
+ * bytes; input position). Byte strings compare as unsigned bytes, lexicographically, a proper prefix
+ * first: "ab" < "ab\0" < "ab\0\0" < "ab\x01", and 0x7F < 0x80 < 0xFF. The key is the major field, so
+ * a key range is one contiguous run of the sorted segment.
+ *   Rows left out: a row whose key range [key_off, key_off + key_len) leaves [0, heap_bytes), or,
+ * with DRP_F_SUBSET, whose subset range does, or whose key or (with DRP_F_SUBSET) subset is longer
+ * than DRP_KEYORDER_MAX_BYTES, is never read, is in no output and is counted in totals[1]; totals[0]
+ * counts the rows that took part (totals: device, 2 entries, may be NULL). No byte at or beyond heap +
+ * heap_bytes is read, not even as the padding of a word.
+ *   Range: pages is a HOST array of nseg entries, and so are the lo / hi bytes it points to; all are
+ * read before the call returns. Segment f keeps the rows of its sorted order whose key lies inside
+ * pages[f]'s bounds: FROM key >= lo, AFTER key > lo (a resume cursor), UNTIL key < hi. The bounds apply
+ * to the key only; an empty bound is a bound (lo or hi may be NULL when its length is 0); lo >= hi
+ * keeps nothing. A NULL pages, or flags == 0 with limit == UINT64_MAX, keeps everything.
+ *   Limit: of the kept run, segment f keeps the first min(count, limit) rows. With
+ * DRP_KEYORDER_KEEP_TIES a cut inside a run of equal key (the same key bytes; the subsets may differ)
+ * moves forward to the end of that run: the output may then exceed the limit, never the run, a limit
+ * of 0 still keeps nothing, and a peer that resumes with AFTER = the last key sent loses no row and
+ * every non-empty page makes progress. Without the flag the cut is exact. */
+#define DRP_KEYORDER_KEEP_TIES 0x01
+#define DRP_KEYORDER_MAX_BYTES 4096 /* longest key / subset that takes part, longest bound */
+
+#define DRP_KEYPAGE_FROM  0x01 /* keep key >= lo */
+#define DRP_KEYPAGE_AFTER 0x02 /* keep key >  lo  (a resume cursor); with FROM: DRP_E_INVAL */
+#define DRP_KEYPAGE_UNTIL 0x04 /* keep key <  hi */
+typedef struct drp_key_page {   /* HOST, one per segment; lo / hi HOST too, read before the call returns */
+  uint32_t flags, lo_len, hi_len, reserved;
+  const uint8_t *lo, *hi;       /* may be NULL when the length is 0 (an empty bound is a bound) */
+  uint64_t limit;               /* UINT64_MAX: none */
+} drp_key_page;
+/* The result is a function of the input alone. Device pointers only (but pages and its bounds), on
+ * drp_stream(ctx). Host waits: exactly one. After a first pass over the rows the call waits for the
+ * stream to read 32 bytes (the longest key and subset that take part, the counts), which size the
+ * launch chain: one run of the sort's digit passes per 8-byte word of the longest key and of the
+ * longest subset, and none for a field no row has. Which digits of a word run is decided on the
+ * device, as in drp_order_device, without a further wait; everything after the wait is asynchronous.
+ * DRP_E_INVAL: every case of drp_order_device (nseg 0 or above DRP_FANOUT_MAX; a NULL rows, row_base,
+ * out_rows or out_base, or, with rows_cap > 0, a NULL array in rows or out_rows; out_sel_idx without
+ * sel_idx; out_rows->change == rows->change; rows_cap above 2^32 - 1); a NULL heap with heap_bytes >
+ * 0; unknown bits in flags or in a page's flags; FROM together with AFTER; a bound longer than
+ * DRP_KEYORDER_MAX_BYTES; a NULL bound with a nonzero length. All of these are reported before the
+ * ctx is touched. Scratch, from the ctx's (DRP_E_NOMEM if it cannot be had): drp_order_device's (24
+ * bytes per entry of rows_cap, about 1 KiB per 4096 entries), one more byte per entry, 1 KiB, and the
+ * bounds' bytes (at most 8 KiB per segment). */
+int drp_order_keys_device(drp_ctx *ctx, const uint8_t *heap, uint64_t heap_bytes,
+                          const drp_change_src *rows, const uint64_t *row_base, uint32_t nseg,
+                          uint64_t rows_cap, const drp_key_page *pages /* nseg, may be NULL */,
+                          uint32_t flags, const drp_change_src *out_rows, const uint64_t *sel_idx,
+                          uint64_t *out_sel_idx, uint64_t *out_base, uint64_t *totals /* device, 2, may be NULL */);
 
 /* ---- digest / reconcile: what differs between two stores, without a shared version ---------- */
 /* "What changed since T?" needs two parties that share one `change` counter. Two hubs that each hold

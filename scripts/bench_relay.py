@@ -89,6 +89,18 @@ probe, and the host relay through drp_relay_staged against the host round trip i
               encode is then also given over the parent's figure. --order-profile: K = 64 and the plain
               calls alone, for a rocprofv3 --kernel-trace --stats run (profiles/relay/order_kernel_stats.csv).
 
+  keyorder    (--keyorder-out, default profiles/relay/keyorder_bench.json; no other leg runs) The store
+              leg's final store, listed in key order as K = 1 and K = 64 version-bounded listings that
+              share its rows out among them, over its own keys and over the same keys behind a shared 16-byte prefix (a
+              second heap built here). HIP events, three warm-up rounds and --iters timed ones:
+              drp_order_keys_device whole, the same with limit 0 for every peer (prepass, sort and cut:
+              no gather), and drp_order_device over the same rows with every pass left on (a second ctx
+              opened under DRP_ORDER_SKIP=0): both share the pass kernels, so time per active digit
+              pass is compared. The host alternative: the keys copied to the host and sorted there
+              with numpy's stable argsort, per segment, on one core (wall clock, copy included). The
+              K = 1 permutation is checked against that argsort. Launches and active passes are
+              computed here from the keys by the launcher's rule; the call waits for the stream once.
+
   news        (--news-out, default profiles/relay/news_bench.json; no other leg runs) The store leg's
               stream and sequences of 8 merges into an empty store, three ways: drp_store_merge_device,
               drp_store_merge_report_device with a NULL report, and with a full report (outcome,
@@ -1245,6 +1257,113 @@ def order_leg(ctx, drp_amd, torch, frames, iters, parent=None, profile=False):
     return res
 
 
+# ---- key-ordered listing ----------------------------------------------------------------------------
+
+KEYORDER_KS = (1, 64)
+KEYORDER_PREFIX = b"tenant-00000001/"
+
+
+def _keyorder_chain(mat, lens, K):
+    """The launcher's rule applied to the keys (mat: rows x longest, zero padded; no subsets): the
+    fields launched, the digit passes that run in them (those in which two values differ), kernels."""
+    longest = int(lens.max())
+    fields, active, launches = 0, 0, 3 + 2 + (5 if K > 1 else 0)
+
+    def field(vals, p_lo, p_hi):
+        nonlocal fields, active, launches
+        diff = int(np.bitwise_or.reduce(vals)) ^ int(np.bitwise_and.reduce(vals))
+        fields += 1
+        active += sum(1 for p in range(p_lo, p_hi) if (diff >> (8 * p)) & 0xFF)
+        launches += 2 + 4 * (p_hi - p_lo)
+
+    field(lens.astype(np.uint64), 0, 2)
+    nw = (longest + 7) // 8
+    pad = np.zeros((mat.shape[0], nw * 8), np.uint8)
+    pad[:, :longest] = mat
+    words = pad.reshape(-1, nw, 8).view(">u8")[:, :, 0].astype(np.uint64)
+    shared = 0  # leading words that lie whole inside every key and are the same in all: not launched
+    while shared < int(lens.min()) // 8 and (words[:, shared] == words[0, shared]).all():
+        shared += 1
+    for w in range(nw - 1, shared - 1, -1):
+        field(words[:, w], 8 - longest % 8 if w == nw - 1 and longest % 8 else 0, 8)
+    return {"fields": fields, "shared_prefix_words": shared, "active_digit_passes": active + (1 if K > 1 else 0), "launches": launches, "host_waits": 1}
+
+
+def keyorder_leg(ctx, drp_amd, torch, frames, iters):
+    import time
+    dev = torch.device("cuda", 0)
+    store, keys, n = _final_store(ctx, drp_amd, torch, frames)
+    ch = store.cols["change"][:keys].cpu().numpy()
+    stat = _timers(ctx, torch, dev, iters)
+    os.environ["DRP_ORDER_SKIP"] = "0"  # (read when a ctx opens: ctx2 runs every pass)
+    ctx2 = drp_amd.Ctx(0)
+    del os.environ["DRP_ORDER_SKIP"]
+    stat2 = _timers(ctx2, torch, dev, iters)
+    res = {"frames": n, "keys": keys, "iters": iters}
+    for K in KEYORDER_KS:
+        # K version-bounded listings that share the store's rows out among them (change is 1 .. 100)
+        edge = [0] + [(100 * (f + 1)) // K + 1 for f in range(K - 1)] + [2**64]
+        flt = [drp_amd.make_filter(change_range=(edge[f], edge[f + 1] - 1)) for f in range(K)]
+        total = keys
+        rows = _row_tensors(torch, dev, total)
+        rb_t = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+        ctx.fanout_device(store.arena, store.cols, store.max_keys, flt, rows, total, None, rb_t)
+        torch.cuda.synchronize()
+        rb = rb_t.cpu().numpy()
+        assert int(rb[K]) == total and not bool((rows["flags"] & 1).any())
+        out_rows = _row_tensors(torch, dev, total)
+        ob_t = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+        osel = torch.zeros(total, dtype=torch.int64, device=dev)
+        tot_t = torch.zeros(2, dtype=torch.int64, device=dev)
+        none = [drp_amd.make_key_page(limit=0)] * K
+        r = {"filters": K, "rows": total}
+        r["order_every_pass_ms"] = stat2(lambda: ctx2.order_device(rows, rb_t, K, total, out_rows, ob_t))
+        r["order_every_pass_digit_passes"] = 8 + (1 if K > 1 else 0)
+        # the keys on the host: the copy and the sort a peer would do today
+        t0 = time.perf_counter()
+        arena = store.arena.cpu().numpy()
+        koff, klen = rows["key_off"].cpu().numpy(), rows["key_len"].cpu().numpy()
+        t1 = time.perf_counter()
+        longest = int(klen.max())
+        mat = arena[np.minimum(koff[:, None] + np.arange(longest), len(arena) - 1)]
+        mat[np.arange(longest)[None, :] >= klen[:, None]] = 0
+        t2 = time.perf_counter()
+        assert not (mat == 0).any(), "numpy's S compare needs keys without NUL bytes"
+        fixed = np.ascontiguousarray(mat).view("S%d" % longest)[:, 0]
+        perm = [int(rb[f]) + np.argsort(fixed[int(rb[f]):int(rb[f + 1])], kind="stable") for f in range(K)]
+        t3 = time.perf_counter()
+        r["host_numpy"] = {"copy_ms": (t1 - t0) * 1e3, "gather_keys_ms": (t2 - t1) * 1e3, "argsort_ms": (t3 - t2) * 1e3,
+                           "total_ms": (t3 - t0) * 1e3}
+        for name in ("own_keys", "prefix16"):
+            if name == "own_keys":
+                heap, src, m = store.arena, rows, mat
+            else:  # the same keys behind a shared prefix, in a heap of their own
+                m = np.concatenate([np.tile(np.frombuffer(KEYORDER_PREFIX, np.uint8), (total, 1)), mat], axis=1)
+                lens2 = klen.astype(np.int64) + 16
+                heap = torch.from_numpy(m[np.arange(m.shape[1])[None, :] < lens2[:, None]]).to(dev)
+                off2 = torch.from_numpy(np.concatenate([[0], np.cumsum(lens2)[:-1]])).to(dev)
+                src = dict(rows, key_off=off2, key_len=rows["key_len"] + 16)
+            lens = klen.astype(np.int64) + (0 if name == "own_keys" else 16)
+            w = _keyorder_chain(m, lens, K)
+            ctx.order_keys_device(heap, src, rb_t, K, total, out_rows, ob_t, sel_idx_t=torch.arange(total, device=dev),
+                                  out_sel_idx_t=osel, totals_t=tot_t)
+            torch.cuda.synchronize()
+            assert [int(v) for v in tot_t.cpu()] == [total, 0] and [int(v) for v in ob_t.cpu()] == [int(v - rb[0]) for v in rb]
+            assert np.array_equal(osel.cpu().numpy(), np.concatenate(perm)), "key order permutation"
+            w["call_ms"] = stat(lambda: ctx.order_keys_device(heap, src, rb_t, K, total, out_rows, ob_t))
+            w["sort_ms"] = stat(lambda: ctx.order_keys_device(heap, src, rb_t, K, total, out_rows, ob_t, pages=none))
+            w["sort_ms_per_active_pass"] = w["sort_ms"]["median"] / max(1, w["active_digit_passes"])
+            w["order_every_pass_ms_per_pass"] = r["order_every_pass_ms"]["median"] / r["order_every_pass_digit_passes"]
+            w["host_over_device"] = r["host_numpy"]["total_ms"] / w["call_ms"]["median"]
+            r[name] = w
+        res[f"K{K}"] = r
+        print("keyorder", K, r, file=sys.stderr, flush=True)
+        rows = out_rows = osel = src = heap = mat = m = None
+        torch.cuda.empty_cache()
+    ctx2.close()
+    return res
+
+
 # ---- digest / reconcile -----------------------------------------------------------------------------
 
 DIGEST_BITS = (8, 12, 16)
@@ -1827,6 +1946,9 @@ def main():
     ap.add_argument("--news-baseline", default=None, help="such a file of the parent commit, read into the news leg's result")
     ap.add_argument("--order-out", nargs="?", default=None, const=os.path.join(ROOT, "profiles", "relay", "order_bench.json"),
                     help="run the ordered catch-up leg alone and write its JSON line here")
+    ap.add_argument("--keyorder-out", nargs="?", default=None,
+                    const=os.path.join(ROOT, "profiles", "relay", "keyorder_bench.json"),
+                    help="run the key-ordered listing leg alone and write its JSON line here")
     ap.add_argument("--order-profile", action="store_true",
                     help="with --order-out: K = 64 and the plain drp_order_device calls alone (for a kernel trace)")
     ap.add_argument("--order-baseline-out", default=None,
@@ -1894,6 +2016,13 @@ def main():
         with open(a.news_out, "w") as f:
             f.write(json.dumps(nw) + "\n")
         print(json.dumps(nw))
+        return
+    if a.keyorder_out:
+        with drp_amd.Ctx(0) as ctx:
+            ko = {"bench": "relay_keyorder", "device": keyorder_leg(ctx, drp_amd, torch, a.frames, a.iters)}
+        with open(a.keyorder_out, "w") as f:
+            f.write(json.dumps(ko) + "\n")
+        print(json.dumps(ko))
         return
     if a.order_baseline_out:
         with drp_amd.Ctx(0) as ctx:
