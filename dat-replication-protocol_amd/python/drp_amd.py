@@ -20,29 +20,6 @@ TYPE_CHANGE, TYPE_BLOB, FRAME_CONT, FRAME_PARTIAL = 1, 2, 0x40, 0x80
 F_SUBSET, F_VALUE, F_BAD, F_MISSING, F_KEY_ASCII, F_KEY_UTF8 = 1, 2, 4, 8, 0x10, 0x20
 ERR_NONE, ERR_TYPE, ERR_LEN, ERR_VARINT, ERR_CHANGE, ERR_REQUIRED = 0, 1, 2, 3, 4, 5
 TAIL_NONE, TAIL_HEADER, TAIL_CHANGE, TAIL_BLOB = 0, 1, 2, 3
-
-EXPORTS = [
-    "drp_abi_version", "drp_open", "drp_close", "drp_stream", "drp_synchronize",
-    "drp_last_timing", "drp_set_tile", "drp_set_strict", "drp_set_exact", "drp_set_key_post",
-    "drp_set_blob_skip", "drp_decode_scratch_bytes",
-    "drp_decode_device", "drp_decode_batch", "drp_decode_stage", "drp_decode_stage_v", "drp_decode_fetch", "drp_decode_fetch_block",
-    "drp_decode_fetch_block_ex", "drp_decode_fetch_keys",
-    "drp_encode_size", "drp_encode_device",
-    "drp_encode_batch", "drp_select_device", "drp_relay_staged", "drp_index_scan", "drp_stream_stats_from_results", "drp_device",
-    "drp_fanout_device", "drp_fanout_staged",
-    "drp_latest_device", "drp_latest_staged", "drp_set_latest_hash_mask",
-    "drp_fanout_latest_device", "drp_fanout_latest_staged", "drp_set_fanout_latest_pass",
-    "drp_store_table_bytes", "drp_store_init", "drp_store_merge_device", "drp_store_merge_staged",
-    "drp_store_compact", "drp_store_query", "drp_order_device", "drp_order_keys_device",
-    "drp_store_merge_report_device", "drp_store_merge_news_staged", "drp_fanout_news_staged",
-    "drp_store_lookup_device", "drp_store_lookup_staged",
-    "drp_store_load_device", "drp_store_rehash_device",
-    "drp_digest_device", "drp_digest_diff_device", "drp_select_buckets_device",
-    "drp_digest_refine_device", "drp_digest_diff_cells_device", "drp_select_refined_device",
-    "drp_comm_id", "drp_comm_init_rank", "drp_comm_init_all", "drp_comm_destroy",
-    "drp_index_allgather", "drp_index_allgather_multi", "drp_index_allgather_host", "drp_device_count",
-    "drp_host_alloc", "drp_host_free",
-]
 KEY_POST_OFF, KEY_POST_HASH, KEY_POST_FLAGS = 0, 1, 2
 BLOB_SKIP_OFF, BLOB_SKIP_AUTO, BLOB_SKIP_ALWAYS = 0, 1, 2
 DRP_E_COMM = -7
@@ -240,6 +217,99 @@ class Timing(C.Structure):
                 ("h2d_bytes", U64), ("h2d_skipped", U64), ("host_copied", U64)]
 
 
+COLS32 = ["key_off", "key_len", "subset_off", "subset_len", "value_off", "value_len"]
+COLS64 = ["change", "from", "to"]
+SRC_COLS = COLS32 + COLS64 + ["flags"]  # the fields of drp_change_src, in order
+
+# ---- the bound ABI: name -> (restype, argtypes), one entry per declaration of include/drp.h --------
+INT = C.c_int
+PP, PU64, PU32 = C.POINTER(P), C.POINTER(U64), C.POINTER(U32)
+PFrames, PChanges, PSrc, PFilter = C.POINTER(Frames), C.POINTER(Changes), C.POINTER(ChangeSrc), C.POINTER(Filter)
+PCarry, PStore, PInfo = C.POINTER(Carry), C.POINTER(StoreDesc), C.POINTER(StoreInfo)
+# the argument runs that recur
+_BATCH = [P, P, U64, PFrames, PChanges, U64, PFilter]  # ctx, bytes, nbytes, frames, cols, n, filter(s)
+_STORE = [P, PStore] + _BATCH[1:]                      # ctx, store, then that batch
+_STAGE_OUT = [PCarry, PU64, PU64, PU32, PU32]          # carry, n_frames, err_frame, err_code, err_detail
+_SELECT_OUT = [PSrc, P, P]                             # out_rows, sel_idx, n_selected
+_FANOUT_OUT = [U32, PSrc, U64, P, P]                   # nfilters, out_rows, rows_cap, sel_idx, row_base
+_RELAY_STAGED = [P, PFilter, P, U64, PU64, PU64]       # ctx, filter, out, cap, written, n_selected
+_FANOUT_STAGED = [P, PFilter, U32, P, U64, P, P]       # ctx, filters, nfilters, out, cap, out_off, n_selected
+_FANOUT_BLOBS = [P, P, U64, P]                         # blob_row, blob_pos, blob_cap, n_blobs
+_MERGE_STAGED = [P, PStore, PFilter, PInfo]            # ctx, store, filter, info_host
+_ORDER_OUT = [PSrc, P, P, P]                           # out_rows, sel_idx, out_sel_idx, out_base
+_GATHER_MULTI = [PP, PP, INT, PP, U64]                 # ctxs, comms, ngpu, local, per_gpu
+
+SIGNATURES = {
+    "drp_abi_version": (INT, []),
+    "drp_open": (INT, [INT, PP]),
+    "drp_close": (None, [P]),
+    "drp_stream": (P, [P]),
+    "drp_synchronize": (INT, [P]),
+    "drp_last_timing": (INT, [P, C.POINTER(Timing)]),
+    "drp_set_tile": (INT, [P, U32]),
+    "drp_set_strict": (INT, [P, INT]),
+    "drp_set_exact": (INT, [P, INT]),
+    "drp_set_key_post": (INT, [P, INT]),
+    "drp_set_blob_skip": (INT, [P, INT]),
+    "drp_decode_scratch_bytes": (U64, [P, U64, U64]),
+    "drp_decode_device": (INT, [P, P, U64, P, P, U64, PFrames, PChanges, U64, P]),
+    "drp_decode_batch": (INT, [P, P, U64, PCarry, PFrames, PChanges, U64] + _STAGE_OUT[1:]),
+    "drp_decode_stage": (INT, [P, P, U64] + _STAGE_OUT),
+    "drp_decode_stage_v": (INT, [P, C.POINTER(Chunk), U64] + _STAGE_OUT),
+    "drp_decode_fetch": (INT, [P, PFrames, PChanges, U64, U64]),
+    "drp_decode_fetch_block": (INT, [P, P, U64, PU64, U64, U64]),
+    "drp_decode_fetch_block_ex": (INT, [P, P, U64, PU64, U64, U64, U32]),
+    "drp_decode_fetch_keys": (INT, [P, U64, U64, P, P, U64, PU64]),
+    "drp_encode_size": (INT, [P, PSrc, U64, PU64]),
+    "drp_encode_device": (INT, [P, PSrc, P, U64, U64, P, P, U64]),
+    "drp_encode_batch": (INT, [P, PSrc, P, U64, U64, P, U64, PU64]),
+    "drp_select_device": (INT, _BATCH + _SELECT_OUT),
+    "drp_relay_staged": (INT, _RELAY_STAGED),
+    "drp_index_scan": (INT, [P, P, U64, P]),
+    "drp_stream_stats_from_results": (INT, [P, P, P, U64, P]),
+    "drp_device": (INT, [P]),
+    "drp_fanout_device": (INT, _BATCH + _FANOUT_OUT + [C.POINTER(Splice)]),
+    "drp_fanout_staged": (INT, _FANOUT_STAGED + _FANOUT_BLOBS),
+    "drp_latest_device": (INT, _BATCH + _SELECT_OUT),
+    "drp_latest_staged": (INT, _RELAY_STAGED),
+    "drp_set_latest_hash_mask": (INT, [P, U64]),
+    "drp_fanout_latest_device": (INT, _BATCH + _FANOUT_OUT),
+    "drp_fanout_latest_staged": (INT, _FANOUT_STAGED),
+    "drp_set_fanout_latest_pass": (INT, [P, U32]),
+    "drp_store_table_bytes": (U64, [U64]),
+    "drp_store_init": (INT, [P, PStore]),
+    "drp_store_merge_device": (INT, _STORE),
+    "drp_store_merge_staged": (INT, _MERGE_STAGED),
+    "drp_store_compact": (INT, [P, PStore, P, U64]),
+    "drp_store_query": (INT, [P, PStore, PInfo]),
+    "drp_order_device": (INT, [P, PSrc, P, U32, U64, P, U32] + _ORDER_OUT),
+    "drp_order_keys_device": (INT, [P, P, U64, PSrc, P, U32, U64, C.POINTER(KeyPage), U32] + _ORDER_OUT + [P]),
+    "drp_store_merge_report_device": (INT, _STORE + [C.POINTER(MergeReport)]),
+    "drp_store_merge_news_staged": (INT, _MERGE_STAGED),
+    "drp_fanout_news_staged": (INT, _FANOUT_STAGED + _FANOUT_BLOBS),
+    "drp_store_lookup_device": (INT, _STORE + [C.POINTER(Lookup)]),
+    "drp_store_lookup_staged": (INT, [P, PStore, PFilter, U32, P, U64, PU64, PU64, PU64]),
+    "drp_store_load_device": (INT, _STORE + [P]),
+    "drp_store_rehash_device": (INT, [P, PStore, P]),
+    "drp_digest_device": (INT, _BATCH + [U32, P, P]),
+    "drp_digest_diff_device": (INT, [P, P, P, U32, P, P]),
+    "drp_select_buckets_device": (INT, _BATCH + [U32, P] + _SELECT_OUT),
+    "drp_digest_refine_device": (INT, _BATCH + [U32, P, U32, P, U64, P]),
+    "drp_digest_diff_cells_device": (INT, [P, P, P, U64, P, P]),
+    "drp_select_refined_device": (INT, _BATCH + [U32, P, U32, P] + _SELECT_OUT),
+    "drp_comm_id": (INT, [P]),
+    "drp_comm_init_rank": (INT, [P, P, INT, INT, PP]),
+    "drp_comm_init_all": (INT, [PP, INT, PP]),
+    "drp_comm_destroy": (None, [P]),
+    "drp_index_allgather": (INT, [P, P, P, U64, P, P]),
+    "drp_index_allgather_multi": (INT, _GATHER_MULTI + [PP, PP]),
+    "drp_index_allgather_host": (INT, _GATHER_MULTI + [P, P]),
+    "drp_device_count": (INT, [C.POINTER(INT)]),
+    "drp_host_alloc": (INT, [U64, PP]),
+    "drp_host_free": (None, [P]),
+}
+EXPORTS = list(SIGNATURES)
+
 _lib = None
 
 
@@ -250,110 +320,9 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise OSError(f"libdrp not built: {LIB_PATH} missing (run __graft_entry__.build())")
         L = C.CDLL(LIB_PATH)
-        L.drp_abi_version.restype = C.c_int
-        L.drp_open.argtypes = [C.c_int, C.POINTER(P)]
-        L.drp_close.argtypes = [P]
-        L.drp_close.restype = None
-        L.drp_stream.argtypes = [P]
-        L.drp_stream.restype = P
-        L.drp_synchronize.argtypes = [P]
-        L.drp_last_timing.argtypes = [P, C.POINTER(Timing)]
-        L.drp_set_tile.argtypes = [P, U32]
-        L.drp_set_strict.argtypes = [P, C.c_int]
-        L.drp_set_exact.argtypes = [P, C.c_int]
-        L.drp_set_key_post.argtypes = [P, C.c_int]
-        L.drp_set_blob_skip.argtypes = [P, C.c_int]
-        L.drp_decode_scratch_bytes.argtypes = [P, U64, U64]
-        L.drp_decode_scratch_bytes.restype = U64
-        L.drp_decode_device.argtypes = [P, P, U64, P, P, U64, C.POINTER(Frames),
-                                        C.POINTER(Changes), U64, P]
-        L.drp_decode_batch.argtypes = [P, P, U64, C.POINTER(Carry), C.POINTER(Frames),
-                                       C.POINTER(Changes), U64, C.POINTER(U64), C.POINTER(U64),
-                                       C.POINTER(U32), C.POINTER(U32)]
-        L.drp_decode_stage.argtypes = [P, P, U64, C.POINTER(Carry), C.POINTER(U64), C.POINTER(U64),
-                                       C.POINTER(U32), C.POINTER(U32)]
-        L.drp_decode_stage_v.argtypes = [P, C.POINTER(Chunk), U64, C.POINTER(Carry), C.POINTER(U64), C.POINTER(U64),
-                                         C.POINTER(U32), C.POINTER(U32)]
-        L.drp_decode_fetch.argtypes = [P, C.POINTER(Frames), C.POINTER(Changes), U64, U64]
-        L.drp_decode_fetch_block.argtypes = [P, P, U64, C.POINTER(U64), U64, U64]
-        L.drp_decode_fetch_block_ex.argtypes = [P, P, U64, C.POINTER(U64), U64, U64, U32]
-        L.drp_decode_fetch_keys.argtypes = [P, U64, U64, P, P, U64, C.POINTER(U64)]
-        L.drp_encode_size.argtypes = [P, C.POINTER(ChangeSrc), U64, C.POINTER(U64)]
-        L.drp_encode_device.argtypes = [P, C.POINTER(ChangeSrc), P, U64, U64, P, P, U64]
-        L.drp_encode_batch.argtypes = [P, C.POINTER(ChangeSrc), P, U64, U64, P, U64,
-                                       C.POINTER(U64)]
-        L.drp_select_device.argtypes = [P, P, U64, C.POINTER(Frames), C.POINTER(Changes), U64, C.POINTER(Filter),
-                                        C.POINTER(ChangeSrc), P, P]
-        L.drp_relay_staged.argtypes = [P, C.POINTER(Filter), P, U64, C.POINTER(U64), C.POINTER(U64)]
-        L.drp_fanout_device.argtypes = [P, P, U64, C.POINTER(Frames), C.POINTER(Changes), U64, C.POINTER(Filter), U32,
-                                        C.POINTER(ChangeSrc), U64, P, P, C.POINTER(Splice)]
-        L.drp_fanout_staged.argtypes = [P, C.POINTER(Filter), U32, P, U64, P, P, P, P, U64, P]
-        L.drp_latest_device.argtypes = L.drp_select_device.argtypes
-        L.drp_latest_staged.argtypes = L.drp_relay_staged.argtypes
-        L.drp_set_latest_hash_mask.argtypes = [P, U64]
-        L.drp_fanout_latest_device.argtypes = L.drp_fanout_device.argtypes[:-1]
-        L.drp_fanout_latest_staged.argtypes = L.drp_fanout_staged.argtypes[:7]
-        L.drp_set_fanout_latest_pass.argtypes = [P, U32]
-        L.drp_store_table_bytes.argtypes = [U64]
-        L.drp_store_table_bytes.restype = U64
-        L.drp_store_init.argtypes = [P, C.POINTER(StoreDesc)]
-        L.drp_store_merge_device.argtypes = [P, C.POINTER(StoreDesc), P, U64, C.POINTER(Frames), C.POINTER(Changes),
-                                             U64, C.POINTER(Filter)]
-        L.drp_store_merge_staged.argtypes = [P, C.POINTER(StoreDesc), C.POINTER(Filter), C.POINTER(StoreInfo)]
-        L.drp_store_merge_report_device.argtypes = L.drp_store_merge_device.argtypes + [C.POINTER(MergeReport)]
-        L.drp_store_merge_news_staged.argtypes = L.drp_store_merge_staged.argtypes
-        L.drp_fanout_news_staged.argtypes = L.drp_fanout_staged.argtypes
-        L.drp_store_lookup_device.argtypes = L.drp_store_merge_device.argtypes + [C.POINTER(Lookup)]
-        L.drp_store_lookup_staged.argtypes = [P, C.POINTER(StoreDesc), C.POINTER(Filter), U32, P, U64, C.POINTER(U64),
-                                              C.POINTER(U64), C.POINTER(U64)]
-        L.drp_store_load_device.argtypes = L.drp_store_merge_device.argtypes + [P]
-        L.drp_store_rehash_device.argtypes = [P, C.POINTER(StoreDesc), P]
-        L.drp_store_compact.argtypes = [P, C.POINTER(StoreDesc), P, U64]
-        L.drp_store_query.argtypes = [P, C.POINTER(StoreDesc), C.POINTER(StoreInfo)]
-        L.drp_order_device.argtypes = [P, C.POINTER(ChangeSrc), P, U32, U64, P, U32, C.POINTER(ChangeSrc), P, P, P]
-        L.drp_order_keys_device.argtypes = [P, P, U64, C.POINTER(ChangeSrc), P, U32, U64, C.POINTER(KeyPage), U32,
-                                            C.POINTER(ChangeSrc), P, P, P, P]
-        L.drp_digest_device.argtypes = [P, P, U64, C.POINTER(Frames), C.POINTER(Changes), U64, C.POINTER(Filter), U32,
-                                        P, P]
-        L.drp_digest_diff_device.argtypes = [P, P, P, U32, P, P]
-        L.drp_select_buckets_device.argtypes = [P, P, U64, C.POINTER(Frames), C.POINTER(Changes), U64,
-                                                C.POINTER(Filter), U32, P, C.POINTER(ChangeSrc), P, P]
-        L.drp_digest_refine_device.argtypes = [P, P, U64, C.POINTER(Frames), C.POINTER(Changes), U64,
-                                               C.POINTER(Filter), U32, P, U32, P, U64, P]
-        L.drp_digest_diff_cells_device.argtypes = [P, P, P, U64, P, P]
-        L.drp_select_refined_device.argtypes = [P, P, U64, C.POINTER(Frames), C.POINTER(Changes), U64,
-                                                C.POINTER(Filter), U32, P, U32, P, C.POINTER(ChangeSrc), P, P]
-        L.drp_index_scan.argtypes = [P, P, U64, P]
-        L.drp_stream_stats_from_results.argtypes = [P, P, P, U64, P]
-        L.drp_device.argtypes = [P]
-        L.drp_comm_id.argtypes = [P]
-        L.drp_comm_init_rank.argtypes = [P, P, C.c_int, C.c_int, C.POINTER(P)]
-        L.drp_comm_init_all.argtypes = [C.POINTER(P), C.c_int, C.POINTER(P)]
-        L.drp_comm_destroy.argtypes = [P]
-        L.drp_comm_destroy.restype = None
-        L.drp_index_allgather.argtypes = [P, P, P, U64, P, P]
-        L.drp_index_allgather_multi.argtypes = [C.POINTER(P), C.POINTER(P), C.c_int, C.POINTER(P), U64,
-                                                C.POINTER(P), C.POINTER(P)]
-        L.drp_index_allgather_host.argtypes = [C.POINTER(P), C.POINTER(P), C.c_int, C.POINTER(P), U64, P, P]
-        L.drp_device_count.argtypes = [C.POINTER(C.c_int)]
-        for f in ["drp_open", "drp_synchronize", "drp_last_timing", "drp_set_tile",
-                  "drp_set_strict", "drp_set_exact", "drp_set_key_post", "drp_set_blob_skip", "drp_decode_device",
-                  "drp_decode_batch",
-                  "drp_decode_stage", "drp_decode_stage_v", "drp_decode_fetch", "drp_encode_size",
-                  "drp_encode_device", "drp_encode_batch", "drp_select_device", "drp_relay_staged", "drp_index_scan",
-                  "drp_fanout_device", "drp_fanout_staged", "drp_latest_device", "drp_latest_staged",
-                  "drp_set_latest_hash_mask", "drp_fanout_latest_device", "drp_fanout_latest_staged",
-                  "drp_set_fanout_latest_pass", "drp_store_init", "drp_store_merge_device", "drp_store_merge_staged",
-                  "drp_store_compact", "drp_store_query", "drp_order_device", "drp_order_keys_device",
-                  "drp_digest_device", "drp_digest_diff_device",
-                  "drp_store_merge_report_device", "drp_store_merge_news_staged", "drp_fanout_news_staged",
-                  "drp_store_lookup_device", "drp_store_lookup_staged",
-                  "drp_store_load_device", "drp_store_rehash_device",
-                  "drp_select_buckets_device", "drp_digest_refine_device", "drp_digest_diff_cells_device",
-                  "drp_select_refined_device", "drp_stream_stats_from_results", "drp_device", "drp_comm_id", "drp_comm_init_rank",
-                  "drp_comm_init_all", "drp_index_allgather", "drp_index_allgather_multi",
-                  "drp_index_allgather_host", "drp_device_count"]:
-            getattr(L, f).restype = C.c_int
+        for name, (restype, argtypes) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -364,17 +333,26 @@ class DrpError(RuntimeError):
         self.rc = rc
 
 
-def _chk(fn, rc):
+def _chk(fn, rc, **attrs):
+    """Raise DrpError(fn, rc) unless rc is DRP_OK; attrs become attributes of the error (.written,
+    .n_selected, .info: what a call that ran out of capacity still reports)."""
     if rc != DRP_OK:
-        raise DrpError(fn, rc)
+        e = DrpError(fn, rc)
+        e.__dict__.update(attrs)
+        raise e
 
 
+# ---- marshalling: numpy arrays, torch tensors and column dicts as the ABI's pointers and structs ----
 def _p(a):
     return C.c_void_p(a.ctypes.data) if a is not None else None
 
 
-COLS32 = ["key_off", "key_len", "subset_off", "subset_len", "value_off", "value_len"]
-COLS64 = ["change", "from", "to"]
+def _tp(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _ref(s):
+    return C.byref(s) if s is not None else None
 
 
 def alloc_host_outputs(cap, key_hash=False):
@@ -390,10 +368,24 @@ def alloc_host_outputs(cap, key_hash=False):
 
 
 def _structs(o, ptr):
-    fr = Frames(ptr(o["payload_off"]), ptr(o["payload_len"]), ptr(o["type"]))
-    co = Changes(*[ptr(o[k]) for k in COLS32], ptr(o["change"]), ptr(o["from"]), ptr(o["to"]),
-                 ptr(o["flags"]), ptr(o["key_hash"]) if o.get("key_hash") is not None else None)
+    """drp_frames and drp_changes over a dict of columns (numpy with _p, torch with _tp); payload_len
+    and key_hash may be missing."""
+    opt = lambda k: ptr(o[k]) if o.get(k) is not None else None
+    fr = Frames(ptr(o["payload_off"]), opt("payload_len"), ptr(o["type"]))
+    co = Changes(*[ptr(o[k]) for k in COLS32 + COLS64], ptr(o["flags"]), opt("key_hash"))
     return fr, co
+
+
+def _batch(wire_t, cols, n):
+    """The arguments bytes, nbytes, frames, cols, n of a *_device call over a decoded batch."""
+    fr, co = _structs(cols, _tp)
+    return _tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n
+
+
+def _src(rows, ptr=_tp):
+    """drp_change_src over a dict of row columns (None: None); a missing column is passed as NULL,
+    which the library answers with DRP_E_INVAL."""
+    return ChangeSrc(*[ptr(rows.get(k)) for k in SRC_COLS]) if rows is not None else None
 
 
 class Ctx:
@@ -564,42 +556,37 @@ class Ctx:
                  frame_bytes=int(carry.frame_bytes))
         return o
 
+    # ---- the asynchronous calls: device pointers, launched on this ctx's stream --------------------
+    def _call(self, fn, ref, *args):
+        """One asynchronous call of the C function `fn` (ctx first, then args): this ctx's stream is
+        ordered after torch's before it and torch's after this ctx's behind it, on the device of the
+        tensor `ref` (None: no ordering)."""
+        if ref is not None:
+            self.order_after_torch(ref)
+        _chk(fn, getattr(self.L, fn)(self.h, *args))
+        if ref is not None:
+            self.order_torch_after(ref)
+
     # ---- device decode over torch tensors (bench path) --------------------------------
     def decode_device(self, wire_t, stream_off_t, entry_t, outs, cap, results_t):
         """All arguments are torch CUDA tensors (uint8 wire, int64 offsets); outs is a dict
         of column tensors; results_t is a uint8 tensor of nstreams*sizeof(StreamResult)."""
-        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        fr, co = _structs(outs, tp)
-        ns = stream_off_t.numel() - 1
-        self.order_after_torch(wire_t)
-        rc = self.L.drp_decode_device(self.h, tp(wire_t), wire_t.numel(), tp(stream_off_t),
-                                      tp(entry_t), ns, C.byref(fr), C.byref(co), cap, tp(results_t))
-        _chk("drp_decode_device", rc)
-        self.order_torch_after(wire_t)
+        fr, co = _structs(outs, _tp)
+        self._call("drp_decode_device", wire_t, _tp(wire_t), wire_t.numel(), _tp(stream_off_t), _tp(entry_t),
+                   stream_off_t.numel() - 1, C.byref(fr), C.byref(co), cap, _tp(results_t))
 
     # ---- encode -----------------------------------------------------------------------
     def encode_device(self, cols_t, heap_t, n, frame_off_t, out_t, cap):
         """Device encode over torch CUDA tensors (asynchronous, on this ctx's stream): cols_t
         holds the drp_change_src columns (int64 offsets, int32 lengths, int64 numbers, uint8
         flags); frame_off_t (int64, n + 1) receives the frame offsets, out_t (uint8) the wire."""
-        tp = lambda t: C.c_void_p(t.data_ptr())
-        src = ChangeSrc(*[tp(cols_t[k]) for k in ["key_off", "key_len", "subset_off", "subset_len",
-                                                  "value_off", "value_len", "change", "from", "to",
-                                                  "flags"]])
-        self.order_after_torch(heap_t)
-        _chk("drp_encode_device", self.L.drp_encode_device(self.h, C.byref(src), tp(heap_t), heap_t.numel(),
-                                                           n, tp(frame_off_t), tp(out_t), cap))
-        self.order_torch_after(heap_t)
+        self._call("drp_encode_device", heap_t, C.byref(_src(cols_t)), _tp(heap_t), heap_t.numel(), n,
+                   _tp(frame_off_t), _tp(out_t), cap)
 
     def encode_batch(self, heap, cols):
         n = len(cols["key_len"])
         h = np.frombuffer(bytes(heap), np.uint8) if not isinstance(heap, np.ndarray) else heap
-        arrs = {k: np.ascontiguousarray(cols[k]) for k in
-                ["key_off", "key_len", "subset_off", "subset_len", "value_off", "value_len",
-                 "change", "from", "to", "flags"]}
-        src = ChangeSrc(*[_p(arrs[k]) for k in ["key_off", "key_len", "subset_off", "subset_len",
-                                                  "value_off", "value_len", "change", "from", "to",
-                                                  "flags"]])
+        src = _src({k: np.ascontiguousarray(cols[k]) for k in SRC_COLS}, _p)
         total = U64()
         _chk("drp_encode_size", self.L.drp_encode_size(self.h, C.byref(src), n, C.byref(total)))
         out = np.zeros(max(16, int(total.value)), np.uint8)
@@ -616,18 +603,8 @@ class Ctx:
         wrote them), out_rows the drp_change_src columns to fill (n entries each: int64 offsets
         and numbers, int32 lengths, uint8 flags), sel_idx_t (int64, n entries) may be None,
         n_selected_t is an int64 tensor of one element."""
-        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
-        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
-                     tp(cols["flags"]), None)
-        dst = ChangeSrc(*[tp(out_rows[k]) for k in ["key_off", "key_len", "subset_off", "subset_len",
-                                                      "value_off", "value_len", "change", "from", "to", "flags"]])
-        self.order_after_torch(wire_t)
-        rc = getattr(self.L, _fn)(self.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n,
-                                  C.byref(filter) if filter is not None else None, C.byref(dst),
-                                  tp(sel_idx_t), tp(n_selected_t))
-        _chk(_fn, rc)
-        self.order_torch_after(wire_t)
+        self._call(_fn, wire_t, *_batch(wire_t, cols, n), _ref(filter), _ref(_src(out_rows)), _tp(sel_idx_t),
+                   _tp(n_selected_t))
 
     def relay_staged(self, filter=None, cap=None, out=None, _fn="drp_relay_staged"):
         """drp_relay_staged over the batch last staged (decode_staged): returns (wire_bytes,
@@ -635,16 +612,12 @@ class Ctx:
         encoding of a Change is never longer than the one received), so one call does it. A given
         cap that is too small raises DrpError(DRP_E_CAPACITY) with .written = the size needed.
         out: a host uint8 array to write into (at least cap bytes)."""
-        fp = C.byref(filter) if filter is not None else None
         written, nsel = U64(), U64()
         if cap is None:
             cap = getattr(self, "_staged_len", 0)
         buf = out if out is not None else np.zeros(max(16, cap), np.uint8)
-        rc = getattr(self.L, _fn)(self.h, fp, _p(buf), cap, C.byref(written), C.byref(nsel))
-        if rc != DRP_OK:
-            e = DrpError(_fn, rc)
-            e.written = int(written.value)
-            raise e
+        rc = getattr(self.L, _fn)(self.h, _ref(filter), _p(buf), cap, C.byref(written), C.byref(nsel))
+        _chk(_fn, rc, written=int(written.value))
         return buf[:int(written.value)].tobytes(), int(nsel.value)
 
     # ---- latest per key (relay fan-in) ---------------------------------------------------
@@ -671,22 +644,12 @@ class Ctx:
         rows_cap entries), filters a list of make_filter results (None: keep every Change),
         row_base_t an int64 tensor of len(filters) + 1 entries. splice: None, or a dict of int64
         tensors blob_row (blob_cap entries), blob_rank (len(filters) * blob_cap) and n_blobs (1)."""
-        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
-        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
-                     tp(cols["flags"]), None)
-        dst = ChangeSrc(*[tp(out_rows[k]) for k in ["key_off", "key_len", "subset_off", "subset_len",
-                                                      "value_off", "value_len", "change", "from", "to", "flags"]])
         sp = None
         if splice is not None:
-            sp = C.byref(Splice(tp(splice["blob_row"]), tp(splice["blob_rank"]), tp(splice["n_blobs"]),
-                                splice["blob_row"].numel() if splice["blob_row"] is not None else 0))
-        self.order_after_torch(wire_t)
-        rc = self.L.drp_fanout_device(self.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n,
-                                      filter_array(filters), len(filters), C.byref(dst), rows_cap, tp(sel_idx_t),
-                                      tp(row_base_t), sp)
-        _chk("drp_fanout_device", rc)
-        self.order_torch_after(wire_t)
+            sp = Splice(_tp(splice["blob_row"]), _tp(splice["blob_rank"]), _tp(splice["n_blobs"]),
+                        splice["blob_row"].numel() if splice["blob_row"] is not None else 0)
+        self._call("drp_fanout_device", wire_t, *_batch(wire_t, cols, n), filter_array(filters), len(filters),
+                   _ref(_src(out_rows)), rows_cap, _tp(sel_idx_t), _tp(row_base_t), _ref(sp))
 
     def fanout_staged(self, filters, cap=None, splice=False, out=None, blob_cap=None, _fn="drp_fanout_staged"):
         """drp_fanout_staged over the batch last staged (decode_staged), filters a list of
@@ -711,13 +674,11 @@ class Ctx:
             brow = np.full(max(blob_cap, 1), 0x5555555555555555, np.uint64)
             bpos = np.full(max(K * blob_cap, 1), 0x5555555555555555, np.uint64)
             nbl = np.zeros(1, np.uint64)
-        rc = getattr(self.L, _fn)(self.h, filter_array(filters), K, _p(buf), cap, _p(out_off), _p(nsel),
-                                  _p(brow), _p(bpos), blob_cap or 0, _p(nbl))
-        if rc != DRP_OK:
-            e = DrpError(_fn, rc)
-            e.written = int(out_off[K]) if K <= FANOUT_MAX else 0
-            e.n_selected = [int(v) for v in nsel[:K]]
-            raise e
+        args = (self.h, filter_array(filters), K, _p(buf), cap, _p(out_off), _p(nsel),
+                _p(brow), _p(bpos), blob_cap or 0, _p(nbl))
+        fn = getattr(self.L, _fn)  # (drp_fanout_latest_staged takes no blob arguments)
+        _chk(_fn, fn(*args[:len(fn.argtypes)]), written=int(out_off[K]) if K <= FANOUT_MAX else 0,
+             n_selected=[int(v) for v in nsel[:K]])
         outs = [buf[int(out_off[f]):int(out_off[f + 1])].tobytes() for f in range(K)]
         sp = None
         if splice:
@@ -732,18 +693,8 @@ class Ctx:
     def fanout_latest_device(self, wire_t, cols, n, filters, out_rows, rows_cap, sel_idx_t, row_base_t):
         """drp_fanout_latest_device: fanout_device's arguments without the splice; output f holds
         what latest_device gives for filters[f]."""
-        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
-        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
-                     tp(cols["flags"]), None)
-        dst = ChangeSrc(*[tp(out_rows[k]) for k in ["key_off", "key_len", "subset_off", "subset_len",
-                                                      "value_off", "value_len", "change", "from", "to", "flags"]])
-        self.order_after_torch(wire_t)
-        rc = self.L.drp_fanout_latest_device(self.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n,
-                                             filter_array(filters), len(filters), C.byref(dst), rows_cap,
-                                             tp(sel_idx_t), tp(row_base_t))
-        _chk("drp_fanout_latest_device", rc)
-        self.order_torch_after(wire_t)
+        self._call("drp_fanout_latest_device", wire_t, *_batch(wire_t, cols, n), filter_array(filters), len(filters),
+                   _ref(_src(out_rows)), rows_cap, _tp(sel_idx_t), _tp(row_base_t))
 
     def fanout_latest_staged(self, filters, cap=None, out=None):
         """drp_fanout_latest_staged over the batch last staged (decode_staged), filters a list of
@@ -752,18 +703,7 @@ class Ctx:
         times the staged batch's length, which is always enough. A given cap that is too small
         raises DrpError(DRP_E_CAPACITY) with .written = the size needed and .n_selected.
         out: a host uint8 array to write into (at least cap bytes)."""
-        K = len(filters)
-        if cap is None:
-            cap = K * getattr(self, "_staged_len", 0)
-        buf = out if out is not None else np.zeros(max(16, cap), np.uint8)
-        out_off, nsel = np.zeros(K + 1, np.uint64), np.zeros(max(K, 1), np.uint64)
-        rc = self.L.drp_fanout_latest_staged(self.h, filter_array(filters), K, _p(buf), cap, _p(out_off), _p(nsel))
-        if rc != DRP_OK:
-            e = DrpError("drp_fanout_latest_staged", rc)
-            e.written = int(out_off[K]) if K <= FANOUT_MAX else 0
-            e.n_selected = [int(v) for v in nsel[:K]]
-            raise e
-        return [buf[int(out_off[f]):int(out_off[f + 1])].tobytes() for f in range(K)], [int(v) for v in nsel[:K]]
+        return self.fanout_staged(filters, cap, False, out, _fn="drp_fanout_latest_staged")[:2]
 
     def set_fanout_latest_pass(self, t):
         """Test hook: the filters one reduction pass of fanout_latest_device / fanout_latest_staged
@@ -773,35 +713,20 @@ class Ctx:
     # ---- store: the latest Change per key, resident on the device ---------------------------
     def store_init(self, store):
         """drp_store_init: an empty store (asynchronous)."""
-        self.order_after_torch(store.arena)
-        _chk("drp_store_init", self.L.drp_store_init(self.h, C.byref(store.desc())))
-        self.order_torch_after(store.arena)
+        self._call("drp_store_init", store.arena, C.byref(store.desc()))
 
     def store_merge_device(self, store, wire_t, cols, n, filter=None):
         """drp_store_merge_device: merge the decoded rows [0, n) of a batch (wire_t and cols as
         latest_device takes them) into the store. Asynchronous; a merge that does not fit is refused on
         the device (store_query(...).refused)."""
-        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
-        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
-                     tp(cols["flags"]), None)
-        self.order_after_torch(wire_t)
-        rc = self.L.drp_store_merge_device(self.h, C.byref(store.desc()), tp(wire_t), wire_t.numel(), C.byref(fr),
-                                           C.byref(co), n, C.byref(filter) if filter is not None else None)
-        _chk("drp_store_merge_device", rc)
-        self.order_torch_after(wire_t)
+        self._call("drp_store_merge_device", wire_t, C.byref(store.desc()), *_batch(wire_t, cols, n), _ref(filter))
 
     def store_merge_staged(self, store, filter=None, _fn="drp_store_merge_staged"):
         """drp_store_merge_staged over the batch last staged (decode_staged): returns the StoreInfo
         record; a refused merge raises DrpError(DRP_E_CAPACITY) with .info = the record."""
         info = StoreInfo()
         self.order_after_torch(store.arena)
-        rc = getattr(self.L, _fn)(self.h, C.byref(store.desc()), C.byref(filter) if filter is not None else None,
-                                  C.byref(info))
-        if rc != DRP_OK:
-            e = DrpError(_fn, rc)
-            e.info = info
-            raise e
+        _chk(_fn, getattr(self.L, _fn)(self.h, C.byref(store.desc()), _ref(filter), C.byref(info)), info=info)
         return info
 
     # ---- merge report: per-row outcomes, the news view and the stale reply -----------------------
@@ -812,22 +737,13 @@ class Ctx:
         outputs (all optional, uint8 / int64 CUDA tensors): outcome_t and news_type_t of n entries,
         reply_rows a dict of drp_change_src columns and reply_idx_t of reply_cap entries, n_reply_t of
         one. flags: REPORT_KEEP_BLOBS. report=False passes a NULL report. Asynchronous."""
-        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
-        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
-                     tp(cols["flags"]), None)
         rep = None
         if report:
-            dst = ChangeSrc(*[tp(reply_rows.get(k)) for k in SRC_COLS]) if reply_rows is not None else None
-            rep = MergeReport(flags, 0, tp(outcome_t), tp(news_type_t), C.pointer(dst) if dst is not None else None,
-                              tp(reply_idx_t), tp(n_reply_t), reply_cap, 0)
-        self.order_after_torch(wire_t)
-        rc = self.L.drp_store_merge_report_device(self.h, C.byref(store.desc()), tp(wire_t), wire_t.numel(),
-                                                  C.byref(fr), C.byref(co), n,
-                                                  C.byref(filter) if filter is not None else None,
-                                                  C.byref(rep) if rep is not None else None)
-        _chk("drp_store_merge_report_device", rc)
-        self.order_torch_after(wire_t)
+            dst = _src(reply_rows)
+            rep = MergeReport(flags, 0, _tp(outcome_t), _tp(news_type_t), C.pointer(dst) if dst is not None else None,
+                              _tp(reply_idx_t), _tp(n_reply_t), reply_cap, 0)
+        self._call("drp_store_merge_report_device", wire_t, C.byref(store.desc()), *_batch(wire_t, cols, n),
+                   _ref(filter), _ref(rep))
 
     def store_merge_news_staged(self, store, filter=None):
         """drp_store_merge_news_staged: store_merge_staged's arguments, result and errors; the ctx
@@ -850,21 +766,13 @@ class Ctx:
         drp_change_src columns and out_query_t (int64) of rows_cap entries, n_out_t (int64, 1).
         emit_mask: lookup_bit of LOOKUP_BEHIND / LEVEL / AHEAD. lookup=False passes a NULL drp_lookup.
         Asynchronous."""
-        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
-        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
-                     tp(cols["flags"]), None)
         lk = None
         if lookup:
-            dst = ChangeSrc(*[tp(out_rows.get(k)) for k in SRC_COLS]) if out_rows is not None else None
-            lk = Lookup(flags, emit_mask, tp(verdict_t), tp(hit_row_t), tp(counts_t), tp(lack_type_t),
-                        C.pointer(dst) if dst is not None else None, tp(out_query_t), tp(n_out_t), rows_cap, 0, 0)
-        self.order_after_torch(wire_t)
-        rc = self.L.drp_store_lookup_device(self.h, C.byref(store.desc()), tp(wire_t), wire_t.numel(), C.byref(fr),
-                                            C.byref(co), n, C.byref(filter) if filter is not None else None,
-                                            C.byref(lk) if lk is not None else None)
-        _chk("drp_store_lookup_device", rc)
-        self.order_torch_after(wire_t)
+            dst = _src(out_rows)
+            lk = Lookup(flags, emit_mask, _tp(verdict_t), _tp(hit_row_t), _tp(counts_t), _tp(lack_type_t),
+                        C.pointer(dst) if dst is not None else None, _tp(out_query_t), _tp(n_out_t), rows_cap, 0, 0)
+        self._call("drp_store_lookup_device", wire_t, C.byref(store.desc()), *_batch(wire_t, cols, n), _ref(filter),
+                   _ref(lk))
 
     def store_lookup_staged(self, store, filter=None, reply=LOOKUP_FOUND, cap=None, out=None):
         """drp_store_lookup_staged over the batch last staged (decode_staged): returns (wire bytes,
@@ -874,31 +782,25 @@ class Ctx:
         reply, then one with that capacity. A given cap that is too small raises
         DrpError(DRP_E_CAPACITY) with .written = the size needed. out: a host uint8 array to write
         into (at least cap bytes)."""
-        fp = C.byref(filter) if filter is not None else None
         written, nrows, counts = U64(), U64(), (U64 * 5)()
         self.order_after_torch(store.arena)
+        call = lambda b, c: self.L.drp_store_lookup_staged(self.h, C.byref(store.desc()), _ref(filter), reply, _p(b), c,
+                                                           C.byref(written), C.byref(nrows), counts)
         if cap is None:
-            rc = self.L.drp_store_lookup_staged(self.h, C.byref(store.desc()), fp, reply, None, 0, C.byref(written),
-                                                C.byref(nrows), counts)
-            if rc not in (DRP_OK, DRP_E_CAPACITY):
-                raise DrpError("drp_store_lookup_staged", rc)
+            rc = call(None, 0)  # (sizes the reply: DRP_E_CAPACITY unless it is empty)
+            if rc != DRP_E_CAPACITY:
+                _chk("drp_store_lookup_staged", rc)
             cap = int(written.value)
         buf = out if out is not None else np.zeros(max(16, cap), np.uint8)
-        rc = self.L.drp_store_lookup_staged(self.h, C.byref(store.desc()), fp, reply, _p(buf), cap, C.byref(written),
-                                            C.byref(nrows), counts)
-        if rc != DRP_OK:
-            e = DrpError("drp_store_lookup_staged", rc)
-            e.written = int(written.value)
-            raise e
+        _chk("drp_store_lookup_staged", call(buf, cap), written=int(written.value))
         return buf[:int(written.value)].tobytes(), int(nrows.value), [int(v) for v in counts]
 
-    def store_compact(self, store, arena2_t):
+    def store_compact(self, store, arena2_t, arena2_bytes=None):
         """drp_store_compact into arena2_t (a uint8 CUDA tensor). Asynchronous; the caller checks
-        store_query(...).refused and, if 0, sets store.arena = arena2_t."""
-        self.order_after_torch(arena2_t)
-        _chk("drp_store_compact", self.L.drp_store_compact(self.h, C.byref(store.desc()), C.c_void_p(arena2_t.data_ptr()),
-                                                           arena2_t.numel()))
-        self.order_torch_after(arena2_t)
+        store_query(...).refused and, if 0, sets store.arena = arena2_t. arena2_bytes: the size to
+        pass where it is not arena2_t's (0 for the one-byte stand-in of an empty arena)."""
+        self._call("drp_store_compact", arena2_t, C.byref(store.desc()), _tp(arena2_t),
+                   arena2_t.numel() if arena2_bytes is None else int(arena2_bytes))
 
     def store_query(self, store):
         """drp_store_query: waits for the ctx's stream and returns the StoreInfo record."""
@@ -913,26 +815,15 @@ class Ctx:
         are distinct and not in the store. clash_t (int64, 1, optional) receives the rows that broke
         the promise; a store with clash > 0 must be dropped. Asynchronous; refused on the device as a
         merge is (store_query(...).refused)."""
-        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
-        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
-                     tp(cols["flags"]), None)
-        self.order_after_torch(wire_t)
-        rc = self.L.drp_store_load_device(self.h, C.byref(store.desc()), tp(wire_t), wire_t.numel(), C.byref(fr),
-                                          C.byref(co), n, C.byref(filter) if filter is not None else None, tp(clash_t))
-        _chk("drp_store_load_device", rc)
-        self.order_torch_after(wire_t)
+        self._call("drp_store_load_device", wire_t, C.byref(store.desc()), *_batch(wire_t, cols, n), _ref(filter),
+                   _tp(clash_t))
 
     def store_rehash_device(self, store, report_t=None):
         """drp_store_rehash_device: the store's table rebuilt from its rows in use under the ctx's
         current hash mask. report_t (int64, 2, optional): the rows left out as invalid, and the rows
         that share their identity with an earlier one; store_query(...).refused is 1 if either is
         nonzero. Asynchronous."""
-        self.order_after_torch(store.arena)
-        rc = self.L.drp_store_rehash_device(self.h, C.byref(store.desc()),
-                                            C.c_void_p(report_t.data_ptr()) if report_t is not None else None)
-        _chk("drp_store_rehash_device", rc)
-        self.order_torch_after(store.arena)
+        self._call("drp_store_rehash_device", store.arena, C.byref(store.desc()), _tp(report_t))
 
     # ---- ordered catch-up: a fan-out's outputs in change order, with a per-peer limit -------------
     def order_device(self, rows, row_base_t, nseg, rows_cap, out_rows, out_base_t, limit=None, keep_ties=False,
@@ -945,21 +836,14 @@ class Ctx:
         an entry of None or 2**64 - 1: no limit); keep_ties: a cut inside a run of equal change moves
         to the run's end. out_sel_idx_t receives sel_idx_t in the same order (both int64, rows_cap
         entries). flags overrides the flag word (tests of the error returns)."""
-        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        mk = lambda r: C.byref(ChangeSrc(*[tp(r.get(k)) for k in SRC_COLS])) if r is not None else None
         lim = None
         if limit is not None:
             vals = [limit] * nseg if isinstance(limit, int) else list(limit)
             lim = (U64 * max(1, len(vals)))(*[0xFFFFFFFFFFFFFFFF if v is None else int(v) for v in vals])
         fl = (ORDER_KEEP_TIES if keep_ties else 0) if flags is None else flags
         ref = next((t for t in (row_base_t, out_base_t) if t is not None), None)
-        if ref is not None:
-            self.order_after_torch(ref)
-        rc = self.L.drp_order_device(self.h, mk(rows), tp(row_base_t), nseg, rows_cap, lim, fl, mk(out_rows),
-                                     tp(sel_idx_t), tp(out_sel_idx_t), tp(out_base_t))
-        _chk("drp_order_device", rc)
-        if ref is not None:
-            self.order_torch_after(ref)
+        self._call("drp_order_device", ref, _ref(_src(rows)), _tp(row_base_t), nseg, rows_cap, lim, fl,
+                   _ref(_src(out_rows)), _tp(sel_idx_t), _tp(out_sel_idx_t), _tp(out_base_t))
 
     # ---- key-ordered listing: a fan-out's outputs in key order, with a key range and a page --------
     def order_keys_device(self, heap_t, rows, row_base_t, nseg, rows_cap, out_rows, out_base_t, pages=None,
@@ -973,19 +857,12 @@ class Ctx:
         key moves to the run's end. totals_t (int64, 2, optional): the rows that took part, and the
         rows left out (a range outside the heap, or a key or subset above KEYORDER_MAX_BYTES). flags
         overrides the flag word (tests of the error returns)."""
-        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        mk = lambda r: C.byref(ChangeSrc(*[tp(r.get(k)) for k in SRC_COLS])) if r is not None else None
         pg = key_page_array(list(pages)) if pages is not None else None
         fl = (KEYORDER_KEEP_TIES if keep_ties else 0) if flags is None else flags
         ref = next((t for t in (row_base_t, out_base_t, heap_t) if t is not None), None)
-        if ref is not None:
-            self.order_after_torch(ref)
-        rc = self.L.drp_order_keys_device(self.h, tp(heap_t), heap_t.numel() if heap_t is not None else 0, mk(rows),
-                                          tp(row_base_t), nseg, rows_cap, pg, fl, mk(out_rows), tp(sel_idx_t),
-                                          tp(out_sel_idx_t), tp(out_base_t), tp(totals_t))
-        _chk("drp_order_keys_device", rc)
-        if ref is not None:
-            self.order_torch_after(ref)
+        self._call("drp_order_keys_device", ref, _tp(heap_t), heap_t.numel() if heap_t is not None else 0,
+                   _ref(_src(rows)), _tp(row_base_t), nseg, rows_cap, pg, fl, _ref(_src(out_rows)), _tp(sel_idx_t),
+                   _tp(out_sel_idx_t), _tp(out_base_t), _tp(totals_t))
 
     # ---- digest / reconcile: what differs between two stores ------------------------------------
     def digest_device(self, wire_t, cols, n, filter, bits, cells_t, totals_t=None):
@@ -993,41 +870,21 @@ class Ctx:
         cols as select_device takes them; cells_t an int64 tensor of 2**bits * 2 elements (count, sum
         per bucket), zeroed and filled; totals_t (int64, two elements, may be None): the rows
         digested, and the selected rows left out for a range outside the wire."""
-        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
-        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
-                     tp(cols["flags"]), None)
-        self.order_after_torch(wire_t)
-        rc = self.L.drp_digest_device(self.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n,
-                                      C.byref(filter) if filter is not None else None, bits, tp(cells_t), tp(totals_t))
-        _chk("drp_digest_device", rc)
-        self.order_torch_after(wire_t)
+        self._call("drp_digest_device", wire_t, *_batch(wire_t, cols, n), _ref(filter), bits, _tp(cells_t),
+                   _tp(totals_t))
 
     def digest_diff_device(self, a_t, b_t, bits, bucket_set_t, n_diff_t):
         """drp_digest_diff_device: a_t, b_t two digests of 2**bits cells; bucket_set_t (int64,
         max(1, 2**bits // 64) words) gets bit b set iff cell b differs, n_diff_t (int64, one element)
         the number of such buckets. Asynchronous."""
-        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self.order_after_torch(a_t)
-        _chk("drp_digest_diff_device", self.L.drp_digest_diff_device(self.h, tp(a_t), tp(b_t), bits, tp(bucket_set_t),
-                                                                     tp(n_diff_t)))
-        self.order_torch_after(a_t)
+        self._call("drp_digest_diff_device", a_t, _tp(a_t), _tp(b_t), bits, _tp(bucket_set_t), _tp(n_diff_t))
 
     def select_buckets_device(self, wire_t, cols, n, filter, bits, bucket_set_t, out_rows, sel_idx_t, n_selected_t):
         """drp_select_buckets_device: select_device's arguments and outputs, for the rows
         digest_device counted (same filter, same bits) in the buckets whose bit is set in
         bucket_set_t."""
-        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
-        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
-                     tp(cols["flags"]), None)
-        dst = ChangeSrc(*[tp(out_rows[k]) for k in SRC_COLS])
-        self.order_after_torch(wire_t)
-        rc = self.L.drp_select_buckets_device(self.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n,
-                                              C.byref(filter) if filter is not None else None, bits, tp(bucket_set_t),
-                                              C.byref(dst), tp(sel_idx_t), tp(n_selected_t))
-        _chk("drp_select_buckets_device", rc)
-        self.order_torch_after(wire_t)
+        self._call("drp_select_buckets_device", wire_t, *_batch(wire_t, cols, n), _ref(filter), bits,
+                   _tp(bucket_set_t), _ref(_src(out_rows)), _tp(sel_idx_t), _tp(n_selected_t))
 
     # ---- refined digests: a second level inside the differing buckets ----------------------------
     def digest_refine_device(self, wire_t, cols, n, filter, bits, bucket_set_t, sub_bits, cells2_t, cells_cap, totals_t):
@@ -1036,46 +893,32 @@ class Ctx:
         elements) at cell slot(bucket) << sub_bits | sub. totals_t (int64, three elements, required):
         the rows digested, the selected rows left out for a range outside the wire, n_set. The cells
         are written only if n_set << sub_bits <= cells_cap; totals_t is complete either way."""
-        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
-        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
-                     tp(cols["flags"]), None)
-        self.order_after_torch(wire_t)
-        rc = self.L.drp_digest_refine_device(self.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n,
-                                             C.byref(filter) if filter is not None else None, bits, tp(bucket_set_t),
-                                             sub_bits, tp(cells2_t), cells_cap, tp(totals_t))
-        _chk("drp_digest_refine_device", rc)
-        self.order_torch_after(wire_t)
+        self._call("drp_digest_refine_device", wire_t, *_batch(wire_t, cols, n), _ref(filter), bits,
+                   _tp(bucket_set_t), sub_bits, _tp(cells2_t), cells_cap, _tp(totals_t))
 
     def digest_diff_cells_device(self, a_t, b_t, ncells, cell_set_t, n_diff_t):
         """drp_digest_diff_cells_device: digest_diff_device for any cell count; cell_set_t (int64,
         max(1, ceil(ncells / 64)) words), n_diff_t (int64, one element). Asynchronous."""
-        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        self.order_after_torch(a_t)
-        _chk("drp_digest_diff_cells_device", self.L.drp_digest_diff_cells_device(self.h, tp(a_t), tp(b_t), ncells,
-                                                                                 tp(cell_set_t), tp(n_diff_t)))
-        self.order_torch_after(a_t)
+        self._call("drp_digest_diff_cells_device", a_t, _tp(a_t), _tp(b_t), ncells, _tp(cell_set_t), _tp(n_diff_t))
 
     def select_refined_device(self, wire_t, cols, n, filter, bits, bucket_set_t, sub_bits, cell_set_t, out_rows,
                               sel_idx_t, n_selected_t):
         """drp_select_refined_device: select_buckets_device's arguments and outputs, for the rows
         digest_refine_device counted (same filter, bits, bucket set and sub_bits) in the cells whose
         bit is set in cell_set_t."""
-        tp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        fr = Frames(tp(cols["payload_off"]), tp(cols.get("payload_len")), tp(cols["type"]))
-        co = Changes(*[tp(cols[k]) for k in COLS32], tp(cols["change"]), tp(cols["from"]), tp(cols["to"]),
-                     tp(cols["flags"]), None)
-        dst = ChangeSrc(*[tp(out_rows[k]) for k in SRC_COLS]) if out_rows is not None else None
-        self.order_after_torch(wire_t)
-        rc = self.L.drp_select_refined_device(self.h, tp(wire_t), wire_t.numel(), C.byref(fr), C.byref(co), n,
-                                              C.byref(filter) if filter is not None else None, bits, tp(bucket_set_t),
-                                              sub_bits, tp(cell_set_t), C.byref(dst) if dst is not None else None,
-                                              tp(sel_idx_t), tp(n_selected_t))
-        _chk("drp_select_refined_device", rc)
-        self.order_torch_after(wire_t)
+        self._call("drp_select_refined_device", wire_t, *_batch(wire_t, cols, n), _ref(filter), bits,
+                   _tp(bucket_set_t), sub_bits, _tp(cell_set_t), _ref(_src(out_rows)), _tp(sel_idx_t),
+                   _tp(n_selected_t))
 
 
-SRC_COLS = ["key_off", "key_len", "subset_off", "subset_len", "value_off", "value_len", "change", "from", "to", "flags"]
+_SIGNED = {8: np.int64, 4: np.int32, 1: np.uint8}  # (torch's dtypes for the 64-, 32- and 8-bit columns)
+
+
+def _upload(a, dev):
+    """A numpy array as a tensor on dev, its unsigned 64- and 32-bit entries as the signed dtype torch has."""
+    import torch
+    a = np.ascontiguousarray(a)
+    return torch.from_numpy(a.view(_SIGNED[a.dtype.itemsize])).to(dev)
 
 
 class Store:
@@ -1102,9 +945,21 @@ class Store:
         ctx.store_init(self)
 
     def desc(self):
-        tp = lambda t: C.c_void_p(t.data_ptr())
-        fr, co = _structs(self.cols, tp)
-        return StoreDesc(tp(self.arena), self.arena_bytes, fr, co, self.max_keys, tp(self.table), tp(self.info))
+        fr, co = _structs(self.cols, _tp)
+        return StoreDesc(_tp(self.arena), self.arena_bytes, fr, co, self.max_keys, _tp(self.table), _tp(self.info))
+
+    def _view(self):
+        return self.arena[:self.arena_bytes] if self.arena_bytes else self.arena[:0]
+
+    def _zeros(self, n, dtype):
+        import torch
+        return torch.zeros(max(int(n), 1), dtype=dtype, device=self.arena.device)
+
+    def _out_rows(self, cap):
+        """A set of output rows: the ten drp_change_src columns, cap entries each, on the store's device."""
+        import torch
+        return {k: self._zeros(cap, torch.int32 if k.endswith("_len") else torch.uint8 if k == "flags" else torch.int64)
+                for k in SRC_COLS}
 
     def merge_device(self, wire_t, cols, n, filter=None):
         self.ctx.store_merge_device(self, wire_t, cols, n, filter)
@@ -1122,14 +977,11 @@ class Store:
         batch's stale winners as drp_change_src columns over the arena, their store rows, and the
         count as an int64 tensor of one element (reply_cap = n). Asynchronous."""
         import torch
-        dev = self.arena.device
-        z = lambda k, dt: torch.zeros(max(int(k), 1), dtype=dt, device=dev)
+        z = self._zeros
         r = {"outcome": z(n, torch.uint8), "news_type": z(n, torch.uint8), "reply_rows": None, "reply_idx": None,
              "n_reply": None}
         if reply:
-            r["reply_rows"] = {k: z(n, torch.int32 if k.endswith("_len") else torch.uint8 if k == "flags" else
-                                    torch.int64) for k in SRC_COLS}
-            r["reply_idx"], r["n_reply"] = z(n, torch.int64), z(1, torch.int64)
+            r["reply_rows"], r["reply_idx"], r["n_reply"] = self._out_rows(n), z(n, torch.int64), z(1, torch.int64)
         self.ctx.store_merge_report_device(self, wire_t, cols, n, filter, r["outcome"], r["news_type"],
                                            r["reply_rows"], r["reply_idx"], r["n_reply"], n if reply else 0,
                                            REPORT_KEEP_BLOBS if keep_blobs else 0)
@@ -1137,21 +989,27 @@ class Store:
         return r
 
     def _encode_outputs(self, rows, base, heap_t, K):
-        """One encode_device of fan-out rows (bounds base, K outputs) over heap_t: [bytes per output]."""
+        """One encode_device of fan-out rows (bounds base: a tensor, or its entries as a list; K
+        outputs) over heap_t: [bytes per output]."""
         import torch
-        rb = [int(v) for v in base.cpu()]  # (torch's stream was ordered after the ctx's)
+        rb = base if isinstance(base, list) else [int(v) for v in base.cpu()]  # (torch's stream was ordered after the ctx's)
         total = rb[K]
         if total == 0:
             return [b""] * K
-        src = ChangeSrc(*[C.c_void_p(rows[k].data_ptr()) for k in SRC_COLS])
         need = U64()
-        _chk("drp_encode_size", self.ctx.L.drp_encode_size(self.ctx.h, C.byref(src), total, C.byref(need)))
-        dev = self.arena.device
-        foff = torch.zeros(total + 1, dtype=torch.int64, device=dev)
-        out = torch.zeros(max(int(need.value), 1), dtype=torch.uint8, device=dev)
+        _chk("drp_encode_size", self.ctx.L.drp_encode_size(self.ctx.h, C.byref(_src(rows)), total, C.byref(need)))
+        foff = self._zeros(total + 1, torch.int64)
+        out = self._zeros(need.value, torch.uint8)
         self.ctx.encode_device(rows, heap_t, total, foff, out, int(need.value))
         fo, o = foff.cpu().numpy(), out.cpu().numpy()
         return [o[int(fo[rb[f]]):int(fo[rb[f + 1]])].tobytes() for f in range(K)]
+
+    def _encode_rows(self, rows, n_t):
+        """One encode_device of rows [0, n_t[0]) (n_t: an int64 tensor on the device) with the arena as
+        the heap: their bytes."""
+        import torch
+        base = torch.cat([self._zeros(1, torch.int64), n_t[:1]])
+        return self._encode_outputs(rows, base, self._view(), 1)[0]
 
     def relay_news(self, wire_t, cols, n, filters, merge_filter=None):
         """The hub step: one merge with a report, one fanout_device over the batch with the report's
@@ -1159,18 +1017,12 @@ class Store:
         [wire bytes per filter]): output f holds the batch's Changes that changed the store and pass
         filters[f], in batch-row order."""
         import torch
-        dev = self.arena.device
-        news = torch.zeros(max(int(n), 1), dtype=torch.uint8, device=dev)
+        news = self._zeros(n, torch.uint8)
         self.ctx.store_merge_report_device(self, wire_t, cols, n, merge_filter, None, news, flags=REPORT_KEEP_BLOBS)
         K = len(filters)
         cap = K * int(n)
-        rows = {k: torch.zeros(max(cap, 1), dtype=(torch.int32 if k.endswith("_len") else
-                                                   torch.uint8 if k == "flags" else torch.int64), device=dev)
-                for k in SRC_COLS}
-        base = torch.zeros(K + 1, dtype=torch.int64, device=dev)
-        view = dict(cols)
-        view["type"] = news
-        self.ctx.fanout_device(wire_t, view, n, filters, rows, cap, None, base)
+        rows, base = self._out_rows(cap), self._zeros(K + 1, torch.int64)
+        self.ctx.fanout_device(wire_t, dict(cols, type=news), n, filters, rows, cap, None, base)
         outs = self._encode_outputs(rows, base, wire_t, K)
         return self.query(), outs
 
@@ -1179,9 +1031,7 @@ class Store:
         encode_device of the reply rows with the arena as the heap."""
         if report.get("n_reply") is None:
             raise ValueError("the report holds no reply (merge_report(..., reply=True))")
-        import torch
-        base = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.arena.device), report["n_reply"][:1]])
-        return self._encode_outputs(report["reply_rows"], base, self._view(), 1)[0]
+        return self._encode_rows(report["reply_rows"], report["n_reply"])
 
     def compact(self, arena2_bytes=None):
         """Compact into a fresh arena of arena2_bytes (default: the live bytes); returns the record.
@@ -1190,12 +1040,9 @@ class Store:
         if arena2_bytes is None:
             i = self.query()
             arena2_bytes = i.arena_used - i.arena_dead
-        a2 = torch.zeros(max(int(arena2_bytes), 1), dtype=torch.uint8, device=self.arena.device)
+        a2 = self._zeros(arena2_bytes, torch.uint8)
         # (arena2's true size is passed: the 1-byte stand-in for an empty arena holds nothing)
-        self.ctx.order_after_torch(a2)
-        _chk("drp_store_compact", self.ctx.L.drp_store_compact(self.ctx.h, C.byref(self.desc()),
-                                                               C.c_void_p(a2.data_ptr()), int(arena2_bytes)))
-        self.ctx.order_torch_after(a2)
+        self.ctx.store_compact(self, a2, int(arena2_bytes))
         i = self.query()
         if not i.refused:
             self.arena, self.arena_bytes = a2, int(arena2_bytes)
@@ -1206,6 +1053,15 @@ class Store:
         """This store becomes `other` (its tensors and sizes)."""
         for k in ["max_keys", "arena", "arena_bytes", "cols", "table", "info"]:
             setattr(self, k, getattr(other, k))
+
+    def _rehash_checked(self):
+        """One rehash with a report: DrpError if it names an invalid or a duplicate row."""
+        import torch
+        report = self._zeros(2, torch.int64)
+        self.ctx.store_rehash_device(self, report)
+        bad = [int(v) for v in report.cpu()]
+        if any(bad):
+            raise DrpError(f"drp_store_rehash_device (report {bad})", DRP_E_INVAL)
 
     def grow(self, max_keys=None, arena_bytes=None):
         """Resize the store in place: new column tensors and a new table for max_keys (the rows in use
@@ -1232,12 +1088,11 @@ class Store:
                 new.cols[k][:i.rows] = v[:i.rows]
             new.table = torch.zeros(lib().drp_store_table_bytes(mk) // 8, dtype=torch.int64, device=dev)
             new.max_keys = mk
-            report = torch.zeros(2, dtype=torch.int64, device=dev)
-            self.ctx.store_rehash_device(new, report)
-            bad = [int(v) for v in report.cpu()]
-            if any(bad):
+            try:
+                new._rehash_checked()
+            except DrpError:
                 self.ctx.store_rehash_device(self)  # (the shared record's last-merge group, and this table)
-                raise DrpError(f"drp_store_rehash_device (report {bad})", DRP_E_INVAL)
+                raise
         self._take(new)
         return self.query()
 
@@ -1250,13 +1105,10 @@ class Store:
         load was refused or clashed. The kept rows are renumbered in their old order, the arena is
         compacted and arena_dead is 0."""
         import torch
-        dev = self.arena.device
         new = Store(self.ctx, self.max_keys if max_keys is None else max_keys,
-                    self.arena_bytes if arena_bytes is None else arena_bytes, device=dev)
-        view = dict(self.cols)
-        if type_t is not None:
-            view["type"] = type_t
-        clash = torch.zeros(1, dtype=torch.int64, device=dev)
+                    self.arena_bytes if arena_bytes is None else arena_bytes, device=self.arena.device)
+        view = self.cols if type_t is None else dict(self.cols, type=type_t)
+        clash = self._zeros(1, torch.int64)
         self.ctx.store_load_device(new, self._view(), view, self.max_keys, filter, clash)
         i = new.query()
         i.clash = int(clash.cpu()[0])
@@ -1280,7 +1132,6 @@ class Store:
         the columns, the arena and the record, and rehash with a report. ValueError for a state that
         does not fit the sizes or its own counts; DrpError if the rehash reports an invalid or
         duplicate row."""
-        import torch
         rows, used = int(state["rows"]), int(state["arena_used"])
         mk = max(rows, 1) if max_keys is None else int(max_keys)
         ab = used if arena_bytes is None else int(arena_bytes)
@@ -1290,19 +1141,13 @@ class Store:
         if set(state["cols"]) != set(s.cols) or any(len(v) != rows for v in state["cols"].values()):
             raise ValueError("the state's columns are not a store's, or not `rows` long")
         dev = s.arena.device
-        signed = {8: np.int64, 4: np.int32, 1: np.uint8}  # (torch's dtypes for the 64-, 32- and 8-bit columns)
         for k, v in state["cols"].items():
-            v = np.ascontiguousarray(v)
-            s.cols[k][:rows] = torch.from_numpy(v.view(signed[v.dtype.itemsize])).to(dev)
-        s.arena[:used] = torch.from_numpy(np.ascontiguousarray(state["arena"], np.uint8)).to(dev)
+            s.cols[k][:rows] = _upload(v, dev)
+        s.arena[:used] = _upload(np.asarray(state["arena"], np.uint8), dev)
         rec = np.zeros(C.sizeof(StoreInfo) // 8, np.int64)
         rec[:4] = [rows, used, int(state["arena_dead"]), int(state["merges"])]
-        s.info.copy_(torch.from_numpy(rec).to(dev))
-        report = torch.zeros(2, dtype=torch.int64, device=dev)
-        ctx.store_rehash_device(s, report)
-        bad = [int(v) for v in report.cpu()]
-        if any(bad):
-            raise DrpError(f"drp_store_rehash_device (report {bad})", DRP_E_INVAL)
+        s.info.copy_(_upload(rec, dev))
+        s._rehash_checked()
         return s
 
     def lookup(self, wire_t, cols, n, filter=None, emit=(LOOKUP_BEHIND, LOOKUP_LEVEL, LOOKUP_AHEAD), lack=False):
@@ -1315,8 +1160,7 @@ class Store:
         max_keys entries under which the store's view holds the rows the batch's sender lacks.
         Nothing of the store is written. Asynchronous."""
         import torch
-        dev = self.arena.device
-        z = lambda k, dt: torch.zeros(max(int(k), 1), dtype=dt, device=dev)
+        z = self._zeros
         r = {"verdict": z(n, torch.uint8), "hit_row": z(n, torch.int64), "counts": z(5, torch.int64),
              "lack_type": z(self.max_keys, torch.uint8) if lack else None, "out_rows": None, "out_query": None,
              "n_out": None}
@@ -1324,9 +1168,7 @@ class Store:
         for code in emit or ():
             mask |= lookup_bit(code)
         if mask:
-            r["out_rows"] = {k: z(n, torch.int32 if k.endswith("_len") else torch.uint8 if k == "flags" else
-                                  torch.int64) for k in SRC_COLS}
-            r["out_query"], r["n_out"] = z(n, torch.int64), z(1, torch.int64)
+            r["out_rows"], r["out_query"], r["n_out"] = self._out_rows(n), z(n, torch.int64), z(1, torch.int64)
         self.ctx.store_lookup_device(self, wire_t, cols, n, filter, mask, r["verdict"], r["hit_row"], r["counts"],
                                      r["lack_type"], r["out_rows"], r["out_query"], r["n_out"], n if mask else 0)
         r["verdict"], r["hit_row"] = r["verdict"][:n], r["hit_row"][:n]
@@ -1341,7 +1183,6 @@ class Store:
         one lookup that emits every found row and one encode_device with the arena as the heap.
         Returns (hit_row, wire bytes): an int64 numpy array, the store row of each key or -1 where the
         store does not hold it, and the found rows in query order as change frames."""
-        import torch
         n = len(keys)
         dev = self.arena.device
         q = alloc_host_outputs(max(n, 1))
@@ -1356,13 +1197,10 @@ class Store:
                 heap += sub
             q["payload_len"][i] = len(heap) - int(q["payload_off"][i])
             q["value_off"][i] = q["payload_len"][i]
-        signed = {np.dtype(np.uint64): np.int64, np.dtype(np.uint32): np.int32, np.dtype(np.uint8): np.uint8}
-        cols = {k: torch.from_numpy(v.view(signed[v.dtype])).to(dev) for k, v in q.items()}
-        heap_t = torch.from_numpy(np.frombuffer(bytes(heap) or b"\0", np.uint8).copy()).to(dev)[:len(heap)]
+        cols = {k: _upload(v, dev) for k, v in q.items()}
+        heap_t = _upload(np.frombuffer(bytes(heap) or b"\0", np.uint8).copy(), dev)[:len(heap)]
         r = self.lookup(heap_t, cols, n)
-        base = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), r["n_out"][:1]])
-        wire = self._encode_outputs(r["out_rows"], base, self._view(), 1)[0]
-        return r["hit_row"].cpu().numpy().copy(), wire
+        return r["hit_row"].cpu().numpy().copy(), self._encode_rows(r["out_rows"], r["n_out"])
 
     def sync_reply(self, wire_t, cols, n, filter=None):
         """The answer to a have-list (wire_t, cols, n: a batch of Changes whose values do not matter,
@@ -1383,35 +1221,34 @@ class Store:
         n = self.max_keys if n is None else int(n)
         K = len(filters)
         cap = K * n if rows_cap is None else int(rows_cap)
-        dev = self.arena.device
-        rows = {k: torch.zeros(max(cap, 1), dtype=(torch.int32 if k.endswith("_len") else
-                                                   torch.uint8 if k == "flags" else torch.int64), device=dev)
-                for k in SRC_COLS}
-        base = torch.zeros(K + 1, dtype=torch.int64, device=dev)
+        rows, base = self._out_rows(cap), self._zeros(K + 1, torch.int64)
         view = self.cols if type_t is None else dict(self.cols, type=type_t)
-        self.ctx.fanout_device(self.arena[:self.arena_bytes] if self.arena_bytes else self.arena[:0], view, n,
-                               filters, rows, cap, None, base)
+        self.ctx.fanout_device(self._view(), view, n, filters, rows, cap, None, base)
         return rows, base
 
     def fanout(self, filters, n=None):
         """The catch-up call: one fanout_device over the store and one encode_device with the arena
         as the heap. filters: make_filter results (peer f at version T: change_range=(T + 1,
         2**64 - 1), with its subset / key prefix). Returns [wire bytes per filter], in store order."""
-        import torch
         rows, base = self.fanout_rows(filters, n)
-        rb = [int(v) for v in base.cpu()]  # (torch's stream was ordered after the ctx's)
-        total = rb[-1]
+        return self._encode_outputs(rows, base, self._view(), len(filters))
+
+    def _ordered(self, filters, n, order):
+        """fanout_rows, then order(rows, base, K, total, out_rows, out_base) (one of the ctx's two
+        orders), then one encode_device with the arena as the heap: (out_rows, the bounds of the
+        outputs as a list, [bytes per output]), or None when nothing is to be sent."""
+        import torch
+        K = len(filters)
+        rows, base = self.fanout_rows(filters, n)
+        total = int(base.cpu()[K])  # (torch's stream was ordered after the ctx's)
         if total == 0:
-            return [b""] * len(filters)
-        src = ChangeSrc(*[C.c_void_p(rows[k].data_ptr()) for k in SRC_COLS])
-        need = U64()
-        _chk("drp_encode_size", self.ctx.L.drp_encode_size(self.ctx.h, C.byref(src), total, C.byref(need)))
-        dev = self.arena.device
-        foff = torch.zeros(total + 1, dtype=torch.int64, device=dev)
-        out = torch.zeros(max(int(need.value), 1), dtype=torch.uint8, device=dev)
-        self.ctx.encode_device(rows, self.arena[:self.arena_bytes], total, foff, out, int(need.value))
-        fo, o = foff.cpu().numpy(), out.cpu().numpy()
-        return [o[int(fo[rb[f]]):int(fo[rb[f + 1]])].tobytes() for f in range(len(filters))]
+            return None
+        out_rows, out_base = self._out_rows(total), self._zeros(K + 1, torch.int64)
+        order(rows, base, K, total, out_rows, out_base)
+        ob = [int(v) for v in out_base.cpu()]
+        if ob[K] == 0:
+            return None
+        return out_rows, ob, self._encode_outputs(out_rows, ob, self._view(), K)
 
     def catch_up(self, filters, limit=None, keep_ties=True, n=None):
         """The ordered catch-up: fanout_rows over the store, one order_device and one encode_device
@@ -1423,30 +1260,14 @@ class Store:
         T is last_change, repeat until a page is empty."""
         import torch
         K = len(filters)
-        rows, base = self.fanout_rows(filters, n)
-        total = int(base.cpu()[K])  # (torch's stream was ordered after the ctx's)
-        if total == 0:
+        got = self._ordered(filters, n, lambda *a: self.ctx.order_device(*a, limit=limit, keep_ties=keep_ties))
+        if got is None:
             return [(b"", 0, None)] * K
-        dev = self.arena.device
-        out_rows = {k: torch.zeros(total, dtype=v.dtype, device=dev) for k, v in rows.items()}
-        out_base = torch.zeros(K + 1, dtype=torch.int64, device=dev)
-        self.ctx.order_device(rows, base, K, total, out_rows, out_base, limit=limit, keep_ties=keep_ties)
-        ob = [int(v) for v in out_base.cpu()]
-        sent = ob[K]
-        if sent == 0:
-            return [(b"", 0, None)] * K
-        src = ChangeSrc(*[C.c_void_p(out_rows[k].data_ptr()) for k in SRC_COLS])
-        need = U64()
-        _chk("drp_encode_size", self.ctx.L.drp_encode_size(self.ctx.h, C.byref(src), sent, C.byref(need)))
-        foff = torch.zeros(sent + 1, dtype=torch.int64, device=dev)
-        out = torch.zeros(max(int(need.value), 1), dtype=torch.uint8, device=dev)
-        self.ctx.encode_device(out_rows, self._view(), sent, foff, out, int(need.value))
-        fo, o = foff.cpu().numpy(), out.cpu().numpy()
+        out_rows, ob, outs = got
         ends = [ob[f + 1] - 1 for f in range(K) if ob[f + 1] > ob[f]]
-        last = out_rows["change"][torch.tensor(ends, dtype=torch.int64, device=dev)].cpu().numpy().view(np.uint64)
-        last = dict(zip(ends, (int(v) for v in last)))
-        return [(o[int(fo[ob[f]]):int(fo[ob[f + 1]])].tobytes(), ob[f + 1] - ob[f], last.get(ob[f + 1] - 1)
-                 if ob[f + 1] > ob[f] else None) for f in range(K)]
+        last = out_rows["change"][torch.tensor(ends, dtype=torch.int64, device=self.arena.device)]
+        last = dict(zip(ends, (int(v) for v in last.cpu().numpy().view(np.uint64))))
+        return [(outs[f], ob[f + 1] - ob[f], last.get(ob[f + 1] - 1) if ob[f + 1] > ob[f] else None) for f in range(K)]
 
     def list_keys(self, filters, pages=None, keep_ties=True, n=None):
         """The key-ordered listing: fanout_rows over the store, one order_keys_device and one
@@ -1469,38 +1290,23 @@ class Store:
                 after = last_key"""
         import torch
         K = len(filters)
-        rows, base = self.fanout_rows(filters, n)
-        total = int(base.cpu()[K])  # (torch's stream was ordered after the ctx's)
-        if total == 0:
+        totals = self._zeros(2, torch.int64)
+
+        def order(*a):
+            self.ctx.order_keys_device(self._view(), *a, pages=pages, keep_ties=keep_ties, totals_t=totals)
+            left = int(totals.cpu()[1])
+            if left:
+                raise ValueError(f"list_keys: {left} rows left out of the order (key or subset too long, or outside the arena)")
+
+        got = self._ordered(filters, n, order)
+        if got is None:
             return [(b"", 0, None)] * K
-        dev = self.arena.device
-        out_rows = {k: torch.zeros(total, dtype=v.dtype, device=dev) for k, v in rows.items()}
-        out_base = torch.zeros(K + 1, dtype=torch.int64, device=dev)
-        totals = torch.zeros(2, dtype=torch.int64, device=dev)
-        self.ctx.order_keys_device(self._view(), rows, base, K, total, out_rows, out_base, pages=pages,
-                                   keep_ties=keep_ties, totals_t=totals)
-        ob = [int(v) for v in out_base.cpu()]
-        left = int(totals.cpu()[1])
-        if left:
-            raise ValueError(f"list_keys: {left} rows left out of the order (key or subset too long, or outside the arena)")
-        sent = ob[K]
-        if sent == 0:
-            return [(b"", 0, None)] * K
-        src = ChangeSrc(*[C.c_void_p(out_rows[k].data_ptr()) for k in SRC_COLS])
-        need = U64()
-        _chk("drp_encode_size", self.ctx.L.drp_encode_size(self.ctx.h, C.byref(src), sent, C.byref(need)))
-        foff = torch.zeros(sent + 1, dtype=torch.int64, device=dev)
-        out = torch.zeros(max(int(need.value), 1), dtype=torch.uint8, device=dev)
-        self.ctx.encode_device(out_rows, self._view(), sent, foff, out, int(need.value))
-        fo, o = foff.cpu().numpy(), out.cpu().numpy()
-        ends = torch.tensor([ob[f + 1] - 1 for f in range(K) if ob[f + 1] > ob[f]], dtype=torch.int64, device=dev)
+        out_rows, ob, outs = got
+        ends = torch.tensor([ob[f + 1] - 1 for f in range(K) if ob[f + 1] > ob[f]], dtype=torch.int64,
+                            device=self.arena.device)
         koff, klen = out_rows["key_off"][ends].cpu().tolist(), out_rows["key_len"][ends].cpu().tolist()
         last = {int(e): bytes(self.arena[o_:o_ + l_].cpu().numpy()) for e, o_, l_ in zip(ends.cpu().tolist(), koff, klen)}
-        return [(o[int(fo[ob[f]]):int(fo[ob[f + 1]])].tobytes(), ob[f + 1] - ob[f],
-                 last[ob[f + 1] - 1] if ob[f + 1] > ob[f] else None) for f in range(K)]
-
-    def _view(self):
-        return self.arena[:self.arena_bytes] if self.arena_bytes else self.arena[:0]
+        return [(outs[f], ob[f + 1] - ob[f], last[ob[f + 1] - 1] if ob[f + 1] > ob[f] else None) for f in range(K)]
 
     def digest(self, bits, filter=None, n=None):
         """The store's bucket digest (digest_device over its view, rows [0, n), default max_keys): an
@@ -1512,6 +1318,12 @@ class Store:
         self.ctx.digest_device(self._view(), self.cols, n, filter, bits, cells)
         return cells
 
+    @staticmethod
+    def _set_bits(words_t):
+        """The increasing numbers of the bits set in an int64 tensor of words (numpy int64)."""
+        w = words_t.cpu().numpy().view(np.uint8)
+        return np.flatnonzero(np.unpackbits(w, bitorder="little")).astype(np.int64)
+
     def reconcile(self, peer_cells, bits, filter=None):
         """What this store holds in the buckets where its digest differs from a peer's: digest, diff
         and bucket select over the view with n = max_keys, and one encode_device with the arena as the
@@ -1520,34 +1332,16 @@ class Store:
         change frames, for the peer to decode and merge, and the increasing bucket numbers (numpy
         int64) in which the two digests differ."""
         import torch
-        dev = self.arena.device
-        if not isinstance(peer_cells, torch.Tensor):
-            peer_cells = torch.from_numpy(np.ascontiguousarray(peer_cells).view(np.int64).copy())
-        peer = peer_cells.to(device=dev, dtype=torch.int64).contiguous()
+        peer = self._set_tensor(peer_cells)
         if peer.numel() != 2 << bits:
             raise ValueError(f"peer_cells holds {peer.numel()} words, 2**{bits} cells are {2 << bits}")
         mine = self.digest(bits, filter)
-        words = max(1, (1 << bits) // 64)
-        bset = torch.zeros(words, dtype=torch.int64, device=dev)
-        cnt = torch.zeros(2, dtype=torch.int64, device=dev)  # [0] differing buckets, [1] rows selected
+        bset = self._zeros((1 << bits) // 64, torch.int64)
+        cnt = self._zeros(2, torch.int64)  # [0] differing buckets, [1] rows selected
         self.ctx.digest_diff_device(mine, peer, bits, bset, cnt[0:1])
-        n = self.max_keys
-        rows = {k: torch.zeros(n, dtype=(torch.int32 if k.endswith("_len") else
-                                         torch.uint8 if k == "flags" else torch.int64), device=dev)
-                for k in SRC_COLS}
-        self.ctx.select_buckets_device(self._view(), self.cols, n, filter, bits, bset, rows, None, cnt[1:2])
-        total = int(cnt.cpu()[1])  # (torch's stream was ordered after the ctx's)
-        w = bset.cpu().numpy().view(np.uint64)
-        buckets = np.flatnonzero(np.unpackbits(w.view(np.uint8), bitorder="little")).astype(np.int64)
-        if total == 0:
-            return b"", buckets
-        src = ChangeSrc(*[C.c_void_p(rows[k].data_ptr()) for k in SRC_COLS])
-        need = U64()
-        _chk("drp_encode_size", self.ctx.L.drp_encode_size(self.ctx.h, C.byref(src), total, C.byref(need)))
-        foff = torch.zeros(total + 1, dtype=torch.int64, device=dev)
-        out = torch.zeros(max(int(need.value), 1), dtype=torch.uint8, device=dev)
-        self.ctx.encode_device(rows, self._view(), total, foff, out, int(need.value))
-        return out.cpu().numpy()[:int(need.value)].tobytes(), buckets
+        rows = self._out_rows(self.max_keys)
+        self.ctx.select_buckets_device(self._view(), self.cols, self.max_keys, filter, bits, bset, rows, None, cnt[1:2])
+        return self._encode_rows(rows, cnt[1:2]), self._set_bits(bset)
 
     def _set_tensor(self, words):
         """A bit set (a tensor or a numpy array of 64-bit words) as an int64 tensor on the store's device."""
@@ -1592,7 +1386,6 @@ class Store:
         the rows in store order as change frames, for the peer to decode and merge, and the increasing
         cell numbers (numpy int64) in which the two second levels differ."""
         import torch
-        dev = self.arena.device
         bset = self._set_tensor(bucket_set)
         mine, n_set = self.digest_refined(bits, bset, sub_bits, filter)
         ncells = n_set << sub_bits
@@ -1601,27 +1394,13 @@ class Store:
             raise ValueError(f"peer_cells2 holds {peer.numel()} words, {ncells} cells are {2 * ncells}")
         if ncells == 0:
             return b"", np.zeros(0, np.int64)
-        cset = torch.zeros((ncells + 63) // 64, dtype=torch.int64, device=dev)
-        cnt = torch.zeros(2, dtype=torch.int64, device=dev)  # [0] differing cells, [1] rows selected
+        cset = self._zeros((ncells + 63) // 64, torch.int64)
+        cnt = self._zeros(2, torch.int64)  # [0] differing cells, [1] rows selected
         self.ctx.digest_diff_cells_device(mine, peer, ncells, cset, cnt[0:1])
-        n = self.max_keys
-        rows = {k: torch.zeros(n, dtype=(torch.int32 if k.endswith("_len") else
-                                         torch.uint8 if k == "flags" else torch.int64), device=dev)
-                for k in SRC_COLS}
-        self.ctx.select_refined_device(self._view(), self.cols, n, filter, bits, bset, sub_bits, cset, rows, None,
-                                       cnt[1:2])
-        total = int(cnt.cpu()[1])  # (torch's stream was ordered after the ctx's)
-        w = cset.cpu().numpy().view(np.uint64)
-        cells = np.flatnonzero(np.unpackbits(w.view(np.uint8), bitorder="little")).astype(np.int64)
-        if total == 0:
-            return b"", cells
-        src = ChangeSrc(*[C.c_void_p(rows[k].data_ptr()) for k in SRC_COLS])
-        need = U64()
-        _chk("drp_encode_size", self.ctx.L.drp_encode_size(self.ctx.h, C.byref(src), total, C.byref(need)))
-        foff = torch.zeros(total + 1, dtype=torch.int64, device=dev)
-        out = torch.zeros(max(int(need.value), 1), dtype=torch.uint8, device=dev)
-        self.ctx.encode_device(rows, self._view(), total, foff, out, int(need.value))
-        return out.cpu().numpy()[:int(need.value)].tobytes(), cells
+        rows = self._out_rows(self.max_keys)
+        self.ctx.select_refined_device(self._view(), self.cols, self.max_keys, filter, bits, bset, sub_bits, cset, rows,
+                                       None, cnt[1:2])
+        return self._encode_rows(rows, cnt[1:2]), self._set_bits(cset)
 
 
 class Comm:
@@ -1642,9 +1421,8 @@ class Comm:
     def allgather_index(self, ctx, local_t, global_t, base_t):
         """drp_index_allgather over torch CUDA tensors (int64 (per_rank, 4) local stats)."""
         ctx.order_after_torch(local_t)
-        tp = lambda t: C.c_void_p(t.data_ptr())
-        _chk("drp_index_allgather", self.L.drp_index_allgather(ctx.h, self.h, tp(local_t), local_t.shape[0],
-                                                               tp(global_t), tp(base_t)))
+        _chk("drp_index_allgather", self.L.drp_index_allgather(ctx.h, self.h, _tp(local_t), local_t.shape[0],
+                                                               _tp(global_t), _tp(base_t)))
 
     def close(self):
         if self.h:

@@ -14,8 +14,9 @@ import xxhash
 
 import _oracle as O
 import _streams as S
-from test_gpu_select import SRC_KEYS, _filter, _mask, _rows
-from test_gpu_store import Change, _change, _merge, _store, _winners, _wire
+from _relay import (SRC_KEYS, Change, change_at as _change, make_filter as _filter, mask as _mask, rows as _rows,
+                    wire_winners as _winners)
+from test_gpu_store import _merge, _store, _wire
 
 pytestmark = pytest.mark.gpu
 

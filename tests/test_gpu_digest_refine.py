@@ -14,10 +14,10 @@ import xxhash
 
 import _oracle as O
 import _streams as S
-from test_gpu_digest import (M64, P2, P3, _buckets, _cells_of, _check_rows, _content, _diff, _digest, _filter, _fp,
+from _relay import SRC_KEYS, change_at as _change, make_filter as _filter, wire_winners as _winners
+from test_gpu_digest import (M64, P2, P3, _buckets, _cells_of, _check_rows, _content, _diff, _digest, _fp,
                              _hashes, _np_merge, _set_words, big, ctx)  # noqa: F401 (big, ctx: fixtures)
-from test_gpu_select import SRC_KEYS
-from test_gpu_store import _change, _merge, _store, _winners, _wire
+from test_gpu_store import _merge, _store, _wire
 
 pytestmark = pytest.mark.gpu
 

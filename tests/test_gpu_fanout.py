@@ -11,7 +11,8 @@ import pytest
 
 import _oracle as O
 import _streams as S
-from test_gpu_select import SRC_KEYS, U64MAX, _crafted, _filter, _mask, _mixed_specs, _rows
+from _relay import SRC_KEYS, U64MAX, make_filter as _filter, mask as _mask, rows as _rows
+from test_gpu_select import _crafted, _mixed_specs
 
 pytestmark = pytest.mark.gpu
 

@@ -12,8 +12,8 @@ import pytest
 
 import _oracle as O
 import _streams as S
-from test_gpu_latest import (SRC_KEYS, U64MAX, _blob_stream, _expected, _filter, _mask, _pool_rows, _rows, _winners,
-                             _wire, _with_blobs)
+from _relay import SRC_KEYS, U64MAX, make_filter as _filter, mask as _mask, rows as _rows, winners as _winners
+from test_gpu_latest import _blob_stream, _expected, _pool_rows, _wire, _with_blobs
 from test_gpu_relay_wire_bounds import N as WB_N, _abs, _cuts, _out, _want, decoded  # noqa: F401 (decoded: a fixture)
 
 pytestmark = pytest.mark.gpu

@@ -12,12 +12,10 @@ import pytest
 
 import _oracle as O
 import _streams as S
+from _relay import (SRC_KEYS, U64MAX, check_decoded as _check_decoded, make_filter as _filter, mask as _mask,
+                    rows as _rows, winners as _winners)
 
 pytestmark = pytest.mark.gpu
-
-SRC_KEYS = ["key_off", "key_len", "subset_off", "subset_len", "value_off", "value_len", "change", "from", "to",
-            "flags"]
-U64MAX = 2**64 - 1
 
 
 @pytest.fixture(scope="module")
@@ -29,66 +27,7 @@ def ctx():
     c.close()
 
 
-# ---- the expected side ---------------------------------------------------------------------
-
-def _bytes_at(wire, off, n):
-    return bytes(wire[int(off):int(off) + int(n)])
-
-
-def _mask(wire, ref, n, spec):
-    """The select predicate of `spec` (change_range / subset / subset_none / key_prefix) over the
-    oracle's rows [0, n): numpy for the numbers and lengths, a byte compare per candidate."""
-    ty, fl = ref["type"][:n], ref["flags"][:n]
-    m = ((ty & 0x3F) == 1) & ((fl & 4) == 0)
-    if spec.get("change_range") is not None:
-        lo, hi = spec["change_range"]
-        m &= (ref["change"][:n] >= np.uint64(lo)) & (ref["change"][:n] <= np.uint64(hi))
-    if spec.get("subset_none"):
-        m &= (fl & 1) == 0
-    if spec.get("subset") is not None:
-        want = spec["subset"]
-        m &= ((fl & 1) != 0) & (ref["subset_len"][:n] == len(want))
-        for i in np.flatnonzero(m):
-            off = int(ref["payload_off"][i]) + int(ref["subset_off"][i])
-            m[i] = _bytes_at(wire, off, len(want)) == want
-    if spec.get("key_prefix") is not None:
-        want = spec["key_prefix"]
-        m &= ref["key_len"][:n] >= len(want)
-        for i in np.flatnonzero(m):
-            off = int(ref["payload_off"][i]) + int(ref["key_off"][i])
-            m[i] = _bytes_at(wire, off, len(want)) == want
-    return m
-
-
-def _winners(wire, ref, cand):
-    """Of the candidate rows `cand` (increasing), per identity the row with the greatest
-    (change, row); the winners in increasing row order."""
-    best = {}
-    for i in cand:
-        i = int(i)
-        po = int(ref["payload_off"][i])
-        has = bool(ref["flags"][i] & 1)
-        ident = (has, _bytes_at(wire, po + int(ref["subset_off"][i]), ref["subset_len"][i]) if has else b"",
-                 _bytes_at(wire, po + int(ref["key_off"][i]), ref["key_len"][i]))
-        cur = (int(ref["change"][i]), i)
-        if ident not in best or cur > best[ident]:
-            best[ident] = cur
-    return np.array(sorted(i for _, i in best.values()), np.int64), best
-
-
-def _rows(ref, idx):
-    """Rows idx as encoder rows: offsets absolute (payload_off + column), flags masked to
-    SUBSET | VALUE."""
-    po = ref["payload_off"][idx].astype(np.uint64)
-    cols = {}
-    for k in ["key", "subset", "value"]:
-        cols[k + "_off"] = po + ref[k + "_off"][idx].astype(np.uint64)
-        cols[k + "_len"] = ref[k + "_len"][idx].astype(np.uint32)
-    for k in ["change", "from", "to"]:
-        cols[k] = ref[k][idx].astype(np.uint64)
-    cols["flags"] = (ref["flags"][idx] & 3).astype(np.uint8)
-    return cols
-
+# ---- the expected side (the predicate, the winners, the rows and the decoded check: _relay) ---
 
 def _expected(wire, spec, blob_remaining=0):
     w = np.frombuffer(wire, np.uint8)
@@ -97,36 +36,6 @@ def _expected(wire, spec, blob_remaining=0):
     idx, best = _winners(w, ref, np.flatnonzero(_mask(w, ref, n, spec)))
     cols = _rows(ref, idx)
     return O.encode_changes(wire, cols), idx, cols, ref, best
-
-
-def _filter(spec):
-    from _gpu import drp_amd
-    if not spec:
-        return None
-    return drp_amd.make_filter(**spec)
-
-
-def _field_bytes(wire, cols, k, i):
-    return _bytes_at(wire, cols[k + "_off"][i], cols[k + "_len"][i])
-
-
-def _check_decoded(out, wire, cols):
-    """The output decodes to the winners: numbers, presence and key / subset / value bytes."""
-    w, o = np.frombuffer(wire, np.uint8), np.frombuffer(out, np.uint8)
-    d = O.decode_batch(out)
-    n = len(cols["flags"])
-    assert d["nframes"] == n and d["err_code"] == 0 and d["tail"] == 0
-    assert np.all(d["type"][:n] == 1)
-    for k in ["change", "from", "to"]:
-        np.testing.assert_array_equal(d[k][:n], cols[k], err_msg=k)
-    np.testing.assert_array_equal(d["flags"][:n] & 3, cols["flags"])
-    dc = _rows(d, np.arange(n))
-    for i in range(n):
-        assert _field_bytes(o, dc, "key", i) == _field_bytes(w, cols, "key", i), i
-        if cols["flags"][i] & 1:
-            assert _field_bytes(o, dc, "subset", i) == _field_bytes(w, cols, "subset", i), i
-        if cols["flags"][i] & 2:
-            assert _field_bytes(o, dc, "value", i) == _field_bytes(w, cols, "value", i), i
 
 
 def _latest(ctx, wire, spec, blob_remaining=0, stage=None):

@@ -10,11 +10,10 @@ import pytest
 
 import _oracle as O
 import _streams as S
+from _relay import SRC_KEYS as SRC, U64MAX, change_at, down as _down, dtype as _dtype, up as _up
 
 pytestmark = pytest.mark.gpu
 
-U64MAX = 2**64 - 1
-SRC = ["key_off", "key_len", "subset_off", "subset_len", "value_off", "value_len", "change", "from", "to", "flags"]
 GUARD = 0x5A
 TILE, SCAN = 4096, 1024  # the sort workgroup's pairs and the counts of one first-level scan block
 
@@ -30,10 +29,6 @@ def ctx():
 
 # ---- inputs, the call, the expected side ---------------------------------------------------------
 
-def _dtype(k):
-    return np.uint32 if k.endswith("_len") else np.uint8 if k == "flags" else np.uint64
-
-
 def _rows(change, cap=None):
     """Encoder rows with the given change column; every other column is a different function of the
     row index, so a row that lands in the wrong place shows in each of them. cap: the arrays' entries."""
@@ -46,20 +41,6 @@ def _rows(change, cap=None):
             "from": i ^ 0x5555, "to": i * 2 + 9, "flags": i % 4}
     cols["change"][:n] = change
     return {k: v.astype(_dtype(k)) for k, v in cols.items()}
-
-
-def _signed(a):
-    return a.view({1: np.uint8, 4: np.int32, 8: np.int64}[a.dtype.itemsize])
-
-
-def _up(a):
-    import torch
-    return torch.from_numpy(_signed(np.ascontiguousarray(a)).copy()).to("cuda:0")
-
-
-def _down(t):
-    a = t.cpu().numpy()
-    return a.view({1: np.uint8, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
 
 
 def _guards(cap, K):
@@ -359,9 +340,6 @@ def test_deterministic(ctx):
 
 # ---- end to end through the store ----------------------------------------------------------------------
 
-Change = collections.namedtuple("Change", "has subset key change frm to hv value")
-
-
 def _wire(changes):
     return b"".join(S.frame(S.change_payload(k, ch, fr, to, value=v, subset=sub)) for k, sub, ch, fr, to, v in changes)
 
@@ -373,13 +351,7 @@ def _decode(wire):
     ref = O.decode_batch(wire)
     n = ref["nframes"]
     assert ref["err_code"] == 0 and ref["consumed"] == len(wire) and np.all(ref["type"][:n] == 1)
-    out = []
-    for i in range(n):
-        po, fl = int(ref["payload_off"][i]), int(ref["flags"][i])
-        f = lambda k: wire[po + int(ref[k + "_off"][i]):po + int(ref[k + "_off"][i]) + int(ref[k + "_len"][i])]
-        out.append(Change(bool(fl & 1), f("subset") if fl & 1 else b"", f("key"), int(ref["change"][i]),
-                          int(ref["from"][i]), int(ref["to"][i]), bool(fl & 2), f("value") if fl & 2 else b""))
-    return out, ref
+    return [change_at(wire, ref, i) for i in range(n)], ref
 
 
 def _reorder(wire):

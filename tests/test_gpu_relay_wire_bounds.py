@@ -11,7 +11,7 @@ import pytest
 
 import _oracle as O
 import _streams as S
-from test_gpu_select import SRC_KEYS, _filter, _rows
+from _relay import SRC_KEYS, make_filter as _filter, rows as _rows
 
 pytestmark = pytest.mark.gpu
 

@@ -12,12 +12,12 @@ import pytest
 
 import _oracle as O
 import _streams as S
+from _relay import (U64MAX, Change, bytes_at as _bytes_at, device_cols as _device_cols, make_filter as _filter,
+                    wire_winners as _winners)
 
 pytestmark = pytest.mark.gpu
 
-U64MAX = 2**64 - 1
 COUNTERS = ["winners", "inserted", "replaced", "unchanged", "stale", "skipped"]
-Change = collections.namedtuple("Change", "has subset key change frm to hv value")
 
 
 @pytest.fixture(scope="module")
@@ -29,53 +29,7 @@ def ctx():
     c.close()
 
 
-# ---- the expected side ---------------------------------------------------------------------
-
-def _bytes_at(wire, off, n):
-    return bytes(wire[int(off):int(off) + int(n)])
-
-
-def _mask(wire, ref, n, spec):
-    """The select predicate of `spec` over the oracle's rows [0, n)."""
-    ty, fl = ref["type"][:n], ref["flags"][:n]
-    m = ((ty & 0x3F) == 1) & ((fl & 4) == 0)
-    if spec.get("change_range") is not None:
-        lo, hi = spec["change_range"]
-        m &= (ref["change"][:n] >= np.uint64(lo)) & (ref["change"][:n] <= np.uint64(hi))
-    if spec.get("subset") is not None:
-        want = spec["subset"]
-        m &= ((fl & 1) != 0) & (ref["subset_len"][:n] == len(want))
-        for i in np.flatnonzero(m):
-            m[i] = _bytes_at(wire, int(ref["payload_off"][i]) + int(ref["subset_off"][i]), len(want)) == want
-    if spec.get("key_prefix") is not None:
-        want = spec["key_prefix"]
-        m &= ref["key_len"][:n] >= len(want)
-        for i in np.flatnonzero(m):
-            m[i] = _bytes_at(wire, int(ref["payload_off"][i]) + int(ref["key_off"][i]), len(want)) == want
-    return m
-
-
-def _change(wire, ref, i):
-    po, fl = int(ref["payload_off"][i]), int(ref["flags"][i])
-    f = lambda k: _bytes_at(wire, po + int(ref[k + "_off"][i]), ref[k + "_len"][i])
-    return Change(bool(fl & 1), f("subset") if fl & 1 else b"", f("key"), int(ref["change"][i]), int(ref["from"][i]),
-                  int(ref["to"][i]), bool(fl & 2), f("value") if fl & 2 else b"")
-
-
-def _winners(wire, spec=None, blob_remaining=0):
-    """The winners of drp_latest_device over the wire's delivered rows under `spec`, as
-    (batch rows, Changes), in increasing row order."""
-    ref = O.decode_batch(wire, blob_remaining=blob_remaining)
-    n = ref["nframes"]
-    best = {}
-    for i in np.flatnonzero(_mask(wire, ref, n, spec or {})):
-        c = _change(wire, ref, int(i))
-        cur = (c.change, int(i))
-        if (c.has, c.subset, c.key) not in best or cur > best[(c.has, c.subset, c.key)][0]:
-            best[(c.has, c.subset, c.key)] = (cur, c)
-    win = sorted((cur[1], c) for cur, c in best.values())
-    return [i for i, _ in win], [c for _, c in win]
-
+# ---- the expected side (the predicate, the winners and the Change tuple: _relay) -------------
 
 def _r16(n):
     return (n + 15) & ~15
@@ -206,28 +160,6 @@ def _pool(n, pool, changes, seed, subsets=(None, None, b"s"), first=0):
     rng = random.Random(seed)
     return [(b"key-%d" % (first + rng.randrange(pool)), rng.choice(subsets), rng.randrange(changes), r % 128,
              (r * 7) % 128, b"%d" % r if r % 3 else None) for r in range(n)]
-
-
-def _device_cols(ctx, wire, blob_remaining=0):
-    """The wire on the device with its decoded columns (decode_staged's rows, uploaded): the
-    arguments of merge_device / latest_device. The staged batch stays held."""
-    import torch
-    dev = torch.device("cuda", 0)
-    g = ctx.decode_staged(wire, blob_remaining=blob_remaining)
-    n = g["nframes"]
-    signed = {np.dtype(np.uint64): np.int64, np.dtype(np.uint32): np.int32, np.dtype(np.uint8): np.uint8}
-    cols = {}
-    for k in ["payload_off", "payload_len", "type", "flags"] + O.COLS32 + O.COLS64:
-        a = np.zeros(max(n, 1), g[k].dtype)
-        a[:n] = g[k][:n]
-        cols[k] = torch.from_numpy(a.view(signed[a.dtype])).to(dev)
-    wire_t = torch.from_numpy(np.frombuffer(wire, np.uint8).copy()).to(dev)
-    return wire_t, cols, n
-
-
-def _filter(spec):
-    from _gpu import drp_amd
-    return drp_amd.make_filter(**spec) if spec else None
 
 
 def _store(ctx, max_keys, arena_bytes):

@@ -13,7 +13,8 @@ import copy
 import numpy as np
 import pytest
 
-from test_gpu_store import Model, U64MAX, _check, _device_cols, _dump, _filter, _merge, _same_raw, _store, _winners, _wire
+from _relay import U64MAX, device_cols as _device_cols, make_filter as _filter, wire_winners as _winners
+from test_gpu_store import Model, _check, _dump, _merge, _same_raw, _store, _wire
 
 pytestmark = pytest.mark.gpu
 

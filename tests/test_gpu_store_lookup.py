@@ -11,14 +11,13 @@ import numpy as np
 import pytest
 
 import _streams as S
-from test_gpu_store import (Model, U64MAX, _blob_stream, _device_cols, _dump, _encode, _filter, _mask, _merge, _pool,
-                            _same_raw, _store, _wire)
+from _relay import SRC_KEYS as SRC, U64MAX, device_cols as _device_cols, make_filter as _filter, mask as _mask
+from test_gpu_store import Model, _blob_stream, _dump, _encode, _merge, _pool, _same_raw, _store, _wire
 
 pytestmark = pytest.mark.gpu
 
 NONE, ABSENT, BEHIND, LEVEL, AHEAD = range(5)
 FOUND = (BEHIND, LEVEL, AHEAD)
-SRC = ["key_off", "key_len", "subset_off", "subset_len", "value_off", "value_len", "change", "from", "to", "flags"]
 AA, PAD, M64 = 0xAA, 64, 2**64
 
 

@@ -9,13 +9,13 @@ import pytest
 
 import _oracle as O
 import _streams as S
-from test_gpu_store import (Model, U64MAX, _blob_stream, _change, _check, _device_cols, _dump, _encode, _filter, _mask,
-                            _pool, _same_raw, _store, _wire)
+from _relay import (SRC_KEYS as SRC, U64MAX, change_at as _change, device_cols as _device_cols, make_filter as _filter,
+                    mask as _mask)
+from test_gpu_store import Model, _blob_stream, _check, _dump, _encode, _pool, _same_raw, _store, _wire
 
 pytestmark = pytest.mark.gpu
 
 NONE, INSERTED, REPLACED, UNCHANGED, STALE, SKIPPED = range(6)
-SRC = ["key_off", "key_len", "subset_off", "subset_len", "value_off", "value_len", "change", "from", "to", "flags"]
 EE = 0xEE
 
 
