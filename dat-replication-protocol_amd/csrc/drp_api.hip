@@ -1,9 +1,9 @@
 // drp_api.hip — the extern "C" boundary of libdrp (include/drp.h): the context's life cycle, decode,
 // fetch and encode. The relay entry points (select, latest per key, fan-out) are in drp_relay.hip.
 //
-// Owns one HIP stream + scratch per device context and launches the decode / encode
-// kernels. A decode is one pass: the kernel resolves every tile's entry exactly
-// (DESIGN.md §decode), so there is no host-side repair loop.
+// Owns the HIP streams and scratch of a device context and launches the decode / encode kernels.
+// A decode speculates and verifies (run_decode_spec: a host round trip when the predictions hold,
+// repair passes when not), with the exact one-pass kernel behind it (run_decode_exact).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -164,7 +164,6 @@ int drp_open(int device, drp_ctx **out) {
   if (const char *e = getenv("DRP_CASCADE_MIN")) c->cascade_min = (uint32_t)strtoul(e, nullptr, 10);
   if (const char *e = getenv("DRP_JUMP_MIN")) c->jump_min = strtoll(e, nullptr, 10);
   if (const char *e = getenv("DRP_WALK_MIN")) c->walk_min = strtoull(e, nullptr, 10);
-  if (const char *e = getenv("DRP_SIDE_MIN")) c->side_min = strtoull(e, nullptr, 10);
   if (const char *e = getenv("DRP_PIPE_CHUNK")) c->pipe_chunk = strtoull(e, nullptr, 10) << 20;
   if (const char *e = getenv("DRP_CREC")) c->crec = atoi(e);
   if (const char *e = getenv("DRP_CLAIMS")) c->claims_mode = strcmp(e, "fast") == 0 ? 2 : strcmp(e, "hop") == 0 ? 3 : 0;
@@ -206,12 +205,6 @@ void drp_close(drp_ctx *c) {
   (void)hipStreamSynchronize(c->fst);
   (void)hipStreamDestroy(c->fst);
   (void)hipEventDestroy(c->fev);
-  if (c->sst) {
-    (void)hipStreamSynchronize(c->sst);
-    (void)hipStreamDestroy(c->sst);
-  }
-  for (auto &e : c->sev)
-    if (e) (void)hipEventDestroy(e);
   c->fbounce.release();
   (void)hipStreamDestroy(c->st);
   delete c;
@@ -412,6 +405,21 @@ DecodeParams decode_params(const drp_ctx *c, const DecLayout &L, const uint8_t *
   return P;
 }
 
+// What both decode kernels report of a launch sequence: the event times and the repair counters
+// (seg_repairs is counted as the repairs run; the exact kernel's caller sets exact_retries).
+void launch_timing(drp_ctx *c, uint32_t spec_repairs, uint32_t relisted) {
+  float ms = 0;
+  (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
+  c->timing.decode_ms = ms;
+  (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[3]);
+  c->timing.total_ms = ms;
+  c->timing.finalize_ms = 0;
+  c->timing.strict_reruns = 0;
+  c->timing.exact_retries = 0;
+  c->timing.spec_repairs = spec_repairs;
+  c->timing.verify_relisted = relisted;
+}
+
 int run_decode_exact_once(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const uint64_t *stream_off,
                           const uint64_t *entry, uint64_t ns, const drp_frames *fr, const drp_changes *co,
                           uint64_t cap, drp_stream_result *res) {
@@ -484,15 +492,7 @@ int run_decode_exact_once(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, con
   uint32_t h[2];
   CHK(hipMemcpyAsync(h, ctrl, 8, hipMemcpyDeviceToHost, st));
   CHK(hipStreamSynchronize(st));
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
-  c->timing.decode_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[3]);
-  c->timing.total_ms = ms;
-  c->timing.finalize_ms = 0;
-  c->timing.spec_repairs = 0;
-  c->timing.strict_reruns = 0;
-  c->timing.verify_relisted = 0;
+  launch_timing(c, 0, 0);
   c->timing.seg_repairs = 0;
   TRACE("decode done: tiles=%u flags=%u", h[0], h[1]);
   if (dstats) {
@@ -540,8 +540,7 @@ int run_decode_exact(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const ui
   return r == kWaitExpired ? DRP_E_HIP : r;
 }
 
-// The default decode: speculate-and-verify kernel (drp_decode_spec.hip). Returns DRP_E_RETRY
-// when a prediction failed (or a bounded wait expired): the caller then runs the exact kernel.
+// The speculative decode's repair budget (run_decode_spec, below).
 constexpr int kSpecRepairPasses = 16;
 constexpr int kChain = 3;  // dirty-list repair passes queued per host read
 constexpr int kSegRepairAfter = 3;  // verify passes before the segmented repair of the streams still missing
@@ -563,67 +562,77 @@ __global__ __launch_bounds__(256) void pass_clear_kernel(uint64_t *incl_e, uint6
   }
 }
 
-int run_decode_spec(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const uint64_t *stream_off,
-                    const uint64_t *entry, uint64_t ns, const drp_frames *fr, const drp_changes *co,
-                    uint64_t cap, drp_stream_result *res) {
-  if (((uintptr_t)bytes & 15) != 0) return DRP_E_INVAL;
-  const uint32_t B = drp_spec_tile_bytes() / 64;
-  const DecLayout L = dec_layout(B, nbytes, ns);
-  if (!c->scratch.ensure(L.total)) return DRP_E_NOMEM;
-  const uint64_t NT = L.ntiles_max;
-  uint64_t *tile_prefix = c->scratch.at<uint64_t>(L.tile_prefix);
-  uint64_t *rec = c->scratch.at<uint64_t>(L.rec);
-  uint32_t *tstream = c->scratch.at<uint32_t>(L.tstream);
-  uint64_t *sgscan = c->scratch.at<uint64_t>(L.scan_tmp);
-  hipStream_t st = c->st;
-  CHK(hipEventRecord(c->ev[0], st));
-  DecodeParams P = decode_params(c, L, bytes, nbytes, stream_off, entry, ns, fr, co, cap);
-  uint64_t *perr = P.payload_err, *scount = P.scount;
-  uint32_t *ctrl = P.counter;
-  P.claim = rec;
-  P.incl_e = rec + NT;
-  P.work = reinterpret_cast<uint32_t *>(rec + 2 * NT);
-  P.work_n = ctrl + 2;
-  P.ent = c->scratch.at<uint8_t>(L.ent);
-  P.ent_n = P.ent + NT * 128;
-  P.ent_c = P.ent_n + NT * 128;
-  P.vlist = reinterpret_cast<uint32_t *>(rec + 2 * NT) + NT;  // (after the dense work list)
-  P.vlist_n = ctrl + 5;
-  P.tile_k = c->scratch.at<uint8_t>(L.tk);
-  P.tile_sparse = c->scratch.at<uint8_t>(L.tsp);
-  P.first_miss = c->scratch.at<uint64_t>(L.fmiss);
-  // dirty lists (ping-pong, after the work list and vlist in rec): the tiles each verify pass's
-  // repairs handed to the next pass; counts at ctrl[8 + k], overflow words at ctrl[10 + k]
-  uint32_t *dl[2] = {reinterpret_cast<uint32_t *>(rec + 3 * NT), reinterpret_cast<uint32_t *>(rec + 3 * NT) + NT};
-  P.dlist = dl[0];
-  P.dlist_n = ctrl + 8;
-  P.dlist_cap = NT;
-  P.dstamp = reinterpret_cast<uint32_t *>(rec + 4 * NT);  // (after the dirty lists)
-  P.pass_id = 1;
-  P.change_checks = (uint32_t)c->change_checks;
-  P.kstrong_hbm = c->kstrong_hbm;  // (tests: weaker predictions)
-  P.cascade_min = c->cascade_min;
-  P.jump_min = c->jump_min >= 0 ? (uint32_t)c->jump_min : (uint32_t)std::max<uint64_t>(64, NT / 512);
-  P.dlist_cap = std::min<uint64_t>(NT, c->dirty_cap);  // (tests: DRP_DIRTY_CAP)
-  if (c->claims_mode == 3 || (c->claims_mode == 0 && NT >= c->walk_min)) {
-    P.walk_rp = c->scratch.at<uint64_t>(L.walk);
-    P.walk_entry = c->scratch.at<uint64_t>(L.went);
-    P.walk_dense = c->scratch.at<unsigned long long>(L.wdense);
-    P.walk_hop = c->claims_mode == 3 ? 1u : 2u;  // 2: by the density sample
-    P.walk_tpr = drp_walk_tiles_per_region(NT, (int)P.walk_hop);
+// One speculative decode's state, shared by the steps of run_decode_spec.
+struct SpecCall {
+  drp_ctx *c;
+  DecLayout L;
+  uint64_t ns;
+  const drp_frames *fr;
+  const drp_changes *co;
+  drp_stream_result *res;
+  DecodeParams P;
+  uint64_t NT;
+  uint32_t *dl[2];  // the dirty lists (ping-pong): counts at ctrl[8 + k], overflow words at ctrl[10 + k]
+  uint32_t *ctrl;
+  uint32_t h[16];  // ctrl's words as last read back
+  int pass;        // repair passes run
+  hipStream_t st;
+
+  // The kernels' parameters: decode_params plus the speculative kernels' arrays in the scratch layout.
+  void params(const uint8_t *bytes, uint64_t nbytes, const uint64_t *stream_off, const uint64_t *entry,
+              uint64_t cap) {
+    NT = L.ntiles_max;
+    P = decode_params(c, L, bytes, nbytes, stream_off, entry, ns, fr, co, cap);
+    ctrl = P.counter;
+    st = c->st;
+    uint64_t *rec = c->scratch.at<uint64_t>(L.rec);
+    P.claim = rec;
+    P.incl_e = rec + NT;
+    P.tile_stream = ns > 1 ? c->scratch.at<uint32_t>(L.tstream) : nullptr;  // (drp_launch_spec_head fills it)
+    P.work = reinterpret_cast<uint32_t *>(rec + 2 * NT);
+    P.work_n = ctrl + 2;
+    P.ent = c->scratch.at<uint8_t>(L.ent);
+    P.ent_n = P.ent + NT * 128;
+    P.ent_c = P.ent_n + NT * 128;
+    P.vlist = reinterpret_cast<uint32_t *>(rec + 2 * NT) + NT;  // (after the dense work list)
+    P.vlist_n = ctrl + 5;
+    P.tile_k = c->scratch.at<uint8_t>(L.tk);
+    P.tile_sparse = c->scratch.at<uint8_t>(L.tsp);
+    P.first_miss = c->scratch.at<uint64_t>(L.fmiss);
+    // dirty lists (ping-pong, after the work list and vlist in rec): the tiles each verify pass's
+    // repairs handed to the next pass; counts at ctrl[8 + k], overflow words at ctrl[10 + k]
+    dl[0] = reinterpret_cast<uint32_t *>(rec + 3 * NT);
+    dl[1] = dl[0] + NT;
+    P.dlist = dl[0];
+    P.dlist_n = ctrl + 8;
+    P.dstamp = reinterpret_cast<uint32_t *>(rec + 4 * NT);  // (after the dirty lists)
+    P.pass_id = 1;
+    P.change_checks = (uint32_t)c->change_checks;
+    P.kstrong_hbm = c->kstrong_hbm;  // (tests: weaker predictions)
+    P.cascade_min = c->cascade_min;
+    P.jump_min = c->jump_min >= 0 ? (uint32_t)c->jump_min : (uint32_t)std::max<uint64_t>(64, NT / 512);
+    P.dlist_cap = std::min<uint64_t>(NT, c->dirty_cap);  // (tests: DRP_DIRTY_CAP)
+    if (c->claims_mode == 3 || (c->claims_mode == 0 && NT >= c->walk_min)) {
+      P.walk_rp = c->scratch.at<uint64_t>(L.walk);
+      P.walk_entry = c->scratch.at<uint64_t>(L.went);
+      P.walk_dense = c->scratch.at<unsigned long long>(L.wdense);
+      P.walk_hop = c->claims_mode == 3 ? 1u : 2u;  // 2: by the density sample
+      P.walk_tpr = drp_walk_tiles_per_region(NT, (int)P.walk_hop);
+    }
+    // claims_fast's per-frame records (fast_records, 20 B per frame slot): emit_lean expands them into
+    // columns without reading the wire again (DRP_CREC=0: off; a buffer that cannot be had: off)
+    const uint64_t rec_bytes = al(NT * drp_spec_rec_words() * 4ull);
+    if (c->crec && c->recbuf.ensure(rec_bytes + (cap / 64 + 2) * 4)) {
+      P.rec = c->recbuf.at<uint32_t>(0);
+      P.chunk_tile = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(c->recbuf.p) + rec_bytes);
+      P.tile_rec = c->scratch.at<uint32_t>(L.trec);
+      P.tile_recok = c->scratch.at<uint8_t>(L.trok);
+    }
+    if (c->stats) P.stats = c->dstats;
   }
-  // claims_fast's per-frame records (fast_records, 20 B per frame slot): emit_lean expands them into
-  // columns without reading the wire again (DRP_CREC=0: off; a buffer that cannot be had: off)
-  const uint64_t rec_bytes = al(NT * drp_spec_rec_words() * 4ull);
-  if (c->crec && c->recbuf.ensure(rec_bytes + (cap / 64 + 2) * 4)) {
-    P.rec = c->recbuf.at<uint32_t>(0);
-    P.chunk_tile = reinterpret_cast<uint32_t *>(static_cast<uint8_t *>(c->recbuf.p) + rec_bytes);
-    P.tile_rec = c->scratch.at<uint32_t>(L.trec);
-    P.tile_recok = c->scratch.at<uint8_t>(L.trok);
-  }
-  unsigned long long *dstats = c->stats ? c->dstats : nullptr;
-  if (dstats) P.stats = dstats;
-  {  // tile_prefix and every per-decode clear in one launch
+
+  // tile_prefix and every per-decode clear in one launch
+  int clears() {
     ClearSet cs = {};
     hipError_t ce = hipSuccess;
     auto add = [&](void *p, uint64_t bytes, uint32_t v) {
@@ -635,75 +644,78 @@ int run_decode_spec(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const uin
       cs.bytes[cs.n] = bytes;
       cs.value[cs.n++] = v;
     };
-    add(rec + NT, NT * 8, 0);  // incl_e (every claim is written by the claims kernels)
-    add(perr, ns * 8, 0xFF);
-    add(scount, 2 * ns * 8, 0);
+    add(P.incl_e, NT * 8, 0);  // (every claim is written by the claims kernels)
+    add(P.payload_err, ns * 8, 0xFF);
+    add(P.scount, 2 * ns * 8, 0);
     add(ctrl, 64, 0);
     add(P.dstamp, NT * 4, 0);
     add(P.first_miss, ns * 8, 0xFF);
     if (P.tile_rec) add(P.tile_rec, NT * 4, 0xFF);
     if (P.walk_dense) add(P.walk_dense, 16, 0);
-    if (dstats) add(dstats, 64 * 8, 0);
+    if (P.stats) add(P.stats, 64 * 8, 0);
     CHK(ce);
-    CHK(drp_launch_prologue(B, stream_off, ns, tile_prefix, &cs, st));
+    CHK(drp_launch_prologue(drp_spec_tile_bytes() / 64, P.stream_off, ns, c->scratch.at<uint64_t>(L.tile_prefix), &cs,
+                            st));
+    return DRP_OK;
   }
-  c->timing.seg_repairs = 0;
-  CHK(hipEventRecord(c->ev[1], st));
-  // claims + verification, then the prediction check on the host (one flag word) before any
-  // output is written: a failed prediction is repaired in place first. Verify patched the
-  // missed tiles' claims, so verify runs again (each pass fixes at least the first missed tile,
-  // whose entry is exact) until a pass has no miss. Only when that does not settle within a
-  // few passes (e.g. a protocol error on the exact chain) does the caller run the exact kernel.
-  uint32_t h[16];
-  const uint32_t miss = drp_spec_miss_bit();
-  CHK(drp_launch_spec_head(&P, NT, ns, tstream, st));  // (verify_counts keeps the relisted count in ctrl[14])
+
   // Emission, the output bases and the per-stream results go right behind verification, with no
   // host read in between: the emit, finalize and key kernels read the flag word and do nothing
-  // after a failed prediction, which is repaired below before they run again. A decode whose
+  // after a failed prediction, which is repaired before they run again. A decode whose
   // prediction holds makes one host round trip.
-  const uint32_t *abort_flag = P.overflow;
-  // Batches of at least side_min tiles (DRP_SIDE_MIN; off by default) run the side emitters and
-  // stream_counts on the side stream, beside emit_recs (small ones and staged pieces would only
-  // pay the events' host time).
-  DrpSide side = {};
-  const DrpSide *sidep = nullptr;
-  if (NT >= c->side_min) {
-    if (!c->sst) {
-      hipStream_t s = nullptr;
-      if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess ||
-          hipEventCreateWithFlags(&c->sev[0], hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&c->sev[1], hipEventDisableTiming) != hipSuccess) {
-        if (s) (void)hipStreamDestroy(s);
-        for (auto &e : c->sev) {
-          if (e) (void)hipEventDestroy(e);
-          e = nullptr;
-        }
-        return DRP_E_HIP;
-      }
-      c->sst = s;
-    }
-    side.st = c->sst;
-    side.fork = c->sev[0];
-    side.join = c->sev[1];
-    sidep = &side;
-  }
-  auto launch_tail = [&]() -> int {
-    CHK(drp_launch_spec_tail(&P, NT, ns, tstream, sgscan, st, sidep));
+  int tail() {
+    const uint32_t *abort_flag = P.overflow;
+    CHK(drp_launch_spec_tail(&P, NT, ns, c->scratch.at<uint64_t>(L.scan_tmp), st));
     CHK(hipEventRecord(c->ev[2], st));
-    CHK(drp_launch_finalize(bytes, stream_off, ns, tile_prefix, P.tile_exit, P.tile_base, P.tile_count, perr,
-                            scount, fr->type, co->flags, cap, res, abort_flag, drp_spec_retry_mask(), st));
-    CHK(drp_launch_key_post(bytes, tile_prefix, ns, P.tile_base, P.tile_count, cap, fr, co,
+    CHK(drp_launch_finalize(P.bytes, P.stream_off, ns, P.tile_prefix, P.tile_exit, P.tile_base, P.tile_count,
+                            P.payload_err, P.scount, fr->type, co->flags, P.cap, res, abort_flag,
+                            drp_spec_retry_mask(), st));
+    CHK(drp_launch_key_post(P.bytes, P.tile_prefix, ns, P.tile_base, P.tile_count, P.cap, fr, co,
                             c->key_post == DRP_KEY_POST_FLAGS, abort_flag, drp_spec_retry_mask(), st));
     CHK(hipEventRecord(c->ev[3], st));
     CHK(hipMemcpyAsync(h, ctrl, 64, hipMemcpyDeviceToHost, st));
     CHK(sync_watch(st, "decode (claims .. key_post)"));
     return DRP_OK;
-  };
-  if (const int rt = launch_tail()) return rt;
-  const uint32_t relisted = h[14];
-  int pass = 0;
-  bool seg_done = false;
-  if ((h[1] & drp_spec_retry_mask()) == miss) {
+  }
+
+  // The misses keep coming one tile per pass (wrong predictions that agree with each other):
+  // recompute the claims of each stream from its first missed tile by exact chain walks
+  // (drp_decode_spec.hip, segmented repair); the caller then verifies them, over every tile (*full)
+  // when any claims were rewritten.
+  int seg_repair(bool *full) {
+    std::vector<uint64_t> fm(ns), tp(ns + 1);
+    CHK(hipMemcpyAsync(fm.data(), P.first_miss, ns * 8, hipMemcpyDeviceToHost, st));
+    CHK(hipMemcpyAsync(tp.data(), P.tile_prefix, (ns + 1) * 8, hipMemcpyDeviceToHost, st));
+    CHK(hipStreamSynchronize(st));
+    for (uint64_t s = 0; s < ns; s++) {
+      if (fm[s] == ~0ull) continue;
+      TRACE("decode_spec: segmented repair of stream %llu from tile %llu to %llu", (unsigned long long)s,
+            (unsigned long long)fm[s], (unsigned long long)tp[s + 1]);
+      // the parallel seg_claims' per-tile candidate positions (256 B per tile of the range),
+      // allocated on the first segmented repair that needs more
+      const uint64_t need = std::min<uint64_t>(tp[s + 1] - fm[s], 8192ull * 1024) * 64;
+      if (need > c->ctile_cap) {
+        if (c->ctile) (void)hipFree(c->ctile);
+        c->ctile = nullptr;
+        c->ctile_cap = 0;
+        if (hipMalloc((void **)&c->ctile, need * 4) == hipSuccess) c->ctile_cap = need;
+        else (void)hipGetLastError();
+      }
+      CHK(drp_launch_seg_repair(&P, s, fm[s], tp[s + 1], c->scratch.at<uint64_t>(L.segw), c->ctile, c->ctile_cap,
+                                st));
+      c->timing.seg_repairs++;
+      *full = true;  // (claims rewritten over a range)
+    }
+    return DRP_OK;
+  }
+
+  // A failed prediction is repaired in place before any output is written. Verify patched the
+  // missed tiles' claims, so verify runs again (each pass fixes at least the first missed tile,
+  // whose entry is exact) until a pass has no miss. Only when that does not settle within a
+  // few passes (e.g. a protocol error on the exact chain) does the caller run the exact kernel.
+  int repair() {
+    const uint32_t miss = drp_spec_miss_bit();
+    bool seg_done = false;
     // the next pass verifies the dirty list the last one wrote (k: its index), or every tile
     uint32_t k = 0;
     bool full = h[10] != 0 || h[8] > P.dlist_cap;
@@ -716,33 +728,8 @@ int run_decode_spec(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const uin
       const uint64_t seg_early = std::max<uint64_t>(1024, NT / 256);
       if ((pass >= kSegRepairAfter || (pass > 0 && h[8 + k] > seg_early) || (h[1] & drp_spec_cascade_bit())) &&
           !seg_done) {
-        // the misses keep coming one tile per pass (wrong predictions that agree with each
-        // other): recompute the claims of each stream from its first missed tile by exact
-        // chain walks (drp_decode_spec.hip, segmented repair), then verify them
         seg_done = true;
-        std::vector<uint64_t> fm(ns), tp(ns + 1);
-        CHK(hipMemcpyAsync(fm.data(), P.first_miss, ns * 8, hipMemcpyDeviceToHost, st));
-        CHK(hipMemcpyAsync(tp.data(), tile_prefix, (ns + 1) * 8, hipMemcpyDeviceToHost, st));
-        CHK(hipStreamSynchronize(st));
-        for (uint64_t s = 0; s < ns; s++)
-          if (fm[s] != ~0ull) {
-            TRACE("decode_spec: segmented repair of stream %llu from tile %llu to %llu", (unsigned long long)s,
-                  (unsigned long long)fm[s], (unsigned long long)tp[s + 1]);
-            // the parallel seg_claims' per-tile candidate positions (256 B per tile of the range),
-            // allocated on the first segmented repair that needs more
-            const uint64_t need = std::min<uint64_t>(tp[s + 1] - fm[s], 8192ull * 1024) * 64;
-            if (need > c->ctile_cap) {
-              if (c->ctile) (void)hipFree(c->ctile);
-              c->ctile = nullptr;
-              c->ctile_cap = 0;
-              if (hipMalloc((void **)&c->ctile, need * 4) == hipSuccess) c->ctile_cap = need;
-              else (void)hipGetLastError();
-            }
-            CHK(drp_launch_seg_repair(&P, s, fm[s], tp[s + 1], c->scratch.at<uint64_t>(L.segw), c->ctile, c->ctile_cap,
-                                      st));
-            c->timing.seg_repairs++;
-            full = true;  // (claims rewritten over a range)
-          }
+        if (const int rc = seg_repair(&full)) return rc;
       }
       // a full pass alone; dirty-list passes kChain at a time with one host read at the end
       // (a pass whose input list is empty launches nothing but the memsets)
@@ -758,12 +745,12 @@ int run_decode_spec(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const uin
         V.dlist_n = ctrl + 8 + kn;
         V.pass_id = (uint32_t)(pass + cp + 2);
         if (full) {
-          CHK(drp_launch_spec_verify(&V, NT, ns, tstream, st));
+          CHK(drp_launch_spec_verify(&V, NT, st));
         } else {
           V.vlist = dl[k];
           V.vlist_n = ctrl + 8 + k;
           V.vlist_ovf = ctrl + 10 + k;
-          CHK(drp_launch_spec_verify_list(&V, cp == 0 ? h[8 + k] : ~0ull, ns, tstream, st));
+          CHK(drp_launch_spec_verify_list(&V, cp == 0 ? h[8 + k] : ~0ull, st));
         }
         k = kn;
       }
@@ -780,47 +767,67 @@ int run_decode_spec(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const uin
       }
     }
     TRACE("decode_spec: %d repair pass(es), flags=%#x", pass, h[1]);
-    if (!(h[1] & drp_spec_retry_mask()))  // repaired: emission and results again
-      if (const int rt = launch_tail()) return rt;
+    return DRP_OK;
   }
-  const bool retry = (h[1] & drp_spec_retry_mask()) != 0;
-  if (retry && pass) {  // (the timings then cover the repair passes too, not just the first tail)
-    CHK(hipEventRecord(c->ev[2], st));
-    CHK(hipEventRecord(c->ev[3], st));
-    CHK(hipStreamSynchronize(st));
+
+  // The epilogue: timing, the next decode's change_checks, the DRP_STATS line and the return code.
+  int epilogue(uint32_t relisted) {
+    const bool retry = (h[1] & drp_spec_retry_mask()) != 0;
+    if (retry && pass) {  // (the timings then cover the repair passes too, not just the first tail)
+      CHK(hipEventRecord(c->ev[2], st));
+      CHK(hipEventRecord(c->ev[3], st));
+      CHK(hipStreamSynchronize(st));
+    }
+    if (!retry && c->change_checks_env < 0)  // (h[3]: the call's frames, from stream_counts)
+      c->change_checks = h[3] == 0 || P.nbytes / h[3] >= 512 ? 1 : 0;
+    if (retry) h[1] |= drp_spec_miss_bit();
+    launch_timing(c, (uint32_t)pass, relisted);
+    TRACE("decode_spec done: tiles=%u flags=%#x", h[0], h[1]);
+    if (P.stats) {
+      unsigned long long hs[64];
+      CHK(hipMemcpy(hs, P.stats, sizeof(hs), hipMemcpyDeviceToHost));
+      fprintf(stderr, "[drp-spec] misses=%llu", hs[0]);
+      for (unsigned k = 0; k < 5 && k < hs[0]; k++)
+        fprintf(stderr, " | t=%llu e=%#llx claim=%#llx exit=%#llx", hs[1 + 6 * k], hs[2 + 6 * k], hs[3 + 6 * k],
+                hs[4 + 6 * k]);
+      fprintf(stderr, " walk: synced regions=%llu deaths=%llu first death at %#llx lds=%#llx hbm=%#llx w|lane|o=%#llx", hs[31], hs[32],
+              hs[36], hs[37], hs[38], hs[39]);
+      fprintf(stderr, " sync (lane sums): shape_cyc=%llu rest_cyc=%llu all_cyc=%llu shape_steps=%llu shaped_checks=%llu"
+              " merge_live=%llu merge_chains=%llu general=%llu", hs[33], hs[34], hs[35], hs[40], hs[41], hs[42], hs[43], hs[44]);
+      fprintf(stderr, " repairs=%d (avg cycles per tile) link_rounds=%llu max=%llu tiles_over8=%llu restart_tiles=%llu"
+              " jump_tiles=%llu seg_claims: walk_cycles=%llu frames=%llu tiles=%llu wg_cycles=%llu\n", pass, hs[56],
+              hs[57], hs[58], hs[59], hs[60], hs[61], hs[62], hs[63], hs[55]);
+    }
+    if (h[1] & drp_spec_retry_mask()) return DRP_E_RETRY;
+    if (h[1]) return DRP_E_CAPACITY;
+    return DRP_OK;
   }
-  if (!retry && c->change_checks_env < 0)  // (h[3]: the call's frames, from stream_counts)
-    c->change_checks = h[3] == 0 || nbytes / h[3] >= 512 ? 1 : 0;
-  if (retry) h[1] |= miss;
-  float ms = 0;
-  (void)hipEventElapsedTime(&ms, c->ev[1], c->ev[2]);
-  c->timing.decode_ms = ms;
-  (void)hipEventElapsedTime(&ms, c->ev[0], c->ev[3]);
-  c->timing.total_ms = ms;
-  c->timing.finalize_ms = 0;
-  c->timing.strict_reruns = 0;
-  c->timing.exact_retries = 0;
-  c->timing.spec_repairs = (uint32_t)pass;
-  c->timing.verify_relisted = relisted;
-  TRACE("decode_spec done: tiles=%u flags=%#x", h[0], h[1]);
-  if (dstats) {
-    unsigned long long hs[64];
-    CHK(hipMemcpy(hs, dstats, sizeof(hs), hipMemcpyDeviceToHost));
-    fprintf(stderr, "[drp-spec] misses=%llu", hs[0]);
-    for (unsigned k = 0; k < 5 && k < hs[0]; k++)
-      fprintf(stderr, " | t=%llu e=%#llx claim=%#llx exit=%#llx", hs[1 + 6 * k], hs[2 + 6 * k], hs[3 + 6 * k],
-              hs[4 + 6 * k]);
-    fprintf(stderr, " walk: synced regions=%llu deaths=%llu first death at %#llx lds=%#llx hbm=%#llx w|lane|o=%#llx", hs[31], hs[32],
-            hs[36], hs[37], hs[38], hs[39]);
-    fprintf(stderr, " sync (lane sums): shape_cyc=%llu rest_cyc=%llu all_cyc=%llu shape_steps=%llu shaped_checks=%llu"
-            " merge_live=%llu merge_chains=%llu general=%llu", hs[33], hs[34], hs[35], hs[40], hs[41], hs[42], hs[43], hs[44]);
-    fprintf(stderr, " repairs=%d (avg cycles per tile) link_rounds=%llu max=%llu tiles_over8=%llu restart_tiles=%llu"
-            " jump_tiles=%llu seg_claims: walk_cycles=%llu frames=%llu tiles=%llu wg_cycles=%llu\n", pass, hs[56],
-            hs[57], hs[58], hs[59], hs[60], hs[61], hs[62], hs[63], hs[55]);
+};
+
+// The default decode: speculate-and-verify kernels (drp_decode_spec.hip). Claims and verification,
+// then the prediction check on the host (one flag word) behind the first tail. Returns DRP_E_RETRY
+// when a prediction failed beyond repair (or a bounded wait expired): the caller then runs the
+// exact kernel.
+int run_decode_spec(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const uint64_t *stream_off,
+                    const uint64_t *entry, uint64_t ns, const drp_frames *fr, const drp_changes *co,
+                    uint64_t cap, drp_stream_result *res) {
+  if (((uintptr_t)bytes & 15) != 0) return DRP_E_INVAL;
+  SpecCall D = {c, dec_layout(drp_spec_tile_bytes() / 64, nbytes, ns), ns, fr, co, res};
+  if (!c->scratch.ensure(D.L.total)) return DRP_E_NOMEM;
+  CHK(hipEventRecord(c->ev[0], c->st));
+  D.params(bytes, nbytes, stream_off, entry, cap);
+  if (const int rc = D.clears()) return rc;
+  c->timing.seg_repairs = 0;  // (seg_repair counts them)
+  CHK(hipEventRecord(c->ev[1], c->st));
+  CHK(drp_launch_spec_head(&D.P, D.NT, ns, c->st));  // (verify_counts keeps the relisted count in ctrl[14])
+  if (const int rc = D.tail()) return rc;
+  const uint32_t relisted = D.h[14];
+  if ((D.h[1] & drp_spec_retry_mask()) == drp_spec_miss_bit()) {
+    if (const int rc = D.repair()) return rc;
+    if (!(D.h[1] & drp_spec_retry_mask()))  // repaired: emission and results again
+      if (const int rc = D.tail()) return rc;
   }
-  if (h[1] & drp_spec_retry_mask()) return DRP_E_RETRY;
-  if (h[1]) return DRP_E_CAPACITY;
-  return DRP_OK;
+  return D.epilogue(relisted);
 }
 
 int run_decode(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const uint64_t *stream_off,
@@ -925,6 +932,41 @@ bool stage_aux(drp_ctx *c, StageAux &A) {
   A.dboff = c->aux.at<uint64_t>(stage_meta + sizeof(drp_stream_result));
   return true;
 }
+// a stream's result as decode_stream brings it back
+struct StreamOut {
+  drp_stream_result r;
+  uint64_t boff;  // the payload offset of its last row in the stream's bytes (a cut blob's)
+};
+
+void clear_error(uint64_t *err_frame, uint32_t *err_code, uint32_t *err_detail) {
+  *err_frame = ~0ull;
+  *err_code = DRP_ERR_NONE;
+  *err_detail = 0;
+}
+
+// Rows [first, first + rows) of the `have` staged rows, as a fetch copies them: destination row
+// dst is the first GPU row's (1 when the range begins with the carried blob's row 0, which the
+// host builds), GPU rows [g0, g0 + ng) follow. DRP_E_INVAL: not a range of the staged rows.
+int row_span(const drp_ctx::Staged &S, uint64_t have, uint64_t first, uint64_t rows, uint64_t &dst, uint64_t &g0,
+             uint64_t &ng) {
+  if (first > have || rows > have - first) return DRP_E_INVAL;
+  dst = rows && first == 0 && S.nf0 ? 1 : 0;
+  g0 = first + dst - S.nf0;
+  ng = rows - dst;
+  return DRP_OK;
+}
+
+// one launch sequence's counters added to a sum over pieces (the host-batch fields are the caller's)
+drp_timing &operator+=(drp_timing &s, const drp_timing &t) {
+  s.decode_ms += t.decode_ms;
+  s.total_ms += t.total_ms;
+  s.strict_reruns += t.strict_reruns;
+  s.spec_repairs += t.spec_repairs;
+  s.exact_retries += t.exact_retries;
+  s.verify_relisted += t.verify_relisted;
+  s.seg_repairs += t.seg_repairs;
+  return s;
+}
 
 }  // namespace
 
@@ -936,54 +978,6 @@ int drp_decode_device(drp_ctx *c, const uint8_t *bytes, uint64_t nbytes, const u
   if (!c || !stream_off || !frames || !cols || !results || (!bytes && nbytes)) return DRP_E_INVAL;
   if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
   return run_decode(c, bytes, nbytes, stream_off, entry, nstreams, frames, cols, cap, results);
-}
-
-// drp_decode_batch into caller-owned DEVICE columns: the whole batch is staged and decoded in place.
-static int decode_batch_device_out(drp_ctx *c, const uint8_t *bytes, uint64_t n, drp_carry *carry,
-                                   const drp_frames *frames, const drp_changes *cols, uint64_t cap,
-                                   uint64_t *n_frames, uint64_t *err_frame, uint32_t *err_code,
-                                   uint32_t *err_detail) {
-  carry->frame_bytes = 0;
-  c->staged.rows = 0;
-  c->staged.valid = false;
-  hipStream_t st = c->st;
-  *err_frame = ~0ull;
-  *err_code = DRP_ERR_NONE;
-  *err_detail = 0;
-  const uint64_t brem = carry->blob_remaining, nf0 = brem ? 1 : 0;
-  if (brem) {
-    if (cap < 1) return DRP_E_CAPACITY;
-    Row0 row;
-    const bool done = carried_blob(brem, n, row, carry, n_frames);
-    CHK(hipMemcpyAsync(frames->payload_off, &row.off, 8, hipMemcpyHostToDevice, st));
-    CHK(hipMemcpyAsync(frames->payload_len, &row.len, 4, hipMemcpyHostToDevice, st));
-    CHK(hipMemcpyAsync(frames->type, &row.type, 1, hipMemcpyHostToDevice, st));
-    CHK(hipStreamSynchronize(st));
-    if (done) return DRP_OK;
-  }
-  // input: device & aligned, or staged
-  const uint8_t *dbytes = bytes;
-  StageAux A;
-  if (!stage_aux(c, A)) return DRP_E_NOMEM;
-  if (!is_device_ptr(bytes) || ((uintptr_t)bytes & 15)) {
-    if (!c->in_stage.ensure(n + 64)) return DRP_E_NOMEM;
-    if (n) CHK(hipMemcpyAsync(c->in_stage.p, bytes, n, hipMemcpyDefault, st));
-    dbytes = (const uint8_t *)c->in_stage.p;
-  }
-  uint64_t hv[3] = {0, n, brem};
-  CHK(hipMemcpyAsync(A.soff, hv, 16, hipMemcpyHostToDevice, st));
-  CHK(hipMemcpyAsync(A.ent, hv + 2, 8, hipMemcpyHostToDevice, st));
-  drp_frames dfr;
-  drp_changes dco;
-  rows_at(*frames, *cols, nf0, dfr, dco);
-  const int rc = run_decode(c, dbytes, n, A.soff, A.ent, 1, &dfr, &dco, cap - nf0, A.dres);
-  if (rc != DRP_OK && rc != DRP_E_CAPACITY) return rc;
-  drp_stream_result r;
-  CHK(hipMemcpyAsync(&r, A.dres, sizeof(r), hipMemcpyDeviceToHost, st));
-  CHK(hipStreamSynchronize(st));
-  *n_frames = nf0 + r.frames;
-  finish(r, nf0, 0, n, carry, err_frame, err_code, err_detail);
-  return rc;
 }
 
 constexpr uint64_t kPieceMin = 64 << 10;     // bytes of a blob-skipping piece, at least
@@ -1042,15 +1036,7 @@ static int h2d_range(drp_ctx *c, const HostSrc &H, uint64_t a, uint64_t len, voi
   return DRP_OK;
 }
 
-// Pass-through of in-batch blob payloads (drp_set_blob_skip): bytes [pos, n) of a host batch are
-// staged and decoded piece by piece. A piece ends kPieceMargin past where the next blob header
-// is expected (the distance from a piece's start to its blob header, learned); when the
-// decode of a piece ends inside a blob, the next piece starts after that blob, so the blob's
-// remaining payload is never copied. A piece that ends inside a header or a Change frame is
-// resumed at that frame. The rows of all pieces are consecutive, as a whole-batch decode
-// writes them (a blob the batch holds whole loses the PARTIAL mark its piece gave it).
-// DRP_E_RETRY: the capacity guess was short; the caller stages the batch whole.
-// a piece's stream bounds and entry (no host buffer to keep alive: the values travel as arguments)
+// a one-stream decode's bounds and entry (decode_stream: the values travel as arguments)
 __global__ void piece_meta_kernel(uint64_t *soff, uint64_t *ent, uint64_t n, uint64_t e) {
   soff[0] = 0;
   soff[1] = n;
@@ -1062,8 +1048,35 @@ __global__ void piece_tail_kernel(const drp_stream_result *r, const uint64_t *pa
   *boff = r->frames ? payload_off[r->frames - 1] : 0;
 }
 
+// Copy staged rows [first, first + rows) into host columns.
 static int fetch_staged(drp_ctx *c, const drp_frames *frames, const drp_changes *cols, uint64_t first,
-                        uint64_t rows);
+                        uint64_t rows) {
+  auto &S = c->staged;
+  uint64_t dst, g0, ng;  // destination row, first GPU row, GPU rows
+  if (const int rc = row_span(S, S.rows, first, rows, dst, g0, ng)) return rc;
+  if (!rows) return DRP_OK;
+  hipStream_t st = c->st;
+  if (dst) put_row0(S.row0, *frames);
+  const double t0 = now_ms();
+  if (ng) {
+    void *from[DRP_FETCH_COLS], *to[DRP_FETCH_COLS];
+    col_ptrs(S.fr, S.co, from);
+    col_ptrs(*frames, *cols, to);
+    for (int k = 0; k < DRP_FETCH_COLS; k++) {
+      if (k == kColKeyHash) {  // only when the caller asks for it
+        if (!to[k]) continue;
+        if (!from[k]) return DRP_E_INVAL;  // not computed: drp_set_key_post(ctx, 1) first
+      }
+      const size_t w = kColW[k];
+      CHK(hipMemcpyAsync(static_cast<char *>(to[k]) + dst * w, static_cast<const char *>(from[k]) + g0 * w, ng * w,
+                         hipMemcpyDeviceToHost, st));
+    }
+    CHK(hipStreamSynchronize(st));
+    shift_pieces(S, g0, ng, frames->payload_off + dst, false);
+  }
+  c->timing.d2h_ms = (float)(now_ms() - t0);
+  return DRP_OK;
+}
 
 // staged rows [first, first + rows) into host columns from their row `first` on (fetch_staged
 // writes from row 0)
@@ -1075,85 +1088,318 @@ static int fetch_staged_at(drp_ctx *c, const drp_frames *frames, const drp_chang
   return fetch_staged(c, &f, &o, first, rows);
 }
 
-// An early fetch of pipelined pieces (worker thread): staged GPU rows [g0, g0 + ng) into the host
-// columns from row `dst` on, by DMA into the pinned bounce buffer on the fetch stream (behind
-// c->fev, recorded after the rows' last writes) and a host copy from there; payload offsets made
-// batch offsets per piece as fetch_staged does. The caller sized c->fbounce (fetch_bounce_bytes).
-struct FetchCol {
-  const void *src;
-  void *dst;
-  uint32_t w;
-};
-static int fetch_cols(const drp_ctx *c, const drp_frames *F, const drp_changes *O, FetchCol *col) {
-  void *src[DRP_FETCH_COLS], *dst[DRP_FETCH_COLS];
-  col_ptrs(c->staged.fr, c->staged.co, src);
-  col_ptrs(*F, *O, dst);
-  int n = 0;
-  for (int k = 0; k < DRP_FETCH_COLS; k++)
-    if (src[k] && dst[k]) col[n++] = {src[k], dst[k], kColW[k]};
-  return n;
-}
 constexpr uint64_t kBounceRows = 1 << 20;  // rows per bounce round (14 columns: <= 112 MiB pinned)
 static uint64_t fetch_bounce_bytes(uint64_t ng) { return DRP_FETCH_COLS * al(std::min(ng, kBounceRows) * 8); }
-static int fetch_bounce(drp_ctx *c, uint64_t dst, uint64_t g0, uint64_t ng) {
-  if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
-  FetchCol col[DRP_FETCH_COLS];
-  const int n = fetch_cols(c, c->dfr, c->dco, col);
-  uint8_t *b = static_cast<uint8_t *>(c->fbounce.p);
-  CHK(hipStreamWaitEvent(c->fst, c->fev, 0));
-  for (uint64_t r = 0; r < ng; r += kBounceRows) {
-    const uint64_t m = std::min(kBounceRows, ng - r);
-    uint64_t o = 0;
-    for (int k = 0; k < n; o += al(m * col[k].w), k++)
-      CHK(hipMemcpyAsync(b + o, static_cast<const uint8_t *>(col[k].src) + (g0 + r) * col[k].w, m * col[k].w,
-                         hipMemcpyDeviceToHost, c->fst));
-    CHK(hipStreamSynchronize(c->fst));
-    o = 0;
-    for (int k = 0; k < n; o += al(m * col[k].w), k++)
-      memcpy(static_cast<uint8_t *>(col[k].dst) + (dst + r) * col[k].w, b + o, m * col[k].w);
-  }
-  shift_pieces(c->staged, g0, ng, c->dfr->payload_off + dst, false);
-  return DRP_OK;
-}
 
-static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, drp_carry *carry,
-                        uint64_t *n_frames, uint64_t *err_frame, uint32_t *err_code, uint32_t *err_detail) {
-  hipStream_t st = c->st;
-  // pipelined (pipe): [pbase, n) goes to in_stage (offset 0) by DMA on c->cst, chunk k ending at
-  // pend[k] and signalled by c->pev[k]; each piece ends at a chunk's end. The copy stream is
-  // drained on every way out (its DMAs write into in_stage).
-  uint64_t pbase = 0, jumped = 0;
-  double tf = 0, tw = 0, tb = now_ms();  // (DRP_TRACE: early-fetch and piece-wait host time)
-  int nfetch = 0;
-  // the early fetches (pipe, drp_decode_batch's host columns): one worker thread at a time
-  std::thread fetcher;
-  int fetch_rc = DRP_OK;
-  struct Join {
-    std::thread &t;
-    ~Join() {
-      if (t.joinable()) t.join();
+// The early fetch of a pipelined batch (drp_decode_batch into host columns): while the copy of the
+// later chunks runs, the rows decoded so far go into the caller's columns, by DMA into the pinned
+// bounce buffer on the fetch stream (behind c->fev, recorded after the rows' last writes) and a
+// host copy from there on a worker thread, one fetch at a time. The destructor joins the worker:
+// after an error in stage_pieces that is when drp_decode_batch returns, and nothing the worker
+// reads (the staged columns and pieces, c->fbounce) is written on the way there.
+struct EarlyFetch {
+  drp_ctx *c;
+  const drp_frames *fr;  // the caller's host columns, of `cap` rows
+  const drp_changes *co;
+  uint64_t cap;
+  uint64_t fetched = 0;  // rows already there
+  std::thread worker;
+  int worker_rc = DRP_OK;
+  int n = 0;  // (DRP_TRACE: fetches started, host time spent waiting for the worker)
+  double waited_ms = 0;
+
+  ~EarlyFetch() { (void)join(); }
+  // waits for the fetch in flight; its return code
+  int join() {
+    if (worker.joinable()) {
+      const double t0 = now_ms();
+      worker.join();
+      waited_ms += now_ms() - t0;
     }
-  } join{fetcher};
+    return worker_rc;
+  }
+  // the batch is staged again from its start: nothing fetched counts
+  void reset() {
+    (void)join();
+    worker_rc = DRP_OK;
+    fetched = 0;
+  }
+  // (worker thread) staged GPU rows [g0, g0 + ng) into the columns from row `dst` on; payload
+  // offsets made batch offsets per piece as fetch_staged does. The caller sized c->fbounce.
+  int bounce(uint64_t dst, uint64_t g0, uint64_t ng) const {
+    if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
+    void *src[DRP_FETCH_COLS], *to[DRP_FETCH_COLS];  // (a column both pairs have is copied)
+    col_ptrs(c->staged.fr, c->staged.co, src);
+    col_ptrs(*fr, *co, to);
+    uint8_t *b = static_cast<uint8_t *>(c->fbounce.p);
+    CHK(hipStreamWaitEvent(c->fst, c->fev, 0));
+    for (uint64_t r = 0; r < ng; r += kBounceRows) {
+      const uint64_t m = std::min(kBounceRows, ng - r);
+      uint64_t o = 0;
+      for (int k = 0; k < DRP_FETCH_COLS; k++) {
+        if (!src[k] || !to[k]) continue;
+        const uint64_t w = kColW[k];
+        CHK(hipMemcpyAsync(b + o, static_cast<const uint8_t *>(src[k]) + (g0 + r) * w, m * w, hipMemcpyDeviceToHost,
+                           c->fst));
+        o += al(m * w);
+      }
+      CHK(hipStreamSynchronize(c->fst));
+      o = 0;
+      for (int k = 0; k < DRP_FETCH_COLS; k++) {
+        if (!src[k] || !to[k]) continue;
+        memcpy(static_cast<uint8_t *>(to[k]) + (dst + r) * kColW[k], b + o, m * kColW[k]);
+        o += al(m * kColW[k]);
+      }
+    }
+    shift_pieces(c->staged, g0, ng, fr->payload_off + dst, false);
+    return DRP_OK;
+  }
+  // The staged rows so far (`have`, the carried blob's row included) into the columns, as far as
+  // they hold: queued behind the rows' last writes on c->st, copied while the caller goes on.
+  int rows_upto(uint64_t have) {
+    auto &S = c->staged;
+    const uint64_t upto = std::min(have, cap);
+    if (upto <= fetched) return DRP_OK;
+    if (const int rc = join()) return rc;
+    uint64_t dst, g0, ng;
+    if (const int rc = row_span(S, have, fetched, upto - fetched, dst, g0, ng)) return rc;
+    if (dst) put_row0(S.row0, *fr);  // (the carried blob's row, built on the host)
+    if (ng) {
+      const uint64_t a = fetched + dst;
+      if (c->fbounce.ensure(fetch_bounce_bytes(ng))) {
+        CHK(hipEventRecord(c->fev, c->st));
+        worker = std::thread([this, a, g0, ng] { worker_rc = bounce(a, g0, ng); });
+      } else {  // (no pinned bounce buffer: a direct fetch here)
+        S.rows = have;
+        if (const int rc = fetch_staged_at(c, fr, co, a, ng)) return rc;
+      }
+      n++;
+    }
+    fetched = upto;
+    return DRP_OK;
+  }
+};
+
+// The copy pipeline of a pipelined range: batch bytes [pbase, n) go to in_stage by DMA on c->cst,
+// chunk k ending at batch offset pend[k] and signalled by c->pev[k], c->hev[0..1] around the
+// copies. The copy stream is drained on every way out (its DMAs write into in_stage).
+struct CopyPipe {
+  drp_ctx *c;
   std::vector<uint64_t> pend;
-  size_t pk = 0;
-  struct Drain {
-    drp_ctx *c;
-    const std::vector<uint64_t> &pend;
-    ~Drain() {
-      if (!pend.empty()) (void)hipStreamSynchronize(c->cst);
+  size_t pk = 0;  // the first chunk no piece has waited for yet
+  uint64_t pbase = 0;
+
+  ~CopyPipe() {
+    if (started()) (void)hipStreamSynchronize(c->cst);
+  }
+  bool started() const { return !pend.empty(); }
+  // queues every chunk's copy of flat[pos & ~15, n); base0: the batch offset of in_stage's byte 0
+  int start(const uint8_t *flat, uint64_t pos, uint64_t n, uint64_t base0) {
+    pbase = pos & ~15ull;
+    const uint64_t m = n - pbase;
+    // uniform chunks, then a half and a quarter chunk: the decode and fetch left after the copy
+    // are a quarter chunk's (each piece's decode hides behind the next, shorter copy)
+    const uint64_t chunk =
+        (std::max(c->pipe_chunk, (m + kPipeEvents - 3) / (kPipeEvents - 2)) + 0xFFFF) & ~0xFFFFull;
+    const uint64_t t2 = (n - chunk / 4) & ~0xFFFFull, t1 = (n - 3 * chunk / 4) & ~0xFFFFull;
+    for (uint64_t e = pbase + chunk; e < t1; e += chunk) pend.push_back(e);
+    if (t1 > pbase) pend.push_back(t1);
+    if (t2 > t1) pend.push_back(t2);
+    pend.push_back(n);
+    CHK(hipEventRecord(c->hev[0], c->cst));
+    for (size_t k = 0; k < pend.size(); k++) {
+      if (!c->pev[k]) CHK(hipEventCreateWithFlags(&c->pev[k], hipEventDisableTiming));
+      const uint64_t lo = k ? pend[k - 1] : pbase;
+      CHK(hipMemcpyAsync(c->in_stage.at<uint8_t>(lo - base0), flat + lo, pend[k] - lo, hipMemcpyHostToDevice,
+                         c->cst));
+      CHK(hipEventRecord(c->pev[k], c->cst));
     }
-  } drain{c, pend};
-  auto &S = c->staged;
+    CHK(hipEventRecord(c->hev[1], c->cst));
+    TRACE("stage: pipelined from %llu in %zu chunks of %llu B", (unsigned long long)pbase, pend.size(),
+          (unsigned long long)chunk);
+    return DRP_OK;
+  }
+  // the next piece: to the end (*pe) of the first chunk past pos and past the last piece's end,
+  // which st waits for
+  int next(uint64_t pos, hipStream_t st, uint64_t *pe) {
+    while (pk < pend.size() && pend[pk] <= pos) pk++;
+    if (pk == pend.size()) return DRP_E_HIP;  // (unreachable: pos < n)
+    *pe = pend[pk];
+    CHK(hipStreamWaitEvent(st, c->pev[pk], 0));
+    pk++;
+    return DRP_OK;
+  }
+  // waits for the last copy; adds the copies' time
+  int finish(float *h2d_ms) {
+    if (!started()) return DRP_OK;
+    CHK(hipStreamSynchronize(c->cst));
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, c->hev[0], c->hev[1]) == hipSuccess) *h2d_ms += ms;
+    return DRP_OK;
+  }
+};
+
+// Decode one stream (bytes [0, m) at dbytes, entered at `entry`) into columns of `cap` rows and
+// bring its result back, with one host wait behind the decode's own: the bounds and the entry
+// travel as kernel arguments (no host buffer to keep alive), and the payload offset of the last
+// row, a cut blob's, comes back with the result. DRP_E_CAPACITY: the result (without that offset).
+static int decode_stream(drp_ctx *c, const uint8_t *dbytes, uint64_t m, uint64_t entry,
+                         const drp_frames *fr, const drp_changes *co, uint64_t cap, StreamOut *out) {
+  hipStream_t st = c->st;
   StageAux A;
   if (!stage_aux(c, A)) return DRP_E_NOMEM;
-  const uint64_t n = H.n;
-  uint64_t copied = 0;
-  const uint64_t cap = stage_cap(c, n - pos);
+  hipLaunchKernelGGL(piece_meta_kernel, dim3(1), dim3(1), 0, st, A.soff, A.ent, m, entry);
+  CHK(hipGetLastError());
+  const int rc = run_decode(c, dbytes, m, A.soff, A.ent, 1, fr, co, cap, A.dres);
+  if (rc != DRP_OK && rc != DRP_E_CAPACITY) return rc;
+  if (rc == DRP_OK) {  // (r.frames <= cap: the last row is in the columns)
+    hipLaunchKernelGGL(piece_tail_kernel, dim3(1), dim3(1), 0, st, A.dres, fr->payload_off, A.dboff);
+    CHK(hipGetLastError());
+  }
+  CHK(hipMemcpyAsync(out, A.dres, sizeof(*out), hipMemcpyDeviceToHost, st));
+  CHK(hipStreamSynchronize(st));
+  return rc;
+}
+
+// drp_decode_batch into caller-owned DEVICE columns: the whole batch is staged and decoded in place.
+static int decode_batch_device_out(drp_ctx *c, const uint8_t *bytes, uint64_t n, drp_carry *carry,
+                                   const drp_frames *frames, const drp_changes *cols, uint64_t cap,
+                                   uint64_t *n_frames, uint64_t *err_frame, uint32_t *err_code,
+                                   uint32_t *err_detail) {
+  carry->frame_bytes = 0;
+  c->staged.rows = 0;
+  c->staged.valid = false;
+  hipStream_t st = c->st;
+  clear_error(err_frame, err_code, err_detail);
+  const uint64_t brem = carry->blob_remaining, nf0 = brem ? 1 : 0;
+  if (brem) {
+    if (cap < 1) return DRP_E_CAPACITY;
+    Row0 row;
+    const bool done = carried_blob(brem, n, row, carry, n_frames);
+    CHK(hipMemcpyAsync(frames->payload_off, &row.off, 8, hipMemcpyHostToDevice, st));
+    CHK(hipMemcpyAsync(frames->payload_len, &row.len, 4, hipMemcpyHostToDevice, st));
+    CHK(hipMemcpyAsync(frames->type, &row.type, 1, hipMemcpyHostToDevice, st));
+    CHK(hipStreamSynchronize(st));
+    if (done) return DRP_OK;
+  }
+  // input: device & aligned, or staged
+  const uint8_t *dbytes = bytes;
+  if (!is_device_ptr(bytes) || ((uintptr_t)bytes & 15)) {
+    if (!c->in_stage.ensure(n + 64)) return DRP_E_NOMEM;
+    if (n) CHK(hipMemcpyAsync(c->in_stage.p, bytes, n, hipMemcpyDefault, st));
+    dbytes = (const uint8_t *)c->in_stage.p;
+  }
+  drp_frames dfr;
+  drp_changes dco;
+  rows_at(*frames, *cols, nf0, dfr, dco);
+  StreamOut o;
+  const int rc = decode_stream(c, dbytes, n, brem, &dfr, &dco, cap - nf0, &o);
+  if (rc != DRP_OK && rc != DRP_E_CAPACITY) return rc;
+  *n_frames = nf0 + o.r.frames;
+  finish(o.r, nf0, 0, n, carry, err_frame, err_code, err_detail);
+  return rc;
+}
+
+// The piece loop's state and steps (stage_pieces).
+struct Pieces {
+  drp_ctx *c;
+  const HostSrc &H;
+  bool pipe;  // the rest of the batch is copied in chunks while it is decoded (CopyPipe)
+  drp_carry *carry;
+  uint64_t *err_frame;
+  uint32_t *err_code, *err_detail;
+  uint64_t pos, pos0;  // the next piece's first byte; the first piece's
+  uint64_t want;       // the next piece's length; doubled within this batch after each piece that met no blob
+  uint64_t npieces = 0, span_now = 0;  // (span_now: batch bytes per piece so far)
+  uint64_t rows = 0, bad = 0;          // (bad: a failing Change's row, kept behind the frames)
+  uint64_t staged = 0, skipped = 0, jumped = 0, copied = 0;
+  float h2d_ms = 0;
+  double t_begin = now_ms();  // (DRP_TRACE)
+  drp_timing sum = {};  // (run_decode describes one launch sequence: the call's timing is the sum over its pieces)
+
+  // Dense blobs in a flat batch (AUTO): the rest in one piece, pipelined when it qualifies.
+  void plan_rest() {
+    if (pipe || !H.flat || c->blob_skip != DRP_BLOB_SKIP_AUTO) return;
+    const uint64_t span = npieces >= kPieceProbe ? span_now : c->piece_span, rest = H.n - pos;
+    if (span && rest / span > kPieceBudget) {
+      want = rest;
+      pipe = c->pipe_chunk && rest >= 2 * c->pipe_chunk && is_pinned_host(H.flat);
+    }
+  }
+
+  // A piece [ps, pe) decoded to result o: the batch's outcome when it ends the batch (*done), else
+  // where the next piece starts. When the decode of a piece ends inside a blob, the next piece starts
+  // after that blob; a piece that ends inside a header or a Change frame is resumed at that frame.
+  int advance(const StreamOut &o, uint64_t ps, uint64_t pe, bool *done) {
+    auto &S = c->staged;
+    const drp_stream_result &r = o.r;
+    const uint64_t n = H.n;
+    *done = true;
+    if (r.err_code || pe == n) {  // the batch's end or its error: this piece's tail is the batch's
+      finish(r, S.nf0 + rows, ps, n, carry, err_frame, err_code, err_detail);
+      rows += kept_rows(r);
+      bad = kept_rows(r) - r.frames;
+      return DRP_OK;
+    }
+    rows += r.frames;
+    if (r.tail_kind != DRP_TAIL_BLOB) {
+      // no blob reached: resume at the frame the piece cut (or its end), with a longer piece
+      const uint64_t np = r.tail_kind == DRP_TAIL_NONE ? pe : ps + r.consumed;
+      want *= 2;
+      if (np > pos) pos = np;
+    } else {
+      const uint64_t bend = pe + r.blob_remaining;  // the blob's end in the batch
+      c->blob_run = ps + o.boff - pos;              // (where this piece's blob payload began)
+      want = std::max(kPieceMin, c->blob_run + kPieceMargin);
+      (pipe ? jumped : skipped) += std::min(bend, n) - pe;
+      if (bend <= n)  // the batch holds the whole blob: its row is not partial
+        CHK(hipMemsetAsync(S.fr.type + rows - 1, DRP_TYPE_BLOB, 1, c->st));
+      if (bend >= n) {  // the blob ends the batch, or continues past it: the carry says how far
+        carry->blob_remaining = bend - n;
+        carry->consumed = n;
+        carry->tail_kind = bend > n ? DRP_TAIL_BLOB : DRP_TAIL_NONE;
+        if (bend == n) span_now = (n - pos0) / npieces;
+        return DRP_OK;
+      }
+      pos = bend;
+    }
+    span_now = (pos - pos0) / npieces;
+    *done = false;
+    return DRP_OK;
+  }
+
+  // The batch's timing, what the ctx learns from it for the next batch, and its row counts.
+  void end(uint64_t *n_frames) {
+    auto &S = c->staged;
+    c->timing = sum;
+    c->timing.h2d_ms = h2d_ms;
+    c->timing.h2d_bytes = staged;
+    c->timing.h2d_skipped = skipped;
+    c->timing.host_copied = copied;
+    if (span_now) c->piece_span = span_now;
+    c->blob_heavy = (skipped + jumped) * 4 >= H.n;  // (AUTO: keep skipping while it pays)
+    c->frames_per_byte = (double)rows / (double)(H.n - S.pieces[0].second);
+    S.rows = S.nf0 + rows;
+    *n_frames = S.nf0 + rows - bad;
+    S.good = *n_frames - S.nf0;
+  }
+};
+
+// Pass-through of in-batch blob payloads (drp_set_blob_skip): bytes [pos, n) of a host batch are
+// staged and decoded piece by piece. A piece ends kPieceMargin past where the next blob header
+// is expected (the distance from a piece's start to its blob header, learned), or, pipelined
+// (pipe: the whole rest copied in chunks while it is decoded), at a chunk's end. The blob payload
+// behind a piece's end is never copied. The rows of all pieces are consecutive, as a whole-batch
+// decode writes them (a blob the batch holds whole loses the PARTIAL mark its piece gave it).
+// DRP_E_RETRY: the capacity guess was short; the caller stages the batch whole.
+static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, EarlyFetch *ef, drp_carry *carry,
+                        uint64_t *n_frames, uint64_t *err_frame, uint32_t *err_code, uint32_t *err_detail) {
+  hipStream_t st = c->st;
+  CopyPipe cp{c};
+  auto &S = c->staged;
+  const uint64_t n = H.n, cap = stage_cap(c, n - pos);
   if (!c->dec_cols.ensure(carve_bytes(cap))) return DRP_E_NOMEM;
-  // every piece is staged at its own batch offset (from base0 on), so the Changes of the whole
-  // batch stay on the device for drp_relay_staged; the skipped blob payloads are holes never
-  // written or read
-  const uint64_t base0 = pos & ~15ull;
+  const uint64_t base0 = pos & ~15ull;  // (every piece at its own batch offset from here on: Staged::wire)
   if (!c->in_stage.ensure(n - base0 + 64)) return DRP_E_NOMEM;
   S.wire = static_cast<const uint8_t *>(c->in_stage.p);
   S.wire_bytes = n - base0;
@@ -1162,212 +1408,71 @@ static int stage_pieces(drp_ctx *c, const HostSrc &H, uint64_t pos, bool pipe, d
   if (c->key_post != DRP_KEY_POST_HASH) S.co.key_hash = nullptr;
   S.cap = cap;
   S.pieces.clear();
-  uint64_t rows = 0, bad = 0, staged = 0, skipped = 0;  // (bad: a failing Change's row, kept behind the frames)
-  // the next piece: kPieceMargin past where the last blob seen suggests the next blob header is;
-  // doubled within this batch after each piece that met no blob
-  uint64_t want = std::max(kPieceMin, c->blob_run + kPieceMargin);
-  const uint64_t pos0 = pos;
-  uint64_t npieces = 0, span_now = 0;  // (span_now: batch bytes per piece so far)
-  float h2d_ms = 0;
-  drp_timing sum = {};
-  // (per piece, one wait for the decode's verification and one for its result: the H2D, the
-  // piece's bounds and the blob row's type are queued on the stream)
-  struct {
-    drp_stream_result r;
-    uint64_t boff;  // the cut blob's payload offset in the piece (tail BLOB)
-  } hr;
-  drp_stream_result &r = hr.r;
-  for (;;) {
-    if (!pipe && H.flat && c->blob_skip == DRP_BLOB_SKIP_AUTO) {  // dense blobs in a flat batch: the rest in one piece
-      const uint64_t span = npieces >= kPieceProbe ? span_now : c->piece_span;
-      if (span && (n - pos) / span > kPieceBudget) {
-        want = n - pos;
-        pipe = c->pipe_chunk && n - pos >= 2 * c->pipe_chunk && is_pinned_host(H.flat);
-      }
+  Pieces W{c, H, pipe, carry, err_frame, err_code, err_detail, pos, pos};
+  W.want = std::max(kPieceMin, c->blob_run + kPieceMargin);  // (past where the last blob seen suggests the next header)
+  for (bool done = false; !done;) {
+    // plan: the piece [ps, pe), its bytes on their way to in_stage
+    W.plan_rest();
+    if (W.pipe && !cp.started()) {  // (the compute stream is idle here: every piece ends in a wait)
+      if (const int rc = cp.start(H.flat, W.pos, n, base0)) return rc;
+      W.staged += n - cp.pbase;
+      S.pieces.emplace_back(W.rows, cp.pbase);
     }
-    if (pipe && pend.empty()) {  // (the compute stream is idle here: every piece ends in a wait)
-      pbase = pos & ~15ull;
-      const uint64_t m = n - pbase;
-      // uniform chunks, then a half and a quarter chunk: the decode and fetch left after the copy
-      // are a quarter chunk's (each piece's decode hides behind the next, shorter copy)
-      const uint64_t chunk =
-          (std::max(c->pipe_chunk, (m + kPipeEvents - 3) / (kPipeEvents - 2)) + 0xFFFF) & ~0xFFFFull;
-      const uint64_t t2 = (n - chunk / 4) & ~0xFFFFull, t1 = (n - 3 * chunk / 4) & ~0xFFFFull;
-      for (uint64_t e = pbase + chunk; e < t1; e += chunk) pend.push_back(e);
-      if (t1 > pbase) pend.push_back(t1);
-      if (t2 > t1) pend.push_back(t2);
-      pend.push_back(n);
-      CHK(hipEventRecord(c->hev[0], c->cst));
-      for (size_t k = 0; k < pend.size(); k++) {
-        if (!c->pev[k]) CHK(hipEventCreateWithFlags(&c->pev[k], hipEventDisableTiming));
-        const uint64_t lo = k ? pend[k - 1] : pbase;
-        CHK(hipMemcpyAsync(c->in_stage.at<uint8_t>(lo - base0), H.flat + lo, pend[k] - lo, hipMemcpyHostToDevice,
-                           c->cst));
-        CHK(hipEventRecord(c->pev[k], c->cst));
-      }
-      CHK(hipEventRecord(c->hev[1], c->cst));
-      TRACE("stage: pipelined from %llu in %zu chunks of %llu B", (unsigned long long)pbase, pend.size(),
-            (unsigned long long)chunk);
-      staged += m;
-      S.pieces.emplace_back(rows, pbase);
-    }
-    uint64_t pe, ps, mp;
-    const uint8_t *dp;
-    if (pipe) {  // to the end of the first chunk past pos (and past the last piece's end)
-      while (pk < pend.size() && pend[pk] <= pos) pk++;
-      if (pk == pend.size()) return DRP_E_HIP;  // (unreachable: pos < n)
-      pe = pend[pk];
-      ps = pos & ~15ull;
-      mp = pe - ps;
-      dp = c->in_stage.at<uint8_t>(ps - base0);
-      CHK(hipStreamWaitEvent(st, c->pev[pk], 0));
-      pk++;
-      hipLaunchKernelGGL(piece_meta_kernel, dim3(1), dim3(1), 0, st, A.soff, A.ent, mp, pos - ps);
-      CHK(hipGetLastError());
+    const uint64_t ps = W.pos & ~15ull;
+    uint8_t *dp = c->in_stage.at<uint8_t>(ps - base0);
+    uint64_t pe;
+    if (W.pipe) {
+      if (const int rc = cp.next(W.pos, st, &pe)) return rc;
     } else {
-      pe = std::min(n, pos + want);
-      ps = pos & ~15ull;
-      mp = pe - ps;
-      dp = c->in_stage.at<uint8_t>(ps - base0);
+      pe = std::min(n, W.pos + W.want);
       CHK(hipEventRecord(c->hev[0], st));
-      if (const int rc = h2d_range(c, H, ps, mp, c->in_stage.at<uint8_t>(ps - base0), st, &copied)) return rc;
-      hipLaunchKernelGGL(piece_meta_kernel, dim3(1), dim3(1), 0, st, A.soff, A.ent, mp, pos - ps);
-      CHK(hipGetLastError());
+      if (const int rc = h2d_range(c, H, ps, pe - ps, dp, st, &W.copied)) return rc;
       CHK(hipEventRecord(c->hev[1], st));
-      staged += mp;
+      W.staged += pe - ps;
     }
-    npieces++;
+    W.npieces++;
+    // decode it behind the rows so far (one wait for the decode's verification, one for its result)
     drp_frames fr;
     drp_changes co;
-    rows_at(S.fr, S.co, rows, fr, co);
-    const int rc = run_decode(c, dp, mp, A.soff, A.ent, 1, &fr, &co, cap - rows, A.dres);
+    rows_at(S.fr, S.co, W.rows, fr, co);
+    StreamOut o;
+    const int rc = decode_stream(c, dp, pe - ps, W.pos - ps, &fr, &co, cap - W.rows, &o);
     if (rc == DRP_E_CAPACITY) return DRP_E_RETRY;
     if (rc != DRP_OK) return rc;
-    // (run_decode describes one launch sequence: the call's timing is the sum over its pieces)
-    sum.decode_ms += c->timing.decode_ms;
-    sum.total_ms += c->timing.total_ms;
-    sum.strict_reruns += c->timing.strict_reruns;
-    sum.spec_repairs += c->timing.spec_repairs;
-    sum.exact_retries += c->timing.exact_retries;
-    sum.verify_relisted += c->timing.verify_relisted;
-    sum.seg_repairs += c->timing.seg_repairs;
-    hipLaunchKernelGGL(piece_tail_kernel, dim3(1), dim3(1), 0, st, A.dres, fr.payload_off, A.dboff);
-    CHK(hipGetLastError());
-    CHK(hipMemcpyAsync(&hr, A.dres, sizeof(hr), hipMemcpyDeviceToHost, st));
-    {
-      const double t0 = now_ms();
-      CHK(hipStreamSynchronize(st));
-      tw += now_ms() - t0;
-    }
-    const uint64_t boff = hr.boff;
-    if (pipe) {  // the pipelined range is one piece: its rows' payload offsets from pbase
-      const uint64_t nr = kept_rows(r);
-      if (nr && ps > pbase) {
+    W.sum += c->timing;
+    if (W.pipe) {  // the pipelined range is one piece: its rows' payload offsets from pbase
+      const uint64_t nr = kept_rows(o.r);
+      if (nr && ps > cp.pbase) {
         const uint32_t g = (uint32_t)std::min<uint64_t>((nr + 255) / 256, 1024);
-        hipLaunchKernelGGL(piece_shift_kernel, dim3(g), dim3(256), 0, st, fr.payload_off, nr, ps - pbase);
+        hipLaunchKernelGGL(piece_shift_kernel, dim3(g), dim3(256), 0, st, fr.payload_off, nr, ps - cp.pbase);
         CHK(hipGetLastError());
       }
-      S.dev = c->in_stage.at<uint8_t>(pbase - base0);
+      S.dev = c->in_stage.at<uint8_t>(cp.pbase - base0);
     } else {
       float ms = 0;
-      if (hipEventElapsedTime(&ms, c->hev[0], c->hev[1]) == hipSuccess) h2d_ms += ms;
-      S.pieces.emplace_back(rows, ps);
+      if (hipEventElapsedTime(&ms, c->hev[0], c->hev[1]) == hipSuccess) W.h2d_ms += ms;
+      S.pieces.emplace_back(W.rows, ps);
       S.dev = dp;
     }
-    if (r.err_code || pe == n) {  // the batch's end or its error: this piece's tail is the batch's
-      finish(r, S.nf0 + rows, ps, n, carry, err_frame, err_code, err_detail);
-      rows += kept_rows(r);
-      bad = kept_rows(r) - r.frames;
-      break;
-    }
-    rows += r.frames;
-    if (r.tail_kind == DRP_TAIL_BLOB) {
-      const uint64_t bend = pe + r.blob_remaining;  // the blob's end in the batch
-      c->blob_run = ps + boff - pos;                // (where this piece's blob payload began)
-      want = std::max(kPieceMin, c->blob_run + kPieceMargin);
-      if (bend <= n) {  // the batch holds the whole blob: its row is not partial
-        CHK(hipMemsetAsync(S.fr.type + rows - 1, DRP_TYPE_BLOB, 1, st));
-        (pipe ? jumped : skipped) += bend - pe;
-        pos = bend;
-        span_now = (pos - pos0) / npieces;
-        if (pos == n) {
-          carry->blob_remaining = 0;
-          carry->consumed = n;
-          carry->tail_kind = DRP_TAIL_NONE;
-          break;
-        }
-      } else {  // the blob continues past the batch: the carry says how far
-        (pipe ? jumped : skipped) += n - pe;
-        carry->blob_remaining = bend - n;
-        carry->consumed = n;
-        carry->tail_kind = DRP_TAIL_BLOB;
-        break;
-      }
-    } else {
-      // no blob reached: resume at the frame the piece cut (or its end), with a longer piece
-      const uint64_t np = r.tail_kind == DRP_TAIL_NONE ? pe : ps + r.consumed;
-      want *= 2;
-      if (np > pos) pos = np;
-      span_now = (pos - pos0) / npieces;
-    }
-    if (pipe && c->dfr) {  // the rows so far into drp_decode_batch's host columns, while the copy runs
-      const uint64_t upto = std::min(S.nf0 + rows, c->dcap);
-      if (upto > c->dfetched) {
-        const double t0 = now_ms();
-        if (fetcher.joinable()) fetcher.join();
-        tf += now_ms() - t0;
-        if (fetch_rc) return fetch_rc;
-        uint64_t a = c->dfetched;
-        if (a == 0 && S.nf0) {  // (the carried blob's row, built on the host)
-          put_row0(S.row0, *c->dfr);
-          a = 1;
-        }
-        if (upto > a) {
-          const uint64_t g0 = a - S.nf0, ng = upto - a;
-          if (c->fbounce.ensure(fetch_bounce_bytes(ng))) {
-            CHK(hipEventRecord(c->fev, st));
-            fetcher = std::thread([c, a, g0, ng, &fetch_rc] { fetch_rc = fetch_bounce(c, a, g0, ng); });
-          } else {  // (no pinned bounce buffer: a direct fetch here)
-            S.rows = S.nf0 + rows;
-            if (const int rc = fetch_staged_at(c, c->dfr, c->dco, a, ng)) return rc;
-          }
-          nfetch++;
-        }
-        c->dfetched = upto;
-      }
-    }
+    // its result: the batch's outcome, or the next piece's start
+    if (const int rc = W.advance(o, ps, pe, &done)) return rc;
+    // the rows so far into drp_decode_batch's host columns, while the copy runs
+    if (!done && W.pipe && ef)
+      if (const int rc = ef->rows_upto(S.nf0 + W.rows)) return rc;
   }
-  if (fetcher.joinable()) {
-    const double t0 = now_ms();
-    fetcher.join();
-    tf += now_ms() - t0;
-  }
-  if (fetch_rc) return fetch_rc;
-  c->timing = sum;
-  if (span_now) c->piece_span = span_now;
-  if (!pend.empty()) {
-    CHK(hipStreamSynchronize(c->cst));
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, c->hev[0], c->hev[1]) == hipSuccess) h2d_ms += ms;
-  }
-  c->timing.h2d_ms = h2d_ms;
-  TRACE("stage: %llu pieces in %.2f ms (h2d %.2f): %d early fetches (%.2f ms waited for), result waits %.2f ms",
-        (unsigned long long)npieces, now_ms() - tb, h2d_ms, nfetch, tf, tw);
-  c->timing.h2d_bytes = staged;
-  c->timing.h2d_skipped = skipped;
-  c->timing.host_copied = copied;
-  c->blob_heavy = (skipped + jumped) * 4 >= n;  // (AUTO: keep skipping while it pays)
-  c->frames_per_byte = (double)rows / (double)(n - S.pieces[0].second);
-  S.rows = S.nf0 + rows;
-  *n_frames = S.nf0 + rows - bad;
-  S.good = *n_frames - S.nf0;
+  if (ef)
+    if (const int rc = ef->join()) return rc;
+  if (const int rc = cp.finish(&W.h2d_ms)) return rc;
+  TRACE("stage: %llu pieces in %.2f ms (h2d %.2f): %d early fetches (%.2f ms waited for)",
+        (unsigned long long)W.npieces, now_ms() - W.t_begin, W.h2d_ms, ef ? ef->n : 0, ef ? ef->waited_ms : 0.0);
+  W.end(n_frames);
   return DRP_OK;
 }
 
 // Decode a host batch (bytes [a, n), a = the 16-byte-aligned start of the bytes after a leading
 // blob continuation) into the ctx's device columns. The frame capacity starts at a guess and is
 // grown to the exact count when the first launch overflows it (the count is exact either way).
-static int stage_batch(drp_ctx *c, const HostSrc &H, drp_carry *carry, uint64_t *n_frames,
+static int stage_batch(drp_ctx *c, const HostSrc &H, EarlyFetch *ef, drp_carry *carry, uint64_t *n_frames,
                        uint64_t *err_frame, uint32_t *err_code, uint32_t *err_detail) {
   hipStream_t st = c->st;
   const uint64_t n = H.n;
@@ -1377,9 +1482,7 @@ static int stage_batch(drp_ctx *c, const HostSrc &H, drp_carry *carry, uint64_t 
   S.pieces.clear();
   S.wire = nullptr;
   S.wire_bytes = S.base = S.good = 0;
-  *err_frame = ~0ull;
-  *err_code = DRP_ERR_NONE;
-  *err_detail = 0;
+  clear_error(err_frame, err_code, err_detail);
   carry->frame_bytes = 0;
   c->timing.h2d_bytes = 0;
   c->timing.h2d_skipped = 0;
@@ -1405,13 +1508,11 @@ static int stage_batch(drp_ctx *c, const HostSrc &H, drp_carry *carry, uint64_t 
     // (AUTO: a ctx's first batch probes in pieces too; pieces grow geometrically while no blob
     // is met, so a batch without blobs costs a few more launches once)
     const drp_carry in = *carry;
-    const int rc = stage_pieces(c, H, brem, pipe, carry, n_frames, err_frame, err_code, err_detail);
+    const int rc = stage_pieces(c, H, brem, pipe, ef, carry, n_frames, err_frame, err_code, err_detail);
     if (rc != DRP_E_RETRY) return rc;
-    c->dfetched = 0;
+    if (ef) ef->reset();
     *carry = in;  // (capacity: staged whole below)
-    *err_frame = ~0ull;
-    *err_code = DRP_ERR_NONE;
-    *err_detail = 0;
+    clear_error(err_frame, err_code, err_detail);
     S.pieces.clear();
   }
   // the continuation's payload bytes are pass-through: only [a, n) goes to the device
@@ -1429,23 +1530,17 @@ static int stage_batch(drp_ctx *c, const HostSrc &H, drp_carry *carry, uint64_t 
     h2d_ms = (float)(now_ms() - t0);
     dbytes = (const uint8_t *)c->in_stage.p;
   }
-  StageAux A;
-  if (!stage_aux(c, A)) return DRP_E_NOMEM;
-  uint64_t hv[3] = {0, m, brem - a};
-  CHK(hipMemcpyAsync(A.soff, hv, 16, hipMemcpyHostToDevice, st));
-  CHK(hipMemcpyAsync(A.ent, hv + 2, 8, hipMemcpyHostToDevice, st));
   uint64_t cap = stage_cap(c, m);
-  drp_stream_result r;
+  StreamOut o;
+  const drp_stream_result &r = o.r;
   int rc = DRP_OK;
   for (int attempt = 0; attempt < 2; attempt++) {
     if (!c->dec_cols.ensure(carve_bytes(cap))) return DRP_E_NOMEM;
     carve(c->dec_cols, cap, S.fr, S.co);
     if (c->key_post != DRP_KEY_POST_HASH) S.co.key_hash = nullptr;
     S.cap = cap;
-    rc = run_decode(c, dbytes, m, A.soff, A.ent, 1, &S.fr, &S.co, cap, A.dres);
+    rc = decode_stream(c, dbytes, m, brem - a, &S.fr, &S.co, cap, &o);
     if (rc != DRP_OK && rc != DRP_E_CAPACITY) return rc;
-    CHK(hipMemcpyAsync(&r, A.dres, sizeof(r), hipMemcpyDeviceToHost, st));
-    CHK(hipStreamSynchronize(st));
     if (rc == DRP_OK) break;
     // The chain held more frames than the guess. Rows needed: the delivered frames plus a
     // malformed Change. When they fit, the result is complete (a malformed Change inside the
@@ -1463,6 +1558,8 @@ static int stage_batch(drp_ctx *c, const HostSrc &H, drp_carry *carry, uint64_t 
   if (host_in && c->blob_skip == DRP_BLOB_SKIP_AUTO && r.blobs) {
     // the batch's blob payload bytes: mostly blobs -> the next batches are staged in pieces
     uint64_t bb = 0;
+    StageAux A;
+    if (!stage_aux(c, A)) return DRP_E_NOMEM;
     CHK(hipMemsetAsync(A.bsum, 0, 8, st));
     CHK(drp_launch_blob_bytes(S.fr.type, S.fr.payload_len, r.frames, A.bsum, st));
     CHK(hipMemcpyAsync(&bb, A.bsum, 8, hipMemcpyDeviceToHost, st));
@@ -1489,48 +1586,13 @@ static int stage_batch(drp_ctx *c, const HostSrc &H, drp_carry *carry, uint64_t 
 
 // A staged decode of a host batch, whole or in pieces: the batch the fetch and relay calls serve
 // from now on (staged.seq), held (staged.valid) when the decode succeeded.
-static int stage_decode(drp_ctx *c, const HostSrc &H, drp_carry *carry, uint64_t *n_frames,
+static int stage_decode(drp_ctx *c, const HostSrc &H, EarlyFetch *ef, drp_carry *carry, uint64_t *n_frames,
                         uint64_t *err_frame, uint32_t *err_code, uint32_t *err_detail) {
   c->staged.valid = false;
   c->staged.seq++;
-  const int rc = stage_batch(c, H, carry, n_frames, err_frame, err_code, err_detail);
+  const int rc = stage_batch(c, H, ef, carry, n_frames, err_frame, err_code, err_detail);
   c->staged.valid = rc == DRP_OK;
   return rc;
-}
-
-// Copy staged rows [first, first + rows) into host columns.
-static int fetch_staged(drp_ctx *c, const drp_frames *frames, const drp_changes *cols, uint64_t first,
-                        uint64_t rows) {
-  auto &S = c->staged;
-  if (first > S.rows || rows > S.rows - first) return DRP_E_INVAL;
-  if (!rows) return DRP_OK;
-  hipStream_t st = c->st;
-  uint64_t dst = 0;  // destination row
-  if (first == 0 && S.nf0) {
-    put_row0(S.row0, *frames);
-    dst = 1;
-  }
-  const uint64_t g0 = first + dst - S.nf0;  // first GPU row
-  const uint64_t ng = rows - dst;
-  const double t0 = now_ms();
-  if (ng) {
-    void *from[DRP_FETCH_COLS], *to[DRP_FETCH_COLS];
-    col_ptrs(S.fr, S.co, from);
-    col_ptrs(*frames, *cols, to);
-    for (int k = 0; k < DRP_FETCH_COLS; k++) {
-      if (k == kColKeyHash) {  // only when the caller asks for it
-        if (!to[k]) continue;
-        if (!from[k]) return DRP_E_INVAL;  // not computed: drp_set_key_post(ctx, 1) first
-      }
-      const size_t w = kColW[k];
-      CHK(hipMemcpyAsync(static_cast<char *>(to[k]) + dst * w, static_cast<const char *>(from[k]) + g0 * w, ng * w,
-                         hipMemcpyDeviceToHost, st));
-    }
-    CHK(hipStreamSynchronize(st));
-    shift_pieces(S, g0, ng, frames->payload_off + dst, false);
-  }
-  c->timing.d2h_ms = (float)(now_ms() - t0);
-  return DRP_OK;
 }
 
 // drp_decode_fetch_block: the staged columns' rows packed into the caller's block layout on the
@@ -1574,13 +1636,12 @@ int drp_decode_fetch_block_ex(drp_ctx *c, void *block, uint64_t block_bytes, con
   if (rows && is_device_ptr(block)) return DRP_E_INVAL;
   if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
   auto &S = c->staged;
-  if (first > S.rows || rows > S.rows - first) return DRP_E_INVAL;
+  uint64_t dst, g0, ng;  // (dst: a carried blob row, set on the host below)
+  if (const int rc = row_span(S, S.rows, first, rows, dst, g0, ng)) return rc;
   if (kh && !S.co.key_hash) return DRP_E_INVAL;  // not computed: drp_set_key_post(ctx, 1) first
   if (!rows) return DRP_OK;
   uint8_t *B = static_cast<uint8_t *>(block);
   const double t0 = now_ms();
-  const uint64_t dst = first == 0 && S.nf0 ? 1 : 0;  // (a carried blob row: set on the host below)
-  const uint64_t g0 = first + dst - S.nf0, ng = rows - dst;
   if (ng) {
     if (!c->fetch_tmp.ensure(block_bytes)) return DRP_E_NOMEM;
     void *src[DRP_FETCH_COLS];
@@ -1653,12 +1714,11 @@ int drp_decode_fetch_keys(drp_ctx *c, uint64_t first, uint64_t rows, uint32_t *k
   if (!c || !kp || !text_len || (!text && text_cap)) return DRP_E_INVAL;
   if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
   auto &S = c->staged;
-  if (first > S.rows || rows > S.rows - first) return DRP_E_INVAL;
+  uint64_t dst, g0, ng;  // (dst: a carried blob row, no key)
+  if (const int rc = row_span(S, S.rows, first, rows, dst, g0, ng)) return rc;
   if (!S.valid || S.pieces.size() != 1 || !S.dev || c->key_post == DRP_KEY_POST_OFF) return DRP_E_INVAL;
   *text_len = 0;
   if (!rows) return DRP_OK;
-  const uint64_t dst = first == 0 && S.nf0 ? 1 : 0;  // (a carried blob row: no key)
-  const uint64_t g0 = first + dst - S.nf0, ng = rows - dst;
   if (dst) kp[0] = 0;
   if (!ng) return DRP_OK;
   hipStream_t st = c->st;
@@ -1704,7 +1764,7 @@ int drp_decode_stage(drp_ctx *c, const uint8_t *bytes, uint64_t n, drp_carry *ca
   HostSrc H;
   H.flat = bytes;
   H.n = n;
-  return stage_decode(c, H, carry, n_frames, err_frame, err_code, err_detail);
+  return stage_decode(c, H, nullptr, carry, n_frames, err_frame, err_code, err_detail);
 }
 
 int drp_decode_stage_v(drp_ctx *c, const drp_chunk *chunks, uint64_t nchunks, drp_carry *carry, uint64_t *n_frames,
@@ -1724,7 +1784,7 @@ int drp_decode_stage_v(drp_ctx *c, const drp_chunk *chunks, uint64_t nchunks, dr
   }
   if (hipSetDevice(c->device) != hipSuccess) return DRP_E_HIP;
   HostSrc E;
-  return stage_decode(c, H.n ? H : E, carry, n_frames, err_frame, err_code, err_detail);
+  return stage_decode(c, H.n ? H : E, nullptr, carry, n_frames, err_frame, err_code, err_detail);
 }
 
 int drp_decode_fetch(drp_ctx *c, const drp_frames *frames, const drp_changes *cols, uint64_t first, uint64_t rows) {
@@ -1748,17 +1808,12 @@ int drp_decode_batch(drp_ctx *c, const uint8_t *bytes, uint64_t n, drp_carry *ca
   HostSrc H;
   H.flat = bytes;
   H.n = n;
-  c->dfr = frames;
-  c->dco = cols;
-  c->dcap = cap;
-  c->dfetched = 0;
-  int rc = stage_decode(c, H, carry, n_frames, err_frame, err_code, err_detail);
-  c->dfr = nullptr;
-  c->dco = nullptr;
+  EarlyFetch ef{c, frames, cols, cap};  // (pipelined pieces fetch their rows during the copy)
+  int rc = stage_decode(c, H, &ef, carry, n_frames, err_frame, err_code, err_detail);
   c->key_post = key_post;
   if (rc != DRP_OK) return rc;
   const uint64_t rows = c->staged.rows, upto = rows < cap ? rows : cap;
-  rc = fetch_staged_at(c, frames, cols, c->dfetched, upto > c->dfetched ? upto - c->dfetched : 0);
+  rc = fetch_staged_at(c, frames, cols, ef.fetched, upto > ef.fetched ? upto - ef.fetched : 0);
   if (rc != DRP_OK) return rc;
   return rows > cap ? DRP_E_CAPACITY : DRP_OK;
 }

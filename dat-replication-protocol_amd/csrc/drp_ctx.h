@@ -102,15 +102,6 @@ struct drp_ctx {
   hipStream_t fst = nullptr;
   hipEvent_t fev = nullptr;
   drp::PinBuf fbounce;
-  // the speculative decode's side stream: the emitters of the tiles without records and
-  // stream_counts run on it beside emit_recs, for batches of at least side_min tiles (DRP_SIDE_MIN;
-  // 0: always, a huge value: never). Stream and events are created by the first decode that forks.
-  // Off unless asked for: the kernels do overlap, but emit_recs slows by what they save (C2 and C4
-  // within 0.03 ms of the one-stream order, inside the noise, at every threshold tried; DESIGN.md,
-  // round 9).
-  hipStream_t sst = nullptr;
-  hipEvent_t sev[2] = {};  // fork, join
-  uint64_t side_min = ~0ull;
   uint64_t pipe_chunk = 128ull << 20;  // DRP_PIPE_CHUNK (MiB; 0: no pipelining)
   uint32_t B = 128;
   int strict = 0;
@@ -154,11 +145,6 @@ struct drp_ctx {
   uint64_t blob_run = 0;       // bytes from a piece's start to its blob's payload, last seen
   uint64_t piece_span = 0;     // batch bytes one blob-skipping piece covered on average, last seen
   drp_timing timing = {};
-  // drp_decode_batch's host columns while it stages (pipelined pieces fetch their rows into them
-  // during the copy; dfetched: rows already there)
-  const drp_frames *dfr = nullptr;
-  const drp_changes *dco = nullptr;
-  uint64_t dcap = 0, dfetched = 0;
   std::vector<uint64_t> host_tmp;
   // fan-out: the filter table on its way to the device (page-locked; fan_ev: the copy of the last
   // call has left it), and drp_fanout_staged's selected rows and splice ranks

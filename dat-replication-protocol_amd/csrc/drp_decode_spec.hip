@@ -3876,16 +3876,14 @@ extern "C" uint32_t drp_spec_cascade_bit(void) { return spec::F_CASCADE; }
 // Claims and verification only (the host checks the prediction before anything is emitted).
 
 extern "C" hipError_t drp_launch_spec_head(const DecodeParams *P, uint64_t nt_max, uint64_t nstreams,
-                                           uint32_t *tile_stream, hipStream_t st) {
+                                           hipStream_t st) {
   if (nt_max == 0) return hipSuccess;
-  DecodeParams Q = *P;
-  Q.tile_stream = nullptr;
-  if (nstreams > 1) {
+  DecodeParams Q = *P;  // (the claims form below may change its walk_* members)
+  if (P->tile_stream) {  // (set for more than one stream: filled here, read by every later launch)
     const uint32_t blk = 256;
     hipLaunchKernelGGL(spec::tile_stream_kernel, dim3((uint32_t)((nt_max + blk - 1) / blk)), dim3(blk), 0, st,
-                       P->tile_prefix, nstreams, nt_max, tile_stream);
+                       P->tile_prefix, nstreams, nt_max, const_cast<uint32_t *>(P->tile_stream));
     drp_dbg_mark("tile_stream_kernel", st);
-    Q.tile_stream = tile_stream;
   }
   // interior tiles in the fast form (or by the region walkers); the edge and dense tiles they list
   // in the general one
@@ -3942,39 +3940,29 @@ extern "C" hipError_t drp_launch_spec_head(const DecodeParams *P, uint64_t nt_ma
       fclose(f);
     }
   }
-  return drp_launch_spec_verify(&Q, nt_max, nstreams, tile_stream, st);  // (sets the same Q.tile_stream)
+  return drp_launch_spec_verify(&Q, nt_max, st);
 }
 
 // A verify pass over every tile: the head's, and one more over the repaired claims (the caller
 // clears incl_e and the flags first).
-extern "C" hipError_t drp_launch_spec_verify(const DecodeParams *P, uint64_t nt_max, uint64_t nstreams,
-                                             uint32_t *tile_stream, hipStream_t st) {
+extern "C" hipError_t drp_launch_spec_verify(const DecodeParams *P, uint64_t nt_max, hipStream_t st) {
   if (nt_max == 0) return hipSuccess;
-  DecodeParams Q = *P;
-  Q.tile_stream = nstreams > 1 ? tile_stream : nullptr;
-  if (Q.vlist) {  // records-only verification, verify_counts on the tiles it lists (caller zeroes vlist_n)
-    const uint64_t nb = (nt_max * spec::VL_G + spec::VL_BLK - 1) / spec::VL_BLK;
-    hipLaunchKernelGGL(spec::verify_lite, dim3((uint32_t)nb), dim3(spec::VL_BLK), 0, st, Q);
-    drp_dbg_mark("verify_lite", st);
-    hipLaunchKernelGGL(spec::verify_counts, dim3((uint32_t)(nt_max < 16384 ? nt_max : 16384)), dim3(spec::NT), 0, st,
-                       Q);
-    drp_dbg_mark("verify_counts", st);
-  } else {
-    hipLaunchKernelGGL(spec::verify_counts, dim3((uint32_t)nt_max), dim3(spec::NT), 0, st, Q);
-    drp_dbg_mark("verify_counts", st);
-  }
+  // records-only verification, then verify_counts on the tiles it lists (the caller zeroes vlist_n)
+  const uint64_t nb = (nt_max * spec::VL_G + spec::VL_BLK - 1) / spec::VL_BLK;
+  hipLaunchKernelGGL(spec::verify_lite, dim3((uint32_t)nb), dim3(spec::VL_BLK), 0, st, *P);
+  drp_dbg_mark("verify_lite", st);
+  hipLaunchKernelGGL(spec::verify_counts, dim3((uint32_t)(nt_max < 16384 ? nt_max : 16384)), dim3(spec::NT), 0, st,
+                     *P);
+  drp_dbg_mark("verify_counts", st);
   return hipGetLastError();
 }
 
 // A repair pass over the tiles the previous pass listed (P->vlist / P->vlist_n: its dirty list,
 // n entries), appending to P->dlist.
-extern "C" hipError_t drp_launch_spec_verify_list(const DecodeParams *P, uint64_t n, uint64_t nstreams,
-                                                  uint32_t *tile_stream, hipStream_t st) {
+extern "C" hipError_t drp_launch_spec_verify_list(const DecodeParams *P, uint64_t n, hipStream_t st) {
   if (n == 0) return hipSuccess;  // (n = ~0: the count is on the device only)
-  DecodeParams Q = *P;
-  Q.tile_stream = nstreams > 1 ? tile_stream : nullptr;
   const uint64_t g = n == ~0ull ? 1024 : (n < 16384 ? n : 16384);
-  hipLaunchKernelGGL(spec::verify_counts, dim3((uint32_t)g), dim3(spec::NT), 0, st, Q);
+  hipLaunchKernelGGL(spec::verify_counts, dim3((uint32_t)g), dim3(spec::NT), 0, st, *P);
   drp_dbg_mark("verify_counts", st);
   return hipGetLastError();
 }
@@ -3994,8 +3982,8 @@ extern "C" hipError_t drp_launch_tile_scan2(const DecodeParams *P, uint64_t nstr
   S.nch_base = P->tile_nch_base;
   S.cap = P->cap;
   S.overflow = P->overflow;
-  S.vlist_n = P->vlist ? P->vlist_n : nullptr;
-  S.rec_on = P->vlist && P->rec ? P->counter + 13 : nullptr;
+  S.vlist_n = P->vlist_n;
+  S.rec_on = P->rec ? P->counter + 13 : nullptr;
   S.chunk_tile = P->chunk_tile;
   const uint32_t nb = (uint32_t)((nt_max + spec::SCAN_SPAN - 1) / spec::SCAN_SPAN);
   if (nb == 1) {  // (small batches: one launch; a staged piece pays each launch's host cost)
@@ -4009,38 +3997,21 @@ extern "C" hipError_t drp_launch_tile_scan2(const DecodeParams *P, uint64_t nstr
 }
 
 // Everything after verification: the output and change-count bases (one scan, which also zeroes
-// the deferred-tile count and marks emit_recs' chunks), emission, stream counts. With a side
-// stream (side != null: the caller's choice by batch size) the emitters of the few tiles without
-// records and stream_counts run there, forked behind the scan and joined before this returns,
-// beside emit_recs on st: their rows are disjoint from its rows (emit_sparse takes tile_sparse
-// tiles, which have no records; emit_lean skips both marks; emit_tiles takes emit_lean's list).
+// the deferred-tile count and marks emit_recs' chunks), emission, stream counts, all on st. The
+// emitters' rows are disjoint: emit_sparse takes tile_sparse tiles, which have no records; emit_recs
+// the tiles with records; emit_lean skips both marks; emit_tiles takes the tiles emit_lean lists.
 extern "C" hipError_t drp_launch_spec_tail(const DecodeParams *P, uint64_t nt_max, uint64_t nstreams,
-                                           uint32_t *tile_stream, uint64_t *scan_tmp, hipStream_t st,
-                                           const DrpSide *side) {
+                                           uint64_t *scan_tmp, hipStream_t st) {
   if (nt_max == 0) return hipSuccess;
-  DecodeParams Q = *P;
-  Q.tile_stream = nstreams > 1 ? tile_stream : nullptr;
-  hipError_t e = drp_launch_tile_scan2(&Q, nstreams, nt_max, scan_tmp, st);
+  DecodeParams Q = *P;  // (tile_sparse is cleared below when the sparse form is compiled out)
+  const hipError_t e = drp_launch_tile_scan2(&Q, nstreams, nt_max, scan_tmp, st);
   if (e != hipSuccess) return e;
   drp_dbg_mark("tile_scan", st);
-  if (!Q.vlist) {  // every tile in the general form
-    hipLaunchKernelGGL(spec::emit_tiles, dim3((uint32_t)nt_max), dim3(spec::NT), 0, st, Q);
-    drp_dbg_mark("emit_tiles", st);
-    return drp_launch_stream_counts(Q.tile_prefix, nstreams, Q.tile_count, Q.tile_base, Q.tile_nch, Q.tile_nch_base,
-                                    Q.scount, st, Q.counter + 3);
-  }
   // the fast kernels, then the general one on the tiles emit_lean lists
-  hipStream_t ss = st;
-  if (side) {
-    e = hipEventRecord(side->fork, st);
-    if (e == hipSuccess) e = hipStreamWaitEvent(side->st, side->fork, 0);
-    if (e != hipSuccess) return e;
-    ss = side->st;
-  }
   if (spec::SP_FRAMES && Q.tile_sparse) {  // sparse tiles first (no staging), then every other tile
     hipLaunchKernelGGL(spec::emit_sparse, dim3((uint32_t)((nt_max + spec::SP_TPB - 1) / spec::SP_TPB)), dim3(256), 0,
-                       ss, Q);
-    drp_dbg_mark("emit_sparse", ss);
+                       st, Q);
+    drp_dbg_mark("emit_sparse", st);
   } else {
     Q.tile_sparse = nullptr;
   }
@@ -4053,18 +4024,12 @@ extern "C" hipError_t drp_launch_spec_tail(const DecodeParams *P, uint64_t nt_ma
   hipLaunchKernelGGL(spec::emit_lean,
                      dim3((uint32_t)(Q.change_checks || Q.rec ? (nt_max + spec::EMIT_LONG_TPW - 1) / spec::EMIT_LONG_TPW
                                                               : nt_max)),
-                     dim3(spec::NT), 0, ss, Q);
-  drp_dbg_mark("emit_fast", ss);
-  hipLaunchKernelGGL(spec::emit_tiles, dim3((uint32_t)(nt_max < 16384 ? nt_max : 16384)), dim3(spec::NT), 0, ss, Q);
-  drp_dbg_mark("emit_tiles", ss);
-  e = drp_launch_stream_counts(Q.tile_prefix, nstreams, Q.tile_count, Q.tile_base, Q.tile_nch, Q.tile_nch_base,
-                               Q.scount, ss, Q.counter + 3);
-  if (side) {  // (joined even after a failed launch: st never runs ahead of the side stream's work)
-    hipError_t j = hipEventRecord(side->join, ss);
-    if (j == hipSuccess) j = hipStreamWaitEvent(st, side->join, 0);
-    if (e == hipSuccess) e = j;
-  }
-  return e;
+                     dim3(spec::NT), 0, st, Q);
+  drp_dbg_mark("emit_fast", st);
+  hipLaunchKernelGGL(spec::emit_tiles, dim3((uint32_t)(nt_max < 16384 ? nt_max : 16384)), dim3(spec::NT), 0, st, Q);
+  drp_dbg_mark("emit_tiles", st);
+  return drp_launch_stream_counts(Q.tile_prefix, nstreams, Q.tile_count, Q.tile_base, Q.tile_nch, Q.tile_nch_base,
+                                  Q.scount, st, Q.counter + 3);
 }
 
 extern "C" hipError_t drp_launch_blob_bytes(const uint8_t *type, const uint32_t *plen, uint64_t n, uint64_t *out,

@@ -48,7 +48,7 @@ struct DecodeParams {
   uint64_t *incl_e;    // entry of tile t + 1
   uint64_t *agg_n;     // exact frames of tile t + 1
   uint64_t *incl_n;    // frames of tiles <= t + 1
-  const uint32_t *tile_stream;  // tile -> stream (null: one stream)
+  const uint32_t *tile_stream;  // tile -> stream (null: one stream; drp_launch_spec_head fills it)
   uint8_t *ent;                 // [tile][thread]: entry offset in the thread's 64 B, 0xFF none
   uint8_t *ent_n, *ent_c;       // [tile][thread]: frames / change frames from that entry
   uint32_t *work;               // tiles for the general claims kernel (edge / dense tiles)
@@ -57,6 +57,7 @@ struct DecodeParams {
   uint64_t *tile_nch_base;      //  same-address atomics per tile serialise across the XCDs)
   // verify_lite: tiles it leaves to verify_counts, and each tile's first entry thread (emit skips
   // the threads before it); null: verify_counts verifies every tile
+  // (the host always sets vlist: the kernels' null forms are kept only so their code does not change)
   uint32_t *vlist, *vlist_n;
   uint8_t *tile_k;
   // per tile: 1 when the tile is sparse (every thread from tile_k on delivers at most one frame,
@@ -423,26 +424,16 @@ uint32_t drp_spec_cascade_bit(void);
 hipError_t drp_launch_claims_walk(const drp::DecodeParams *P, uint64_t nt_max, hipStream_t st);
 uint32_t drp_walk_tiles_per_region(uint64_t nt_max, int hop);
 hipError_t drp_launch_walk_density(const drp::DecodeParams *P, hipStream_t st);
-hipError_t drp_launch_spec_head(const drp::DecodeParams *P, uint64_t nt_max, uint64_t nstreams,
-                                uint32_t *tile_stream, hipStream_t st);
+hipError_t drp_launch_spec_head(const drp::DecodeParams *P, uint64_t nt_max, uint64_t nstreams, hipStream_t st);
 // out[0] = payload bytes of the blob rows among rows [0, n) (out zeroed by the caller)
 hipError_t drp_launch_blob_bytes(const uint8_t *type, const uint32_t *plen, uint64_t n, uint64_t *out, hipStream_t st);
 // ctile: 64 u32 per tile of the range (seg_claims_par; null or too small: the serial seg_claims)
 hipError_t drp_launch_seg_repair(const drp::DecodeParams *P, uint64_t s, uint64_t t0, uint64_t tl, uint64_t *scratch,
                                  uint32_t *ctile, uint64_t ctile_cap, hipStream_t st);
-hipError_t drp_launch_spec_verify(const drp::DecodeParams *P, uint64_t nt_max, uint64_t nstreams,
-                                  uint32_t *tile_stream, hipStream_t st);
-hipError_t drp_launch_spec_verify_list(const drp::DecodeParams *P, uint64_t n, uint64_t nstreams,
-                                       uint32_t *tile_stream, hipStream_t st);
-// the tail's side stream (drp_ctx: created on first use) and the events that fork it off the
-// decode stream and join it again
-struct DrpSide {
-  hipStream_t st;
-  hipEvent_t fork, join;
-};
-// side: null keeps every launch on st
-hipError_t drp_launch_spec_tail(const drp::DecodeParams *P, uint64_t nt_max, uint64_t nstreams,
-                                uint32_t *tile_stream, uint64_t *scan_tmp, hipStream_t st, const DrpSide *side);
+hipError_t drp_launch_spec_verify(const drp::DecodeParams *P, uint64_t nt_max, hipStream_t st);
+hipError_t drp_launch_spec_verify_list(const drp::DecodeParams *P, uint64_t n, hipStream_t st);
+hipError_t drp_launch_spec_tail(const drp::DecodeParams *P, uint64_t nt_max, uint64_t nstreams, uint64_t *scan_tmp,
+                                hipStream_t st);
 // the tail's scan: tile_count -> tile_base (capacity check) and tile_nch -> tile_nch_base in one
 // pass, which also zeroes vlist_n and writes emit_recs' chunk_tile marks; tmp: 2 block-sum arrays
 hipError_t drp_launch_tile_scan2(const drp::DecodeParams *P, uint64_t nstreams, uint64_t nt_max, uint64_t *tmp,

@@ -1,6 +1,6 @@
-"""Helpers of the tail tests (test_gpu_tail_chain.py, test_gpu_dual_scan.py): a context with the
-side stream forced or disabled and records on or off, and a device decode of cut streams checked
-against per-stream oracle decodes."""
+"""Helpers of the tail tests (test_gpu_tail_chain.py, test_gpu_dual_scan.py): a context with
+claims_fast's records on or off, and a device decode of cut streams checked against per-stream
+oracle decodes."""
 import ctypes as C
 import os
 
@@ -8,12 +8,10 @@ import numpy as np
 
 import _oracle as O
 
-SIDE = {"side": "0", "main": str(1 << 62)}  # DRP_SIDE_MIN, in tiles
 
-
-def tail_ctx(side, rec, **env):
+def tail_ctx(rec, **env):
     from _gpu import drp_amd
-    env = {"DRP_SIDE_MIN": SIDE[side], "DRP_CREC": str(rec), **env}
+    env = {"DRP_CREC": str(rec), **env}
     keep = {k: os.environ.get(k) for k in env}
     os.environ.update(env)
     try:

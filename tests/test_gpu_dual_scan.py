@@ -6,16 +6,15 @@ matter. A scan block covers 4096 tiles. The largest case has ~4200 tiles: one st
 sums (scan_top2's second array, bsum[gridDim.x + blockIdx.x]) reach the streams' results. The
 launcher picks its form by its bound on the tile count (bytes / 8192 + 2 * streams + 2): the next
 two cases sit on either side of it (4097: reduce, top and down; 4096: the one-block launch); the
-smallest decodes are three streams sharing two tiles, and one stream of one tile. Every case runs
-in the one-stream order and with the side stream forced. (Capacity overflow:
-tests/test_gpu_change_matrix.py.)"""
+smallest decodes are three streams sharing two tiles, and one stream of one tile. (Capacity
+overflow: tests/test_gpu_change_matrix.py.)"""
 import functools
 
 import numpy as np
 import pytest
 
 import _streams as S
-from _tail import SIDE, device_decode_check, stream_refs, tail_ctx
+from _tail import device_decode_check, stream_refs, tail_ctx
 
 pytestmark = pytest.mark.gpu
 
@@ -63,9 +62,9 @@ SIZES = {"two_blocks": (MAX_BYTES, (near_tile(4000), near_tile(4130))),
 BOUND = {"bound_4097": 4097, "bound_4096": 4096}  # the launcher's tile bound at those sizes
 
 
-@pytest.fixture(scope="module", params=list(SIDE))
-def ctx(request):
-    c = tail_ctx(request.param, 1)
+@pytest.fixture(scope="module")
+def ctx():
+    c = tail_ctx(1)
     yield c
     c.close()
 

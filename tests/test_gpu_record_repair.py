@@ -46,13 +46,13 @@ def whole(k):
 
 @pytest.fixture(scope="module")
 def ctxs():
-    """Contexts by (side, records, environment), opened once (tests/_tail.tail_ctx)."""
+    """Contexts by (records, environment), opened once (tests/_tail.tail_ctx)."""
     cache = {}
 
-    def get(side="main", rec=1, **env):
-        key = (side, rec, tuple(sorted(env.items())))
+    def get(rec=1, **env):
+        key = (rec, tuple(sorted(env.items())))
         if key not in cache:
-            cache[key] = tail_ctx(side, rec, **env)
+            cache[key] = tail_ctx(rec, **env)
         return cache[key]
     yield get
     for c in cache.values():
@@ -198,7 +198,7 @@ def test_full_pass_by_identity_run(ctxs, k):
 def stats_decode(wire, ref, label):
     """One decode on a context opened with DRP_STATS=1 (it prints the first five misses to stderr)."""
     from _gpu import assert_same
-    c = tail_ctx("main", 1, DRP_STATS="1")
+    c = tail_ctx(1, DRP_STATS="1")
     try:
         g = c.decode_batch(wire)
     finally:
@@ -247,10 +247,9 @@ def cut_case(where):
     return wire, cuts, entry, stream_refs(wire, cuts, entry), nrows
 
 
-@pytest.mark.parametrize("side", ["main", "side"])
 @pytest.mark.parametrize("where", ["host", "before"])
-def test_three_streams(ctxs, where, side):
-    device_decode_check(ctxs(side=side), *cut_case(where))
+def test_three_streams(ctxs, where):
+    device_decode_check(ctxs(), *cut_case(where))
 
 
 @pytest.mark.parametrize("name", CASCADE_NAMES)
@@ -262,16 +261,10 @@ def test_staged_pieces(ctxs, name):
     assert_same(g, oracle(cascade, name), f"staged {name}")
 
 
-@pytest.mark.parametrize("name", CASCADE_NAMES)
-def test_side_stream(ctxs, name):
-    t = check(ctxs(side="side"), cascade, name)
-    assert t.spec_repairs >= 4 and t.seg_repairs >= 1
-
-
 def test_exact_kernel_cross_check():
     """The exact decode (no prediction, no records) of the cascade wire: the oracle's rows too."""
     from _gpu import assert_same
-    c = tail_ctx("main", 1)
+    c = tail_ctx(1)
     try:
         c.set_exact(True)
         assert_same(c.decode_batch(cascade("two")[0]), oracle(cascade, "two"), "exact")

@@ -1,10 +1,9 @@
 """GPU parity of the speculative decode's tail (drp_launch_spec_tail, drp_decode_spec.hip) against
 the oracle: one scan gives the row bases and the change-count bases before emission, zeroes the
-deferred-tile count and marks emit_recs' chunks; emit_sparse, emit_lean, emit_tiles and
-stream_counts then run on the context's side stream beside emit_recs, or behind it on the decode
-stream. Every case runs with the side stream forced (DRP_SIDE_MIN=0) and disabled, and with
-claims_fast's records on and off (DRP_CREC), so that the side emitters own rows in every batch
-(records off: every tile's; records on: the tiles that refuse records)."""
+deferred-tile count and marks emit_recs' chunks; emit_sparse, emit_recs, emit_lean, emit_tiles and
+stream_counts then run behind it on the decode stream. Every case runs with claims_fast's records
+on and off (DRP_CREC), so that the emitters beside emit_recs own rows in every batch (records off:
+every tile's; records on: the tiles that refuse records)."""
 import functools
 import random
 
@@ -12,17 +11,13 @@ import pytest
 
 import _oracle as O
 import _streams as S
-from _tail import SIDE, cut_entries, device_decode_check, stream_refs, tail_ctx
+from _tail import cut_entries, device_decode_check, stream_refs, tail_ctx
 
 pytestmark = pytest.mark.gpu
 
-MODES = [(s, r) for s in SIDE for r in (1, 0)]
-IDS = [f"{s}-rec{r}" for s, r in MODES]
-
-
-@pytest.fixture(scope="module", params=MODES, ids=IDS)
+@pytest.fixture(scope="module", params=(1, 0), ids=("rec1", "rec0"))
 def ctx(request):
-    c = tail_ctx(*request.param)
+    c = tail_ctx(request.param)
     yield c
     c.close()
 
@@ -77,16 +72,14 @@ def test_mixed_batch(ctx):
 
 def test_failed_prediction(ctx):
     """Two framings that never merge: the first tail does nothing (the emitters see the miss flag),
-    repair passes clear and refill the lists, and the tail runs a second time with the same fork
-    and join."""
+    repair passes clear and refill the lists, and the tail runs a second time."""
     check(ctx, shadow_wire, "shadow")
     assert ctx.timing().spec_repairs > 0
 
 
-def test_stale_side_stream_state(ctx):
+def test_stale_scan_sums_chunk_marks_and_deferred_list(ctx):
     """X, Y, X on one context, X and Y of different tile counts: the scan's block sums, the chunk
-    marks, the deferred-tile list and the side stream's events are all left over from the decode
-    before."""
+    marks and the deferred-tile list are all left over from the decode before."""
     assert len(mixed_wire()) // 8192 != len(other_wire()) // 8192
     for k, fn in enumerate([mixed_wire, other_wire, mixed_wire]):
         check(ctx, fn, f"stale{k}")
@@ -104,6 +97,6 @@ def cut_case():
 
 
 def test_device_decode_of_many_streams(ctx):
-    """~150 streams cut at arbitrary bytes: stream_counts on the side stream reads the change-count
-    bases that the scan wrote before emission."""
+    """~150 streams cut at arbitrary bytes: stream_counts reads the change-count bases that the scan
+    wrote before emission."""
     device_decode_check(ctx, *cut_case())
